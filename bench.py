@@ -19,9 +19,14 @@ ranks is used.  extra.c2_and_weak keeps the weak-scaling form (an independent pa
 rank).  At N = 1, extra.rank_slice_ms times on this GPU what rank r of N = 2 / 4 / 8
 does per step, for C2 and C3 uniform.
 
-Prints ONE JSON line (rank 0).  Extra fields:
+Prints ONE JSON line (rank 0).  A plain run (`bench.py --gpus N --steps K --warmup W`) does only what
+the headline needs: it generates the pair, settles and warms up, times the K steps and prints the
+headline fields with the roofline of the timed steps themselves.  `--dump-outputs DIR` then writes what
+the last timed step computed (the serialized result, see _dump_outputs).  Everything else below runs
+only under `--full`, after the timed steps (passes of their own, other workloads, the CPU legs):
   roofline     - dominant kernel (container compute) achieved algorithmic GB/s vs
                  the 8 TB/s HBM peak, timed with HIP events on the engine's stream
+                 (--full adds standalone_kernel_ms from a separate profiled pass)
   cpu_baseline - the CPU oracle (C++ restatement of the reference, not the JVM: no JDK here) on
                  this host, legs for C1-C5 (BASELINE.md §2 protocol: 5 warmup + 5 measured
                  iterations, median; ParallelAggregation legs on cores - 1 workers)
@@ -29,7 +34,7 @@ Prints ONE JSON line (rank 0).  Extra fields:
                  result assembled on GPU 0), C4, C5, runOptimize, decode
 
 `python bench.py --gpus N` without a launcher re-runs itself under torch.distributed.run with N
-ranks; `--only W` runs one workload alone (per-workload rocprofv3 --pmc passes).
+ranks; `--only W` runs one workload alone (per-workload rocprofv3 --pmc passes) and needs no --full.
 """
 import argparse
 import hashlib
@@ -770,6 +775,37 @@ def _relaunch(args):
     sys.exit(subprocess.call(cmd, env=env))
 
 
+DUMP_HEAD = 1 << 20    # leading bytes of the serialized result written whole (cookie, descriptors, offset table)
+DUMP_SAMPLE = 8 << 20  # byte positions of the sample (float32: 32 MiB)
+
+
+def _dump_outputs(outdir, blob, rs):
+    """--dump-outputs: what the last timed step computed, as DIR/<name>.npy (float32 / float64, < 64 MB).
+
+    The step ends at the serialized result in device memory; `blob` is that buffer's bytes (what
+    Engine.fetch hands a caller), rs the engine's result_stats of the same step.  The bytes are written
+    as float32 values 0..255: the first DUMP_HEAD bytes whole, and the bytes at DUMP_SAMPLE positions
+    drawn once from a fixed seed (every byte when the result is shorter); the size and the sha256 of
+    all bytes go with them, so two builds that differ anywhere differ in serialized_sha256."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    u8 = np.frombuffer(blob, dtype=np.uint8)
+    if u8.size > DUMP_SAMPLE:
+        pos = np.sort(np.random.default_rng(0xD0C2).integers(0, u8.size, DUMP_SAMPLE))
+        sample = u8[pos]
+    else:
+        sample = u8
+    digest = np.frombuffer(hashlib.sha256(blob).digest(), dtype=np.uint8)
+    out = {"serialized_head": u8[:DUMP_HEAD].astype(np.float32),
+           "serialized_sample": sample.astype(np.float32),
+           "serialized_sha256": digest.astype(np.float32),
+           "serialized_size": np.array([u8.size], dtype=np.float64),
+           "result_stats": np.array([rs["containers"], rs["payload_bytes"], rs["has_run"], rs["cardinality"]],
+                                    dtype=np.float64)}
+    for name, arr in out.items():
+        np.save(os.path.join(outdir, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -777,6 +813,12 @@ def main():
     # a 0.32 ms step instead of 15 us at 20 steps
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything beside the headline: the per-phase and "
+                         "serialization passes, the other workloads and configurations (extra), the CPU baseline "
+                         "legs; the options below other than --only and --backend apply to it")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps write what the last one computed as DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=24.0, help="bounded CPU-baseline budget (all legs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--c3-n", type=int, default=10000, help="bitmaps of the C3 wide-OR workloads (0 = skip)")
@@ -826,7 +868,8 @@ def main():
     eng.pairwise("and", a, b)
     rs = eng.result_stats()
     out_bytes = rs["payload_bytes"] + 4 * rs["containers"]
-    rs["sha16"] = hashlib.sha256(eng.fetch().serialize()).hexdigest()[:16]  # of the serialized result
+    if args.full:
+        rs["sha16"] = hashlib.sha256(eng.fetch().serialize()).hexdigest()[:16]  # of the serialized result
 
     stream = torch.cuda.ExternalStream(eng.stream_ptr)
     strong = world > 1
@@ -839,7 +882,7 @@ def main():
         def c2_step():  # this rank's key range of ONE pair -> its slice at its global place -> one bitmap on GPU 0
             eng.pairwise("and", a, b, key_lo=key_lo, key_hi=key_hi)
             dshard.place()
-            dshard.gather()  # rank 0 receives every slice at its place: the step ends, like N = 1, with one bitmap
+            return dshard.gather()  # rank 0 receives every slice at its place: like N = 1, the step ends at one bitmap
     elif PIPELINED:
         def c2_step():  # RoaringBitmap.and(x1, x2) + serialize as one pipeline (rbg_ctx_pairwise_serialized):
             eng.pairwise_serialized("and", a, b)  # key range r placed and copied while range r + 1 computes
@@ -878,8 +921,9 @@ def main():
     eng.profile(args.steps, compute_only=not PIPELINED)
     t0 = time.perf_counter()
     ev0.record(stream)
+    last = None
     for _ in range(args.steps):
-        c2_step()
+        last = c2_step()
     ev1.record(stream)
     eng.sync()
     barrier()
@@ -888,6 +932,57 @@ def main():
     n_live, ph_live = eng.profile_read()
     eng.profile(0)
     ph_live = [x / max(n_live, 1) for x in ph_live]
+
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        # the last timed step's result: the serialized bitmap in this GPU's memory (N > 1: the one gathered on GPU 0)
+        blob = bytes(last.cpu().numpy().tobytes()) if strong else eng.fetch().serialize()
+        _dump_outputs(args.dump_outputs, blob, eng.result_stats() if not strong else rs)
+
+    # the headline's cross-rank reduction first: what follows cannot lose it
+    if dist is not None:
+        tmax = torch.tensor([wall], dtype=torch.float64, device=cdev)
+        dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
+        wall_max = float(tmax[0])
+    else:
+        wall_max = wall
+    total_in = float(in_bytes)  # one pair, whatever the number of GPUs (strong scaling)
+    step_s = wall_max / max(args.steps, 1)
+
+    def headline(compute_s):
+        """The result line's own fields; compute_s: the compute kernel's time per step (seconds, device events)."""
+        achieved = (in_bytes + out_bytes) / compute_s / 1e9 if compute_s > 0 else 0.0
+        return {
+            "metric": METRIC,
+            "value": round(total_in / step_s / 1e9, 2),
+            "unit": "GB/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "ms_per_step": round(step_s * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "strong",
+            "vs_baseline": None,
+            "dtype": "u64",
+            "data": "synthetic",
+            "config": {"workload": "C2: RoaringBitmap.and(x1, x2), two full 2^32-universe bitmaps of 65536 "
+                                   "mixed array/bitmap/run containers each (configs[1])",
+                       "per_rank": "the pair's key range [65536 r / N, 65536 (r + 1) / N); slices placed in each "
+                                   "rank's HBM" if strong else "the whole pair",
+                       "parallelism": f"key-range sharding over {world} GPU(s)"},
+            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": _pmc_traffic(),
+                         "kernel": f"{PW_KERNEL}<AND> (container compute)",
+                         "bytes_per_launch": int((in_bytes + out_bytes) / (PIPE_K if PIPELINED and not strong else 1)),
+                         "launches_per_step": PIPE_K if PIPELINED and not strong else 1,
+                         "measured": "HIP events on the engine stream around the compute launches of the timed steps"},
+        }
+
+    if not args.full:  # a plain run ends here: the headline, with the roofline of the timed steps themselves
+        if rank == 0:
+            print(json.dumps(headline(ph_live[1] / 1e3)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
 
     strong_info = None
     if strong:  # the step without its gather (slices left in each rank's HBM), and the gathered bitmap's sha
@@ -932,16 +1027,6 @@ def main():
     n_ops, ph = eng.profile_read()
     eng.profile(0)
     ph_avg = [x / max(n_ops, 1) for x in ph]
-
-    # the headline's cross-rank reduction first: the extras below cannot lose it
-    t = torch.tensor([wall, float(in_bytes)], dtype=torch.float64, device=cdev)
-    if dist is not None:
-        tmax = t.clone()
-        dist.all_reduce(tmax[:1], op=dist.ReduceOp.MAX)
-        wall_max = float(tmax[0])
-    else:
-        wall_max = wall
-    total_in = float(in_bytes)  # one pair, whatever the number of GPUs (strong scaling)
 
     extra = {}
 
@@ -1034,36 +1119,12 @@ def main():
         cpu = cpu_baselines(eng, a, b, in_bytes, args.cpu_seconds)
 
     if rank == 0:
-        step_s = wall_max / args.steps
         # compute phase of the timed steps (pipelined: the span of the K range launches on the engine
         # stream, each launch 1/K of the bytes, so bytes / span = bytes per launch / mean launch time)
-        compute_s = (ph_live[1] if ph_live[1] > 0 else ph_avg[1]) / 1e3
-        achieved = (in_bytes + out_bytes) / compute_s / 1e9 if compute_s > 0 else 0.0
+        line = headline((ph_live[1] if ph_live[1] > 0 else ph_avg[1]) / 1e3)
+        line["roofline"]["standalone_kernel_ms"] = round(ph_avg[1], 4)
         line = {
-            "metric": METRIC,
-            "value": round(total_in / (wall_max / args.steps) / 1e9, 2),
-            "unit": "GB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(step_s * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "strong",
-            "vs_baseline": None,
-            "dtype": "u64",
-            "data": "synthetic",
-            "config": {"workload": "C2: RoaringBitmap.and(x1, x2), two full 2^32-universe bitmaps of 65536 "
-                                   "mixed array/bitmap/run containers each (configs[1])",
-                       "per_rank": "the pair's key range [65536 r / N, 65536 (r + 1) / N); slices placed in each "
-                                   "rank's HBM" if strong else "the whole pair",
-                       "parallelism": f"key-range sharding over {world} GPU(s)"},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": _pmc_traffic(),
-                         "kernel": f"{PW_KERNEL}<AND> (container compute)",
-                         "bytes_per_launch": int((in_bytes + out_bytes) / (PIPE_K if PIPELINED and not strong else 1)),
-                         "launches_per_step": PIPE_K if PIPELINED and not strong else 1,
-                         "measured": "HIP events on the engine stream around the compute launches of the timed steps",
-                         "standalone_kernel_ms": round(ph_avg[1], 4)},
+            **line,
             "cpu_baseline": cpu,
             "extra": {
                 "input_bytes_per_step": int(in_bytes), "output_bytes_per_step": int(out_bytes),

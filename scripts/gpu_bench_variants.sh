@@ -3,10 +3,12 @@
 set -o pipefail
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out
+OUT=${OUT:-bench_out}  # where the bench lines go
+mkdir -p "$OUT"
 for v in base $VARIANTS; do
   if [ $v = base ]; then unset RBG_LIB; else export RBG_LIB=$PWD/roaringbitmap_amd/lib/variants/$v.so; fi
-  timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline > gpurun_out/bench_$v.json 2> gpurun_out/bench_$v.err || { echo "$v failed"; tail -5 gpurun_out/bench_$v.err; exit 1; }
-  python3 - "$v" gpurun_out/bench_$v.json <<'PY'
+  timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_$v.json 2> $OUT/bench_$v.err || { echo "$v failed"; tail -5 $OUT/bench_$v.err; exit 1; }
+  python3 - "$v" $OUT/bench_$v.json <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1]); e = d["extra"]
 print(sys.argv[1], "AND ms", e["phase_ms"]["compute"], "card", e["c2_and_cardinality"]["roofline"]["kernel_ms"],

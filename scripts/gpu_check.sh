@@ -12,7 +12,9 @@ timeout -k 10 500 python -u -m pytest $SEL -k "$KSEL" -m gpu -x -q --timeout 200
   > gpurun_out/check_tests.log 2>&1
 rc=$?; echo "tests exit=$rc"; tail -15 gpurun_out/check_tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 300 python bench.py --steps 20 --warmup 3 --no-cpu-baseline --c3-n 0 --c4-pairs 0 --c5-rows 0 \
-  > gpurun_out/check_bench.json 2> gpurun_out/check_bench.err
-rc=$?; echo "bench exit=$rc"; cat gpurun_out/check_bench.json; tail -5 gpurun_out/check_bench.err
+OUT=${OUT:-bench_out}  # where the bench lines go
+mkdir -p "$OUT"
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --c3-n 0 --c4-pairs 0 --c5-rows 0 \
+  > $OUT/check_bench.json 2> $OUT/check_bench.err
+rc=$?; echo "bench exit=$rc"; cat $OUT/check_bench.json; tail -5 $OUT/check_bench.err
 exit $rc

@@ -10,5 +10,7 @@ rc=$?; echo "tests exit=$rc"; tail -15 gpurun_out/q_tests.log
 [ $rc -eq 0 ] || exit $rc
 timeout -k 10 200 python scripts/kind_matrix.py > gpurun_out/kind_matrix.txt 2>&1
 rc=$?; cat gpurun_out/kind_matrix.txt | grep -v in_MB; [ $rc -eq 0 ] || exit $rc
-timeout -k 10 200 python bench.py --steps 20 --warmup 3 --no-cpu-baseline > gpurun_out/q_bench.json 2> gpurun_out/q_bench.err
-rc=$?; cat gpurun_out/q_bench.json; tail -3 gpurun_out/q_bench.err; exit $rc
+OUT=${OUT:-bench_out}  # where the bench lines go
+mkdir -p "$OUT"
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/q_bench.json 2> $OUT/q_bench.err
+rc=$?; cat $OUT/q_bench.json; tail -3 $OUT/q_bench.err; exit $rc

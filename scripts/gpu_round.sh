@@ -8,6 +8,8 @@ SEL=${1:-tests}
 timeout -k 10 800 python -u -m pytest $SEL -m gpu -x -v --timeout 300 --timeout-method thread > gpurun_out/gpu_tests.log 2>&1
 rc=$?; echo "tests exit=$rc"; tail -5 gpurun_out/gpu_tests.log
 [ $rc -eq 0 ] || exit $rc
-timeout -k 10 400 python bench.py --steps 20 --warmup 3 > gpurun_out/bench.json 2> gpurun_out/bench.err
-rc=$?; echo "bench exit=$rc"; cat gpurun_out/bench.json; tail -5 gpurun_out/bench.err
+OUT=${OUT:-bench_out}  # where the bench lines go
+mkdir -p "$OUT"
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+rc=$?; echo "bench exit=$rc"; cat $OUT/bench.json; tail -5 $OUT/bench.err
 exit $rc

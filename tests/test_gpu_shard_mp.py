@@ -164,16 +164,48 @@ def test_two_rank_device_layout(gpu, op):
     assert res == ref
 
 
-def _bench(gpus):
+def _bench(gpus, *more):
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--backend", "gloo", "--steps", "2",
-           "--warmup", "1", "--c3-n", "64", "--c4-pairs", "2000", "--c5-rows", "2000000", "--no-cpu-baseline"]
+           "--warmup", "1", *more]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-3000:]
     return json.loads([ln for ln in p.stdout.splitlines() if ln.startswith("{")][-1])
 
 
+FULL = ["--full", "--c3-n", "64", "--c4-pairs", "2000", "--c5-rows", "2000000", "--no-cpu-baseline"]
+
+
+def _dumped(d):
+    import numpy as np
+    out = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    assert set(out) == {"serialized_head", "serialized_sample", "serialized_sha256", "serialized_size", "result_stats"}
+    assert all(x.dtype in (np.float32, np.float64) for x in out.values())
+    assert sum(x.nbytes for x in out.values()) <= 64 * 10 ** 6
+    return out, bytes(out["serialized_sha256"].astype(np.uint8)).hex()
+
+
+def test_bench_plain_run(gpu):
+    """A plain run prints the headline alone; --dump-outputs writes the last timed step's serialized result."""
+    with tempfile.TemporaryDirectory() as d:
+        line = _bench(1, "--dump-outputs", d)
+        out, _ = _dumped(d)
+    assert line["steps"] == 2 and line["ms_per_step"] > 0 and line["unit"] == "GB/s" and line["dtype"] == "u64"
+    assert line["value"] > 0 and line["higher_is_better"] is True and line["roofline"]["achieved"] > 0
+    assert "extra" not in line and "cpu_baseline" not in line
+    from roaringbitmap_amd import shard
+    n = int(out["serialized_size"][0])
+    containers, payload, has_run = (int(x) for x in out["result_stats"][:3])
+    assert n == shard.header_size(containers, has_run) + payload
+    assert out["serialized_head"].size == min(n, 1 << 20) and out["serialized_sample"].size == min(n, 8 << 20)
+
+
 def test_bench_two_ranks_rehearsal(gpu):
-    one, two = _bench(1), _bench(2)
+    with tempfile.TemporaryDirectory() as d1, tempfile.TemporaryDirectory() as d2:
+        one, two = _bench(1, *FULL, "--dump-outputs", d1), _bench(2, *FULL, "--dump-outputs", d2)
+        (out1, sha1), (out2, sha2) = _dumped(d1), _dumped(d2)
+    # the dumped bytes are the timed step's result, the same bitmap at one rank and gathered from two
+    assert sha1[:16] == sha2[:16] == one["extra"]["result"]["sha16"]
+    assert all((out1[k] == out2[k]).all() for k in out1)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
     # the N > 1 headline is the key-sharded C2 AND (strong scaling): its slices, gathered on GPU 0,
     # are the same bytes as the one-GPU headline's result (same pair)
