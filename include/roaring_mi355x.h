@@ -177,6 +177,22 @@ int rbg_remove_run_compression(const uint8_t* a, size_t a_len, rbg_buffer* out);
  * becomes an array at <= 4096 values, a run container keeps its runs up to the cut); maxcardinality <= 0:
  * the empty bitmap */
 int rbg_limit(const uint8_t* a, size_t a_len, int32_t maxcard, rbg_buffer* out);
+/* Point queries against one bitmap, n at a time (q: unsigned 32-bit values or positions; out: one int64
+ * per query, in query order):
+ *   RBG_PQ_RANK      rankLong(x) (RB/RoaringBitmap.java:2574-2592): the values <= x; rank(x) (:2621-2624) is
+ *                    its Java int cast, rangeCardinality(start, end) (:2595-2618) the difference of two
+ *   RBG_PQ_SELECT    select(j) (:2820-2835), j unsigned (Util.toUnsignedLong): the j-th smallest value as an
+ *                    unsigned 32-bit number; -1 where j >= cardinality (the reference throws
+ *                    IllegalArgumentException); first() / last() (:2972-2979) are select(0) / previousValue(0xFFFFFFFF)
+ *   RBG_PQ_CONTAINS  contains(x) (:1693-1701): 0 / 1
+ *   RBG_PQ_NEXT      nextValue(x) (:2838-2854): the smallest value >= x, -1 if none
+ *   RBG_PQ_PREV      previousValue(x) (:2857-2883): the largest value <= x, -1 if none
+ * (FastRankRoaringBitmap, RB/FastRankRoaringBitmap.java, answers rank / select the same from its cached
+ * cumulated cardinalities: the device rank directory is that cache plus per-container directories.)
+ * n == 0: RBG_OK, nothing touched.  A null pointer with n > 0 or an unknown op: RBG_ERR_ILLEGAL_ARGUMENT
+ * (checked before any device use).  One-shot: load, query, release. */
+enum { RBG_PQ_RANK = 0, RBG_PQ_SELECT = 1, RBG_PQ_CONTAINS = 2, RBG_PQ_NEXT = 3, RBG_PQ_PREV = 4 };
+int rbg_point_query(int op, const uint8_t* buf, size_t len, const uint32_t* q, size_t n, int64_t* out);
 /* RoaringBitmap.bitmapOfRange(min, max) (RB/RoaringBitmap.java:588-615): every container a run container
  * (RunContainer.rangeOfOnes, even for one or two values; static add over an empty bitmap would write
  * arrays there).  rangeSanityCheck -> RBG_ERR_ILLEGAL_ARGUMENT; max <= min: the empty bitmap. */
@@ -414,6 +430,16 @@ int rbg_ctx_bsi_sums_device(rbg_ctx* ctx, void* dst2);
 /* From now on every rbg_ctx_bsi with want_sum also writes its {sum, count} (two int64) to device
  * memory dst2, in the kernel that computes them (no copy launch); null stops it. */
 int rbg_ctx_bsi_sums_target(rbg_ctx* ctx, void* dst2);
+/* rbg_point_query against bitmap i of a device-resident batch (a single-bitmap key-major batch with
+ * slot-aligned payloads, as the pairwise ops take; any other: RBG_ERR_ILLEGAL_ARGUMENT).  The batch's rank
+ * directory is built on the device by its first query and kept until the batch is released.  q / out are
+ * host memory, staged through the context's pinned buffer; returns after the results are in out. */
+int rbg_ctx_point_query(rbg_ctx* ctx, int op, int32_t batch, size_t i, const uint32_t* q, size_t n, int64_t* out);
+/* The same with q_dev (n uint32) and out_dev (n int64) in device memory, enqueued on the context stream
+ * with no host synchronisation (the first query of a batch builds its directory, which reads one 8-byte
+ * size back). */
+int rbg_ctx_point_query_device(rbg_ctx* ctx, int op, int32_t batch, size_t i, const void* q_dev, size_t n,
+                               void* out_dev);
 /* Retired diagnostic (the per-phase clock builds of rounds 2-5 are gone; their results are in
  * profiles/): writes 20 zeros.  Kept so bindings of earlier rounds still link. */
 int rbg_debug_stamps(uint64_t* out20, int reset);

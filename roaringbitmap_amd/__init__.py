@@ -5,8 +5,8 @@ wide or/and/xor.  Bitmaps travel in the portable serialized
 format; every op runs in hand-written gfx950 HIP kernels behind the C ABI of
 include/roaring_mi355x.h.
 """
-from ._lib import (DeviceError, IllegalArgumentException, InvalidRoaringFormat, RoaringError,  # noqa: F401
-                   TruncatedInput)
+from ._lib import (DeviceError, IllegalArgumentException, InvalidRoaringFormat, NoSuchElementException,  # noqa: F401
+                   RoaringError, TruncatedInput)
 from .engine import Engine  # noqa: F401
 from .roaring import (BufferFastAggregation, FastAggregation, ImmutableRoaringBitmap, MutableRoaringBitmap,  # noqa: F401
                       ParallelAggregation, RoaringBitmap, batch_and_cardinality, run_optimize_many)
@@ -15,4 +15,4 @@ from .bsi import BitSliceIndexBase, ImmutableBitSliceIndex, MutableBitSliceIndex
 __all__ = ["RoaringBitmap", "ImmutableRoaringBitmap", "MutableRoaringBitmap", "FastAggregation", "BufferFastAggregation", "ParallelAggregation", "RoaringBitmapSliceIndex", "ImmutableBitSliceIndex",
            "MutableBitSliceIndex", "BitSliceIndexBase", "Engine", "batch_and_cardinality", "run_optimize_many",
            "InvalidRoaringFormat",
-           "TruncatedInput", "IllegalArgumentException", "DeviceError", "RoaringError"]
+           "TruncatedInput", "IllegalArgumentException", "NoSuchElementException", "DeviceError", "RoaringError"]

@@ -30,6 +30,7 @@ RANGE_OP = {"and": 0, "or": 1, "xor": 2, "andnot": 3,
 RBG_ORNOT_INPLACE, RBG_ORNOT_BUFFER = 1, 2
 RMUT_OP = {"add": 0, "remove": 1, "flip": 2, "add_inplace": 3}  # rbg_range_mut (| RBG_RMUT_BUFFER: MutableRoaringBitmap's)
 RBG_RMUT_BUFFER = 4
+PQ_OP = {"rank": 0, "select": 1, "contains": 2, "next": 3, "prev": 4}  # rbg_point_query (RBG_PQ_*)
 
 
 class rbg_buffer(ctypes.Structure):
@@ -50,6 +51,7 @@ EXPORTED = [
     "rbg_ctx_fetch_shard_device", "rbg_bsi_compare_buffer", "rbg_ctx_bsi_buffer",
     "rbg_ctx_result_layout_device", "rbg_ctx_fetch_shard_device_dyn", "rbg_pairwise_inplace",
     "rbg_ctx_load_separate", "rbg_ctx_load_packed", "rbg_ornot", "rbg_ctx_ornot", "rbg_range_mut", "rbg_ctx_range_mut", "rbg_add_offset", "rbg_ctx_add_offset", "rbg_select_range", "rbg_remove_run_compression", "rbg_limit", "rbg_bitmap_of_range",
+    "rbg_point_query", "rbg_ctx_point_query", "rbg_ctx_point_query_device",
 ]
 
 _lib = None
@@ -80,6 +82,9 @@ def _declare(L):
     L.rbg_remove_run_compression.argtypes = [u8p, sz, buf]
     L.rbg_limit.argtypes = [u8p, sz, ctypes.c_int32, buf]
     L.rbg_bitmap_of_range.argtypes = [ctypes.c_int64, ctypes.c_int64, buf]
+    L.rbg_point_query.argtypes = [ctypes.c_int, u8p, sz, P(ctypes.c_uint32), sz, P(ctypes.c_int64)]
+    L.rbg_ctx_point_query.argtypes = [vp, ctypes.c_int, i32, sz, P(ctypes.c_uint32), sz, P(ctypes.c_int64)]
+    L.rbg_ctx_point_query_device.argtypes = [vp, ctypes.c_int, i32, sz, vp, sz, vp]
     L.rbg_select_range.argtypes = [u8p, sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, buf]
     L.rbg_ctx_add_offset.argtypes = [vp, i32, sz, ctypes.c_int64]
     L.rbg_ctx_select_range.argtypes = [vp, i32, ctypes.c_int64, ctypes.c_int64, P(i32)]
@@ -179,6 +184,10 @@ class IllegalArgumentException(RoaringError, ValueError):
 class ArrayIndexOutOfBoundsException(RoaringError, IndexError):
     """java.lang.ArrayIndexOutOfBoundsException, where the reference's own control flow throws it on
     caller-supplied input (FastAggregation.workAndMemoryShyAnd with a dirty buffer, RB/FastAggregation.java:541-548)"""
+
+
+class NoSuchElementException(RoaringError, LookupError):
+    """java.util.NoSuchElementException: first() / last() of an empty bitmap (RB/RoaringArray.java:971-1027)"""
 
 
 class DeviceError(RoaringError, RuntimeError):

@@ -160,6 +160,10 @@ struct Batch {
   // table, planned by the first query and kept (ctx_bsi)
   bool bsi_cached = false;
   DevBuf bsi_tasks, bsi_nt, bsi_table;
+  // rank directory of a single-bitmap key-major batch (rankdir.hip): built on the device by the first
+  // point query and kept (ctx_rankdir)
+  bool rd_ready = false;
+  DevBuf rd_cum, rd_off, rd_aux;
   uint64_t pair_items_cap = 0;
   // host copy of the container table for fetches (batches are immutable once loaded):
   // h_desc in container order, h_pos[h_pos_off[i] .. h_pos_off[i+1]) = bitmap i's containers
@@ -199,6 +203,8 @@ struct Ctx {
   DevBuf owen_tb, owen_keys, owen_ord, big, big_ctl;
   DevBuf ones;  // 8192 bytes of 0xFF: the full bitmap container of an in-place OR (k_ior_fix)
   DevBuf ornot_plan;  // OrNotPlan of the last orNot
+  DevBuf rd_part;         // scan scratch of the rank directory build
+  DevBuf pt_q, pt_out;    // point queries from host memory: the queries and results on the device
   DevBuf gather_items, gather_out;  // batch fetch: slot gather list and download buffer
   DevBuf order;                     // horizontal_*: chain order of every key segment
   DevBuf ro_info, ro_size, ro_part;  // range selection scratch (kept: no allocation per call)
@@ -855,6 +861,73 @@ static int operand(Batch* b, size_t i, const uint16_t** keys, const CDesc** desc
   *keys = b->keys.as<uint16_t>();
   *desc = b->desc.as<CDesc>();
   *n = (int)b->n_ctr;
+  return RBG_OK;
+}
+
+// The rank directory of a batch operand() accepts (rankdir.hip): the container prefix cum, and per bitmap
+// / run container a u16 directory in an aux arena.  Sizes in one pass, two device scans, then the fill;
+// the host reads back the arena's size alone (8 bytes, once per batch) to allocate it exactly.
+// A build that fails part way leaves rd_ready false and whatever buffers it took on the batch: the next
+// query takes them again (pool_take keeps a buffer that is large enough), release pools them.
+static int ctx_rankdir(Ctx* c, Batch* b) {
+  if (b->rd_ready) return RBG_OK;
+  const size_t n = b->n_ctr;
+  hipStream_t s = c->stream;
+  CHK(pool_take(c, b->rd_cum, 8 * (n + 1)));
+  CHK(pool_take(c, b->rd_off, 8 * (n + 1)));
+  CHK(c->rd_part.ensure(8 * (scan_parts(std::max<uint64_t>(n, 1)) + 1)));
+  uint64_t* cum = b->rd_cum.as<uint64_t>();
+  uint64_t* off = b->rd_off.as<uint64_t>();
+  launch_rd_sizes(s, b->desc.as<CDesc>(), b->payload.as<uint8_t>(), n, cum, off);
+  launch_exclusive_scan(s, cum, cum, n, c->rd_part.as<uint64_t>(), cum + n);
+  launch_exclusive_scan(s, off, off, n, c->rd_part.as<uint64_t>(), off + n);
+  HIPCHK(hipGetLastError());
+  uint64_t aux_bytes = 0;
+  HIPCHK(hipMemcpyAsync(&aux_bytes, off + n, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  CHK(pool_take(c, b->rd_aux, aux_bytes + 16));
+  launch_rd_fill(s, b->desc.as<CDesc>(), b->payload.as<uint8_t>(), n, off, b->rd_aux.as<uint8_t>());
+  HIPCHK(hipGetLastError());
+  b->rd_ready = true;
+  return RBG_OK;
+}
+
+// n point queries (device memory, u32) against bitmap i of a batch into out (device memory, i64), in
+// query order, enqueued on the context stream
+static int ctx_point(Ctx* c, int op, int32_t batch, size_t i, const uint32_t* q_dev, size_t n, long long* out_dev) {
+  Batch* B;
+  CHK(get_batch(c, batch, &B));
+  const uint16_t* keys;
+  const CDesc* desc;
+  int nc;
+  CHK(operand(B, i, &keys, &desc, &nc));
+  CHK(ctx_rankdir(c, B));
+  const PointArgs pa{B->key_off.as<uint32_t>(), desc, B->payload.as<uint8_t>(), B->rd_cum.as<uint64_t>(),
+                     B->rd_off.as<uint64_t>(), B->rd_aux.as<uint8_t>(), (uint32_t)nc};
+  // RBG_PQ_NODIR=1 (measurement only, read at every call): rank with a bitmap's popcounts from word 0
+  if (op == PT_RANK) {
+    const char* e = std::getenv("RBG_PQ_NODIR");
+    if (e && e[0] == '1') op = PT_RANK_NODIR;
+  }
+  launch_point(c->stream, op, pa, q_dev, n, out_dev);
+  HIPCHK(hipGetLastError());
+  return RBG_OK;
+}
+
+// the same from host memory: staged through the context's pinned buffer, results in out on return
+static int ctx_point_host(Ctx* c, int op, int32_t batch, size_t i, const uint32_t* q, size_t n, int64_t* out) {
+  CHK(pinned_ensure(c, 12 * n + 64));
+  CHK(c->pt_q.ensure(4 * n));
+  CHK(c->pt_out.ensure(8 * n));
+  uint8_t* pin = reinterpret_cast<uint8_t*>(c->pinned);
+  hipStream_t s = c->stream;
+  HIPCHK(hipStreamSynchronize(s));  // nothing enqueued earlier still reads the staging buffer
+  std::memcpy(pin + 8 * n, q, 4 * n);
+  HIPCHK(hipMemcpyAsync(c->pt_q.p, pin + 8 * n, 4 * n, hipMemcpyHostToDevice, s));
+  CHK(ctx_point(c, op, batch, i, c->pt_q.as<uint32_t>(), n, c->pt_out.as<long long>()));
+  HIPCHK(hipMemcpyAsync(pin, c->pt_out.p, 8 * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::memcpy(out, pin, 8 * n);
   return RBG_OK;
 }
 
@@ -2407,6 +2480,40 @@ int rbg_add_offset(const uint8_t* a, size_t a_len, int64_t offset, rbg_buffer* o
   return ctx_fetch(c, out);
 }
 
+/* ---- point queries (rankdir.hip) ---- */
+static bool point_op_ok(int op) { return op >= RBG_PQ_RANK && op <= RBG_PQ_PREV; }
+
+int rbg_ctx_point_query(rbg_ctx* ctx, int op, int32_t batch, size_t i, const uint32_t* q, size_t n, int64_t* out) {
+  if (!ctx || !point_op_ok(op)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n == 0) return RBG_OK;
+  if (!q || !out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  CHK(enter(&ctx->c));
+  return ctx_point_host(&ctx->c, op, batch, i, q, n, out);
+}
+
+int rbg_ctx_point_query_device(rbg_ctx* ctx, int op, int32_t batch, size_t i, const void* q_dev, size_t n,
+                               void* out_dev) {
+  if (!ctx || !point_op_ok(op)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n == 0) return RBG_OK;
+  if (!q_dev || !out_dev) return RBG_ERR_ILLEGAL_ARGUMENT;
+  CHK(enter(&ctx->c));
+  return ctx_point(&ctx->c, op, batch, i, reinterpret_cast<const uint32_t*>(q_dev), n,
+                   reinterpret_cast<long long*>(out_dev));
+}
+
+int rbg_point_query(int op, const uint8_t* buf, size_t len, const uint32_t* q, size_t n, int64_t* out) {
+  if (!point_op_ok(op)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n == 0) return RBG_OK;
+  if (!buf || !q || !out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  Ctx* c;
+  CHK(tl_ctx(&c));
+  BatchGuard g{c, {}};
+  int32_t id;
+  CHK(ctx_load_separate(c, &buf, &len, 1, &id));
+  g.ids = {id};
+  return ctx_point_host(c, op, id, 0, q, n, out);
+}
+
 // x.limit(maxcardinality) (RB/RoaringBitmap.java:2457-2476).  The cut is planned from the serialized
 // header's cardinalities on the host (the reference's own loop walks getCardinality per container):
 // keys before it cloned, its container cut to the leftover by k_rmut<RMUT_LIMIT>, the rest dropped.
@@ -2884,7 +2991,7 @@ int rbg_ctx_release(rbg_ctx* ctx, int32_t batch) {
   // back into it at the op's end); a pooled buffer that is freed goes through hipFree, which waits
   // for the device.
   for (DevBuf* d : {&b->keys, &b->desc, &b->bm, &b->key_off, &b->bm_off, &b->payload, &b->ro_stats,
-                    &b->bsi_tasks, &b->bsi_nt, &b->bsi_table})
+                    &b->bsi_tasks, &b->bsi_nt, &b->bsi_table, &b->rd_cum, &b->rd_off, &b->rd_aux})
     pool_put(&c, *d);
   c.batches[batch].reset();
   return RBG_OK;

@@ -486,6 +486,28 @@ void launch_rsel_write(hipStream_t s, const CDesc* desc, const uint32_t* bm, con
                        const uint64_t* idx, CDesc* out_desc, uint16_t* out_keys, uint32_t* out_bm,
                        uint8_t* out_payload);
 
+// rankdir.hip: the rank directory of a single-bitmap key-major batch and the point queries over it
+// (rank / select / contains / nextValue / previousValue, RB/RoaringBitmap.java:1693, 2574-2624, 2820-2883)
+// == RBG_PQ_* (roaring_mi355x.h); PT_RANK_NODIR (internal, RBG_PQ_NODIR=1): rank with a bitmap's popcounts from
+// word 0, the baseline the directory is measured against
+enum PointOp : int { PT_RANK = 0, PT_SELECT = 1, PT_CONTAINS = 2, PT_NEXT = 3, PT_PREV = 4, PT_RANK_NODIR = 16 };
+struct PointArgs {
+  const uint32_t* key_off;  // the batch's key CSR (65,537 entries)
+  const CDesc* desc;
+  const uint8_t* payload;
+  const uint64_t* cum;      // n_ctr + 1: values before each container, then the cardinality
+  const uint64_t* aux_off;  // n_ctr + 1: byte offset of each container's directory in aux
+  const uint8_t* aux;       // B: 128 u16 (set bits before each block of 8 words), R: u16 per run (values before it)
+  uint32_t n_ctr;
+};
+// cum[i] = card, aux_off[i] = directory bytes of container i: both then scanned (launch_exclusive_scan)
+void launch_rd_sizes(hipStream_t s, const CDesc* desc, const uint8_t* payload, uint64_t n, uint64_t* cum,
+                     uint64_t* aux_off);
+void launch_rd_fill(hipStream_t s, const CDesc* desc, const uint8_t* payload, uint64_t n, const uint64_t* aux_off,
+                    uint8_t* aux);
+// out[i] = op(q[i]) for n queries, in query order (-1: no such value)
+void launch_point(hipStream_t s, int op, PointArgs a, const uint32_t* q, uint64_t n, long long* out);
+
 // decode.hip: portable-format decode on the device
 enum DecErr : uint32_t {
   DEC_OK = 0,

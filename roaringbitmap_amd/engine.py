@@ -237,6 +237,55 @@ class Engine:
         check(lib().rbg_ctx_bsi_sums_target(self._ctx, None if dst is None else ctypes.c_void_p(dst.data_ptr())))
         self._bsi_target = dst
 
+    def point_query(self, op, batch, queries, ia=0):
+        """n point queries against a resident bitmap (rbg_ctx_point_query): op "rank" (rankLong), "select",
+        "contains", "next" (nextValue), "prev" (previousValue); one int64 per query, in query order, -1 where
+        there is no such value.  A numpy array (or sequence) of values below 2^32 -> numpy int64 array,
+        synchronous.  A torch tensor on this engine's GPU, int64 holding values in [0, 2^32) (torch has no
+        arithmetic on uint32; a uint32 tensor is taken as it is; as on the numpy path only the low 32 bits
+        of a value are read, so -1 asks for 0xFFFFFFFF) -> torch int64 tensor, enqueued on the
+        engine stream through the device entry point with no host synchronisation (but for a batch's first
+        query, which builds its rank directory); torch's current stream waits for the result, so work
+        enqueued there afterwards may read it."""
+        code = _lib.PQ_OP[op] if isinstance(op, str) else int(op)
+        if type(queries).__module__.split(".")[0] == "torch":
+            import torch
+            if queries.device.type != "cuda" or queries.device.index != self.device:
+                raise ValueError(f"point_query: the query tensor must be on device {self.device}")
+            if queries.dtype == torch.int64:  # the low 32 bits of every element (little-endian words)
+                q = queries.contiguous().reshape(-1).view(torch.int32)[::2].contiguous()
+            elif queries.dtype == torch.uint32:
+                q = queries.contiguous()
+            else:
+                raise ValueError("point_query: an int64 or uint32 tensor is required")
+            q = q.reshape(-1)
+            out = torch.empty(q.numel(), dtype=torch.int64, device=queries.device)
+            if q.numel() == 0:
+                return out
+            # The conversion above ran on torch's current stream: the engine stream waits for it.  The current
+            # stream then waits for the query kernel, so torch's allocator, which orders the reuse of q's and
+            # out's memory on that stream alone, cannot hand either out while the kernel still uses it (the
+            # tensors keep no reference to the engine stream, which close() destroys), and out is ready
+            # for work enqueued on the current stream.
+            cur = torch.cuda.current_stream(queries.device)
+            es = torch.cuda.ExternalStream(self.stream_ptr, device=queries.device)
+            ev = torch.cuda.Event()
+            ev.record(cur)
+            es.wait_event(ev)
+            check(lib().rbg_ctx_point_query_device(self._ctx, code, int(batch), int(ia),
+                                                   ctypes.c_void_p(q.data_ptr()), q.numel(),
+                                                   ctypes.c_void_p(out.data_ptr())))
+            done = torch.cuda.Event()
+            done.record(es)
+            cur.wait_event(done)
+            return out
+        q = np.ascontiguousarray(np.asarray(queries, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        out = np.empty(q.size, dtype=np.int64)
+        check(lib().rbg_ctx_point_query(self._ctx, code, int(batch), int(ia),
+                                        q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), q.size,
+                                        out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
     def batch_counts(self, batch) -> np.ndarray:
         """containers per input bitmap of a batch"""
         n = self.batch_stats(batch)["bitmaps"]

@@ -19,7 +19,8 @@ from collections.abc import Iterator
 import numpy as np
 
 from . import _lib
-from ._lib import ArrayIndexOutOfBoundsException, IllegalArgumentException, check, lib, take
+from ._lib import (ArrayIndexOutOfBoundsException, IllegalArgumentException, NoSuchElementException, check, lib,
+                   take)
 
 EMPTY = bytes.fromhex("3a30000000000000")
 
@@ -299,6 +300,87 @@ class RoaringBitmap:
         starts = pay[0::2]
         i = int(np.searchsorted(starts, low, side="right")) - 1
         return i >= 0 and low <= int(starts[i]) + int(pay[2 * i + 1])
+
+    # ---- point queries (rbg_point_query: the GPU's rank directory) -----------
+    def _point(self, op, xs) -> np.ndarray:
+        q = np.ascontiguousarray(np.asarray(xs, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        out = np.empty(q.size, dtype=np.int64)
+        check(lib().rbg_point_query(_lib.PQ_OP[op], self._buf, len(self._buf),
+                                    q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), q.size,
+                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def rank_many(self, xs) -> np.ndarray:
+        """rankLong of every x (ints taken as unsigned 32-bit), one GPU call -> int64 array"""
+        return self._point("rank", xs)
+
+    def select_many(self, js) -> np.ndarray:
+        """select of every j (unsigned 32-bit), one GPU call -> int64 array of unsigned values, -1 where
+        j >= cardinality"""
+        return self._point("select", js)
+
+    def contains_many(self, xs) -> np.ndarray:
+        """contains(int) of every x, one GPU call -> int64 array of 0 / 1"""
+        return self._point("contains", xs)
+
+    def next_values(self, xs) -> np.ndarray:
+        """nextValue of every x, one GPU call -> int64 array, -1 where there is none"""
+        return self._point("next", xs)
+
+    def previous_values(self, xs) -> np.ndarray:
+        """previousValue of every x, one GPU call -> int64 array, -1 where there is none"""
+        return self._point("prev", xs)
+
+    def rankLong(self, x) -> int:
+        """RoaringBitmap.rankLong(int) (RB/RoaringBitmap.java:2574-2592): the values <= x (x unsigned)"""
+        return int(self._point("rank", [int(x) & 0xFFFFFFFF])[0])
+
+    def rank(self, x) -> int:
+        """rank(int) (:2621-2624): the Java int cast of rankLong"""
+        return _int32(self.rankLong(x))
+
+    def select(self, j) -> int:
+        """select(int j) (:2820-2835): the j-th smallest value (j unsigned) as a Java int;
+        IllegalArgumentException when j >= cardinality"""
+        v = int(self._point("select", [int(j) & 0xFFFFFFFF])[0])
+        if v < 0:
+            raise IllegalArgumentException(f"You are trying to select the {j}th value when the cardinality is "
+                                           f"{self.getCardinality()}.")
+        return _int32(v)
+
+    def nextValue(self, x) -> int:
+        """nextValue(int) (:2838-2854): the smallest value >= x as an unsigned long, -1 if none"""
+        return int(self._point("next", [int(x) & 0xFFFFFFFF])[0])
+
+    def previousValue(self, x) -> int:
+        """previousValue(int) (:2857-2883): the largest value <= x as an unsigned long, -1 if none"""
+        return int(self._point("prev", [int(x) & 0xFFFFFFFF])[0])
+
+    def first(self) -> int:
+        """first() (:2972-2974; RB/RoaringArray.java:971-1027): the smallest value as a Java int;
+        NoSuchElementException on an empty bitmap"""
+        v = int(self._point("select", [0])[0])
+        if v < 0:
+            raise NoSuchElementException("Empty RoaringBitmap")
+        return _int32(v)
+
+    def last(self) -> int:
+        """last() (:2977-2979): the largest value as a Java int; NoSuchElementException on an empty bitmap"""
+        v = int(self._point("prev", [0xFFFFFFFF])[0])
+        if v < 0:
+            raise NoSuchElementException("Empty RoaringBitmap")
+        return _int32(v)
+
+    def rangeCardinality(self, start, end) -> int:
+        """rangeCardinality(long start, long end) (:2595-2618): the values in [start, end), from rankLong of
+        both ends in one two-query call; bounds outside [0, 2^32] raise ValueError, as selectRange does"""
+        start, end = int(start), int(end)
+        if start < 0 or end < 0 or start > 1 << 32 or end > 1 << 32:
+            raise IllegalArgumentException(f"rangeCardinality: bounds [{start}, {end}) outside [0, 2^32]")
+        if start >= end:
+            return 0
+        r = self._point("rank", [end - 1, max(start - 1, 0)])
+        return int(r[0]) - (int(r[1]) if start > 0 else 0)
 
     def selectRange(self, range_start, range_end):
         """x.selectRange(rangeStart, rangeEnd) (RB/RoaringBitmap.java:3095-3147) on the GPU: the values in
