@@ -121,16 +121,33 @@ struct OutCtx {
 };
 constexpr int kAggTile = 64;                     // records per aggregate tile
 constexpr int kMaxAggTiles = 65536 / kAggTile;  // a result has at most 65,536 records
-// a kept result as a tile-aggregate increment: payload bytes [0, 20), containers [20, 27), run
-// containers [27, 34), cardinality [34, 57) -- no field of a 64-record tile can overflow
+// a kept result as a tile-aggregate increment: payload bytes, containers, run containers and
+// cardinality in fields of the widths below, lowest first.  The largest kept record is not an 8 KiB
+// result slot but a run container cloned unchanged (key held by one operand of OR / XOR / ANDNOT):
+// up to 32,768 runs, 2 + 4 x 32,768 B.  Every field holds a whole tile of the largest records.
+constexpr uint32_t kMaxSerLen = 2u + 4u * 32768u;  // serialized bytes of the largest container
+constexpr int kAggBytesBits = 24, kAggCountBits = 7, kAggRunsBits = 7, kAggCardBits = 23;
+constexpr int kAggCountShift = kAggBytesBits, kAggRunsShift = kAggCountShift + kAggCountBits,
+              kAggCardShift = kAggRunsShift + kAggRunsBits;
+static_assert((unsigned long long)kAggTile * kMaxSerLen < (1ull << kAggBytesBits), "tile payload bytes overflow their field");
+static_assert(kAggTile < (1 << kAggCountBits), "tile container count overflows its field");
+static_assert(kAggTile < (1 << kAggRunsBits), "tile run-container count overflows its field");
+static_assert((unsigned long long)kAggTile * 65536ull < (1ull << kAggCardBits), "tile cardinality overflows its field");
+static_assert(kAggCardShift + kAggCardBits <= 64, "tile aggregate does not fit 64 bits");
 __host__ __device__ __forceinline__ unsigned long long agg_pack(uint32_t len, uint32_t card, uint32_t kind) {
-  return (unsigned long long)len | (1ull << 20) | ((unsigned long long)(kind == DK_R ? 1u : 0u) << 27) |
-         ((unsigned long long)card << 34);
+  return (unsigned long long)len | (1ull << kAggCountShift) |
+         ((unsigned long long)(kind == DK_R ? 1u : 0u) << kAggRunsShift) | ((unsigned long long)card << kAggCardShift);
 }
-__host__ __device__ __forceinline__ uint32_t agg_bytes(unsigned long long a) { return (uint32_t)(a & 0xFFFFF); }
-__host__ __device__ __forceinline__ uint32_t agg_count(unsigned long long a) { return (uint32_t)((a >> 20) & 0x7F); }
-__host__ __device__ __forceinline__ uint32_t agg_runs(unsigned long long a) { return (uint32_t)((a >> 27) & 0x7F); }
-__host__ __device__ __forceinline__ uint32_t agg_card(unsigned long long a) { return (uint32_t)(a >> 34); }
+__host__ __device__ __forceinline__ uint32_t agg_bytes(unsigned long long a) {
+  return (uint32_t)(a & ((1ull << kAggBytesBits) - 1));
+}
+__host__ __device__ __forceinline__ uint32_t agg_count(unsigned long long a) {
+  return (uint32_t)((a >> kAggCountShift) & ((1u << kAggCountBits) - 1));
+}
+__host__ __device__ __forceinline__ uint32_t agg_runs(unsigned long long a) {
+  return (uint32_t)((a >> kAggRunsShift) & ((1u << kAggRunsBits) - 1));
+}
+__host__ __device__ __forceinline__ uint32_t agg_card(unsigned long long a) { return (uint32_t)(a >> kAggCardShift); }
 
 // Run containers of more than 2047 runs (8 KiB of runs) do not fit a result slot.  Only the buffer
 // package's run AND / ANDNOT run make them (no toEfficientContainer); such a result is written to

@@ -477,7 +477,10 @@ __global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(8))
   if (T != 0 && T >= ntiles) return;
   const int lane = threadIdx.x & 63, w = (int)uni(threadIdx.x >> 6);  // (w in an SGPR: scalar copy loop)
   // prefix (tiles < T) and totals of the tile sums
-  // (payload bytes of a result fit 32 bits: <= 65,536 x 8 KiB; its cardinality does not)
+  // (a tile's payload bytes are < 2^kAggBytesBits: kAggTile records of at most kMaxSerLen B each, the
+  // largest a run container cloned unchanged.  The result's byte prefix and total are summed in 32 bits:
+  // enough for 65,536 records of 8 KiB and for any result the portable format's 32-bit offset table can
+  // describe, not for 4 GiB of cloned run containers.  Its cardinality needs 64 bits.)
   uint32_t pc = 0, pb = 0, tc = 0, tb = 0, tr = 0;
   unsigned long long tcard = 0;
   for (uint32_t i = threadIdx.x; i < ntiles; i += blockDim.x) {
@@ -550,7 +553,7 @@ __global__ __launch_bounds__(kAggThreads) __attribute__((amdgpu_waves_per_eu(8))
   const uint32_t len = keep ? r.ser_len : 0u;
   int tk, tb_;
   const int ek = wave_excl(keep, &tk);
-  const int eb = wave_excl((int)len, &tb_);  // <= 64 x 8 KiB
+  const int eb = wave_excl((int)len, &tb_);  // <= kAggTile x kMaxSerLen = 8,388,736: fits an int
   const uint64_t off = (uint64_t)pb + (uint64_t)eb;
   // the copy list through the wave's own LDS rows (held in registers across w_copy they spilled)
   s_off[w][lane] = off;

@@ -177,3 +177,72 @@ def test_packed_decode_for_wide_ops(gpu):
     assert e.fetch().serialize() == O.wide("naive_and", [mixed, bufs[1]])
     for b in (packed, padded, one, m):
         e.release(b)
+
+
+# every wide op that reads the packed layout (wide_reads_packed, csrc/engine.cpp; `and` above 10 inputs)
+PACKED_WIDE_OPS = ["or", "xor", "and", "workshy_and", "parallel_or", "parallel_xor", "buffer_or_mutable",
+                   "horizontal_or", "horizontal_xor", "priorityqueue_or", "priorityqueue_xor"]
+
+
+def _odd_array_bitmaps(n):
+    """n bitmaps of arrays alone over 48 keys, each key held with probability 1/2 (so container counts differ:
+    a horizontal_* order that is not the identity), 6 keys held by one bitmap alone (clones), 4 keys held by
+    every bitmap with 37 values in common (so the ANDs keep something), and cardinalities
+    mostly odd across the array sizes (tiny, small, mid, at the 4,096 edge), so that a packed batch's slots
+    start at every 2-byte phase of the 16 B a padded slot is aligned to."""
+    from _fmt import A, encode
+    rng = np.random.default_rng(4800 + n)
+    ranges = [(1, 32), (1, 200), (200, 4097), (4080, 4097)]  # _gen's a_tiny, a_small, a_mid, a_edge
+    keys = np.sort(rng.choice(300, size=48, replace=False))
+    special = rng.choice(keys, size=10, replace=False)
+    alone, everyone = set(int(k) for k in special[:6]), set(int(k) for k in special[6:])
+    core = np.sort(rng.choice(65536, size=37, replace=False))  # on 4 keys every bitmap holds these: AND keeps them
+    ctrs = [[] for _ in range(n)]
+    for k in keys:
+        k = int(k)
+        if k in alone:
+            holders = [int(rng.integers(n))]
+        else:
+            holders = [i for i in range(n) if k in everyone or rng.random() < 0.5]
+        for i in holders:
+            lo, hi = ranges[int(rng.integers(len(ranges)))]
+            card = int(rng.integers(lo, hi))
+            if card % 2 == 0 and card > 1 and rng.random() < 0.85:
+                card -= 1
+            vals = rng.choice(65536, size=card, replace=False)
+            if k in everyone:
+                vals = np.union1d(vals[:max(card - core.size, 0)], core)
+            ctrs[i].append((k, A, np.sort(vals).astype(np.uint16)))
+    return [encode(c) for c in ctrs]
+
+
+@pytest.fixture(scope="module", params=[12, 17])
+def packed_and_padded(request, gpu):
+    from roaringbitmap_amd import Engine
+    e = Engine(0)
+    bufs = _odd_array_bitmaps(request.param)
+    packed, padded = e.load(bufs, packed=True), e.load(bufs)
+    yield e, bufs, packed, padded
+    e.release(packed)
+    e.release(padded)
+    e.close()
+
+
+@pytest.mark.parametrize("op", PACKED_WIDE_OPS)
+def test_packed_decode_every_wide_op_unaligned_arrays(packed_and_padded, op):
+    """Every wide op admitted on a packed batch reads arrays at 2-byte alignment: byte-exact against the oracle
+    from the packed and from the slot-aligned decode of the same bitmaps (RB/FastAggregation.java:124-289,
+    356-414, 586-666, 677-836; RB/ParallelAggregation.java:153-214), with odd cardinalities, differing
+    container counts and keys that one bitmap holds alone (a clone from an unaligned source)."""
+    from roaringbitmap_amd._lib import IllegalArgumentException
+    e, bufs, packed, padded = packed_and_padded
+    counts = [O.stats(x)["array"] for x in bufs]
+    assert len(set(counts)) > 1 and all(O.stats(x)["bitmap"] + O.stats(x)["run"] == 0 for x in bufs)
+    assert sum(O.stats(x)["card"] % 2 for x in bufs) > 0  # some payload ends off the 4-byte phase
+    with pytest.raises(IllegalArgumentException):  # the first batch really is packed: naive_and needs slots
+        e.wide("naive_and", packed)
+    exp = O.wide(op, bufs)
+    assert O.stats(exp)["card"] >= 4 * 37, op  # no op's result is empty
+    for name, b in (("packed", packed), ("padded", padded)):
+        e.wide(op, b)
+        assert e.fetch().serialize() == exp, (op, len(bufs), name)
