@@ -193,6 +193,15 @@ int rbg_limit(const uint8_t* a, size_t a_len, int32_t maxcard, rbg_buffer* out);
  * (checked before any device use).  One-shot: load, query, release. */
 enum { RBG_PQ_RANK = 0, RBG_PQ_SELECT = 1, RBG_PQ_CONTAINS = 2, RBG_PQ_NEXT = 3, RBG_PQ_PREV = 4 };
 int rbg_point_query(int op, const uint8_t* buf, size_t len, const uint32_t* q, size_t n, int64_t* out);
+/* RoaringBitmap.bitmapOf(int...) / add(int...) (RB/RoaringBitmap.java:483-570), with run_optimize followed
+ * by runOptimize() (:2764-2774), built on the GPU: the counterpart of rbg_from_values, same bytes (values
+ * need not be sorted or distinct).  One-shot: upload the values, build the batch, fetch it, release.
+ * Without a usable device: RBG_ERR_DEVICE.  A null pointer with n > 0: RBG_ERR_ILLEGAL_ARGUMENT. */
+int rbg_build_values(const uint32_t* values, size_t n, int run_optimize, rbg_buffer* out);
+/* RoaringBitmap.toArray() (RB/RoaringBitmap.java:3224), expanded on the GPU: the counterpart of
+ * rbg_to_values, same bytes (ascending unsigned values, out->len = 4 * cardinality).  One-shot: load,
+ * expand, release.  Without a usable device: RBG_ERR_DEVICE. */
+int rbg_expand_values(const uint8_t* buf, size_t len, rbg_buffer* out);
 /* RoaringBitmap.bitmapOfRange(min, max) (RB/RoaringBitmap.java:588-615): every container a run container
  * (RunContainer.rangeOfOnes, even for one or two values; static add over an empty bitmap would write
  * arrays there).  rangeSanityCheck -> RBG_ERR_ILLEGAL_ARGUMENT; max <= min: the empty bitmap. */
@@ -440,6 +449,32 @@ int rbg_ctx_point_query(rbg_ctx* ctx, int op, int32_t batch, size_t i, const uin
  * size back). */
 int rbg_ctx_point_query_device(rbg_ctx* ctx, int op, int32_t batch, size_t i, const void* q_dev, size_t n,
                                void* out_dev);
+/* RoaringBitmap.add(int...) / addN / bitmapOf (RB/RoaringBitmap.java:483-570) over an empty bitmap, with
+ * run_optimize followed by runOptimize() (:2764-2774), on the device: *batch = a new single-bitmap key-major
+ * batch with slot-aligned payloads, exactly what rbg_ctx_load of rbg_from_values(values, n, run_optimize)
+ * gives (so every op that takes a loaded bitmap takes it).  The n values need not be sorted or distinct;
+ * n == 0 gives a live empty batch.  values is host memory, staged through the context's pinned buffer.
+ * Synchronous (the container count and the batch totals are read back).  A null pointer with n > 0:
+ * RBG_ERR_ILLEGAL_ARGUMENT. */
+int rbg_ctx_from_values(rbg_ctx* ctx, const uint32_t* values, size_t n, int run_optimize, int32_t* batch);
+/* The same with values_dev (n uint32) in device memory, read by kernels enqueued on the context stream:
+ * work that produces it on another stream must be ordered before the call, and the buffer must not
+ * change until the call returns (it is read twice). */
+int rbg_ctx_from_values_device(rbg_ctx* ctx, const void* values_dev, size_t n, int run_optimize, int32_t* batch);
+/* RoaringBitmap.toArray() (RB/RoaringBitmap.java:3224) and its windowed form (BatchIterator.nextBatch,
+ * limit): the values of ranks [first, first + count), clipped to the cardinality, of bitmap i of a
+ * device-resident batch (as rbg_ctx_point_query takes; any other: RBG_ERR_ILLEGAL_ARGUMENT), ascending and
+ * unsigned, into out (host memory, room for min(count, cardinality - first) values); *n_out (nullable) =
+ * the values written.  Uses the batch's rank directory (built by the first query or expansion and kept).
+ * Returns after the values are in out.  out null with n_out given: only *n_out is computed (the size
+ * of the window, no device work); out and n_out both null with values to write: RBG_ERR_ILLEGAL_ARGUMENT. */
+int rbg_ctx_to_values(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t count, uint32_t* out,
+                      uint64_t* n_out);
+/* The same into device memory out_dev: uint32, or int64 zero-extended when out64 is nonzero; enqueued on
+ * the context stream with no host synchronisation (but for the directory's first build).  *n_out is known
+ * on return (from the batch's cardinality). */
+int rbg_ctx_to_values_device(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t count, int out64,
+                             void* out_dev, uint64_t* n_out);
 /* Retired diagnostic (the per-phase clock builds of rounds 2-5 are gone; their results are in
  * profiles/): writes 20 zeros.  Kept so bindings of earlier rounds still link. */
 int rbg_debug_stamps(uint64_t* out20, int reset);

@@ -52,6 +52,8 @@ EXPORTED = [
     "rbg_ctx_result_layout_device", "rbg_ctx_fetch_shard_device_dyn", "rbg_pairwise_inplace",
     "rbg_ctx_load_separate", "rbg_ctx_load_packed", "rbg_ornot", "rbg_ctx_ornot", "rbg_range_mut", "rbg_ctx_range_mut", "rbg_add_offset", "rbg_ctx_add_offset", "rbg_select_range", "rbg_remove_run_compression", "rbg_limit", "rbg_bitmap_of_range",
     "rbg_point_query", "rbg_ctx_point_query", "rbg_ctx_point_query_device",
+    "rbg_build_values", "rbg_expand_values", "rbg_ctx_from_values", "rbg_ctx_from_values_device",
+    "rbg_ctx_to_values", "rbg_ctx_to_values_device",
 ]
 
 _lib = None
@@ -85,6 +87,13 @@ def _declare(L):
     L.rbg_point_query.argtypes = [ctypes.c_int, u8p, sz, P(ctypes.c_uint32), sz, P(ctypes.c_int64)]
     L.rbg_ctx_point_query.argtypes = [vp, ctypes.c_int, i32, sz, P(ctypes.c_uint32), sz, P(ctypes.c_int64)]
     L.rbg_ctx_point_query_device.argtypes = [vp, ctypes.c_int, i32, sz, vp, sz, vp]
+    u64 = ctypes.c_uint64
+    L.rbg_build_values.argtypes = [P(ctypes.c_uint32), sz, ctypes.c_int, buf]
+    L.rbg_expand_values.argtypes = [u8p, sz, buf]
+    L.rbg_ctx_from_values.argtypes = [vp, P(ctypes.c_uint32), sz, ctypes.c_int, P(i32)]
+    L.rbg_ctx_from_values_device.argtypes = [vp, vp, sz, ctypes.c_int, P(i32)]
+    L.rbg_ctx_to_values.argtypes = [vp, i32, sz, u64, u64, P(ctypes.c_uint32), P(u64)]
+    L.rbg_ctx_to_values_device.argtypes = [vp, i32, sz, u64, u64, ctypes.c_int, vp, P(u64)]
     L.rbg_select_range.argtypes = [u8p, sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, buf]
     L.rbg_ctx_add_offset.argtypes = [vp, i32, sz, ctypes.c_int64]
     L.rbg_ctx_select_range.argtypes = [vp, i32, ctypes.c_int64, ctypes.c_int64, P(i32)]
@@ -204,7 +213,10 @@ def check(status):
 
 
 def take(b: rbg_buffer) -> bytes:
-    out = ctypes.string_at(b.data, b.len) if b.len else b""
+    if b.len >= 1 << 31:  # string_at takes its size as a C int
+        out = bytes((ctypes.c_ubyte * b.len).from_address(ctypes.addressof(b.data.contents)))
+    else:
+        out = ctypes.string_at(b.data, b.len) if b.len else b""
     lib().rbg_free(ctypes.byref(b))
     return out
 

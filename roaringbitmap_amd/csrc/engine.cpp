@@ -205,6 +205,8 @@ struct Ctx {
   DevBuf ornot_plan;  // OrNotPlan of the last orNot
   DevBuf rd_part;         // scan scratch of the rank directory build
   DevBuf pt_q, pt_out;    // point queries from host memory: the queries and results on the device
+  DevBuf bld_info, bld_size, bld_part;  // construction from values (build.hip): the plan's table, slot sizes, scan
+  DevBuf tv_out;                        // expansion to host memory: one window of values on the device
   DevBuf gather_items, gather_out;  // batch fetch: slot gather list and download buffer
   DevBuf order;                     // horizontal_*: chain order of every key segment
   DevBuf ro_info, ro_size, ro_part;  // range selection scratch (kept: no allocation per call)
@@ -929,6 +931,163 @@ static int ctx_point_host(Ctx* c, int op, int32_t batch, size_t i, const uint32_
   HIPCHK(hipStreamSynchronize(s));
   std::memcpy(out, pin, 8 * n);
   return RBG_OK;
+}
+
+// The values of ranks [first, first + count) of bitmap i of a batch, clipped to the cardinality
+// (RoaringBitmap.toArray, RB/RoaringBitmap.java:3224; BatchIterator.nextBatch), into out_dev (u32, or
+// i64 with out64), enqueued on the context stream (expand.hip).  *n_out: the values written, known here
+// from the batch's cardinality.
+static int ctx_to_values(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t count, bool out64, void* out_dev,
+                         uint64_t* n_out) {
+  Batch* B;
+  CHK(get_batch(c, batch, &B));
+  const uint16_t* keys;
+  const CDesc* desc;
+  int nc;
+  CHK(operand(B, i, &keys, &desc, &nc));
+  const uint64_t card = (uint64_t)B->long_card;
+  const uint64_t cnt = first < card ? std::min<uint64_t>(count, card - first) : 0;
+  if (n_out) *n_out = cnt;
+  if (!cnt || (!out_dev && n_out)) return RBG_OK;  // no buffer: the caller asks for the window's size
+  if (!out_dev) {
+    set_err("to_values: no output buffer");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  CHK(ctx_rankdir(c, B));
+  const PointArgs pa{B->key_off.as<uint32_t>(), desc, B->payload.as<uint8_t>(), B->rd_cum.as<uint64_t>(),
+                     B->rd_off.as<uint64_t>(), B->rd_aux.as<uint8_t>(), (uint32_t)nc};
+  launch_to_values(c->stream, pa, first, cnt, out64, out_dev);
+  HIPCHK(hipGetLastError());
+  return RBG_OK;
+}
+
+// the same into host memory (u32), one window of at most kToValuesWindow values on the device at a time
+constexpr uint64_t kToValuesWindow = 64ull << 20;
+static int ctx_to_values_host(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t count, uint32_t* out,
+                              uint64_t* n_out) {
+  uint64_t total = 0;
+  CHK(ctx_to_values(c, batch, i, first, count, false, nullptr, &total));  // the operand check and the size
+  if (n_out) *n_out = total;
+  if (!total || (!out && n_out)) return RBG_OK;
+  if (!out) {
+    set_err("to_values: no output buffer");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  CHK(c->tv_out.ensure(4 * std::min<uint64_t>(total, kToValuesWindow)));
+  for (uint64_t done = 0; done < total; done += kToValuesWindow) {
+    const uint64_t w = std::min<uint64_t>(kToValuesWindow, total - done);
+    uint64_t got = 0;
+    CHK(ctx_to_values(c, batch, i, first + done, w, false, c->tv_out.p, &got));
+    HIPCHK(hipMemcpyAsync(out + done, c->tv_out.p, 4 * w, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return RBG_OK;
+}
+
+// A bitmap from n values in device memory (u32, any order, duplicates allowed) as a new one-bitmap
+// key-major batch: RoaringBitmap.add(int...) / addN / bitmapOf (RB/RoaringBitmap.java:483-570), with
+// run_opt followed by runOptimize() (:2764-2774) -- the batch ctx_load of build_from_values' bytes gives
+// (build.hip).  Two read-backs: the container count (to size the workspace of 8 KiB bitmaps) and the
+// totals (payload size, kinds, cardinality).  The values are read by two kernels: they must not change
+// until the call returns.
+// the scatter reads a word before its atomic (18x on 2^27 values of one key, -16 % on sorted dense input:
+// DESIGN §3.9)
+constexpr bool kBldPrecheck = true;
+static int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32_t* out_id) {
+  hipStream_t s = c->stream;
+  const int32_t id = new_batch(c);
+  Batch& b = *c->batches[id];
+  struct Drop {  // an error below frees the half-built batch
+    Ctx* c;
+    int32_t id;
+    bool keep = false;
+    ~Drop() {
+      if (!keep) c->batches[id].reset();
+    }
+  } drop{c, id};
+  DevBuf ws;  // C zeroed bitmaps; back to the pool at the end (freed on an error)
+  CHK(pool_take(c, b.keys, 2 * std::min<size_t>(n, kMaxKeys) + 16));
+  CHK(pool_take(c, b.key_off, 4 * (kMaxKeys + 1)));
+  CHK(pool_take(c, b.bm_off, 4 * 2));
+  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] C, [1..3] kinds, [4] serialized payload
+                                                                // bytes, [5] cardinality, [6] slot bytes
+  HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
+  HIPCHK(hipMemsetAsync(sc, 0, 64, s));
+  launch_bld_keys(s, v_dev, n, c->flag.as<uint8_t>(), b.keys.as<uint16_t>(), b.key_off.as<uint32_t>(), sc);
+  HIPCHK(hipGetLastError());
+  unsigned long long h[8] = {};
+  HIPCHK(hipMemcpyAsync(h, sc, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const size_t C = (size_t)h[0];
+  dbg(s, "from_values: keys");
+  if (C) {
+    CHK(pool_take(c, ws, 8192 * C));
+    HIPCHK(hipMemsetAsync(ws.p, 0, 8192 * C, s));
+    // RBG_BLD_PRECHECK=0 / 1 (measurement only, read at every call): the scatter without / with the read
+    // in front of every atomic
+    bool precheck = kBldPrecheck;
+    if (const char* e = std::getenv("RBG_BLD_PRECHECK")) precheck = e[0] == '1';
+    launch_bld_scatter(s, v_dev, n, b.key_off.as<uint32_t>(), ws.as<uint32_t>(), precheck);
+    CHK(c->bld_info.ensure(kBldInfoBytes * C));
+    CHK(c->bld_size.ensure(8 * C + 16));
+    CHK(c->bld_part.ensure(8 * (scan_parts(C) + 1)));
+    launch_bld_plan(s, ws.as<uint8_t>(), C, run_opt ? 1 : 0, c->bld_info.p, c->bld_size.as<uint64_t>(), sc + 1);
+    launch_exclusive_scan(s, c->bld_size.as<uint64_t>(), c->bld_size.as<uint64_t>(), C, c->bld_part.as<uint64_t>(),
+                          reinterpret_cast<uint64_t*>(sc + 6));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, sc, 64, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    dbg(s, "from_values: scatter + plan");
+  }
+  b.payload_bytes = (size_t)h[6];
+  CHK(pool_take(c, b.desc, sizeof(CDesc) * C + 16));
+  CHK(pool_take(c, b.bm, 4 * C + 16));
+  CHK(pool_take(c, b.payload, b.payload_bytes + 64));
+  if (C)
+    launch_bld_write(s, ws.as<uint8_t>(), C, c->bld_info.p, c->bld_size.as<uint64_t>(), b.keys.as<uint16_t>(),
+                     b.desc.as<CDesc>(), b.bm.as<uint32_t>(), b.bm_off.as<uint32_t>(), b.payload.as<uint8_t>());
+  else
+    HIPCHK(hipMemsetAsync(b.bm_off.p, 0, 8, s));
+  HIPCHK(hipGetLastError());
+  dbg(s, "from_values: write");
+  pool_put(c, ws);  // whatever takes it next is enqueued on this stream, after the write kernel
+  b.n_bm = 1;
+  b.n_ctr = C;
+  b.key_major = true;
+  for (int k = 0; k < 3; k++) b.n_kind[k] = (int64_t)h[1 + k];
+  const bool has_run = h[3] != 0;
+  b.ser_bytes = (int64_t)(header_size(C, has_run) + h[4]);
+  b.long_card = (int64_t)h[5];
+  b.max_ser = 0;  // no container above 8194 serialized bytes
+  b.h_bm_off = {0, (uint32_t)C};
+  b.h_bm_nctr = {(uint32_t)C};
+  b.h_bm_card = {b.long_card};
+  b.h_has_run = {(uint8_t)has_run};
+  b.live = true;
+  drop.keep = true;
+  *out_id = id;
+  return RBG_OK;
+}
+
+// the same from host memory: the values go to the device through the context's pinned buffer, a chunk
+// at a time
+static int ctx_from_values_host(Ctx* c, const uint32_t* v, size_t n, bool run_opt, int32_t* out_id) {
+  constexpr size_t kChunk = 16u << 20;  // values per staged copy (64 MiB)
+  DevBuf in;
+  CHK(pool_take(c, in, 4 * n + 16));
+  if (n) {
+    CHK(pinned_ensure(c, 4 * std::min(n, kChunk)));
+    HIPCHK(hipStreamSynchronize(c->stream));  // nothing enqueued earlier still reads the staging buffer
+    for (size_t off = 0; off < n; off += kChunk) {
+      const size_t m = std::min(kChunk, n - off);
+      std::memcpy(c->pinned, v + off, 4 * m);
+      HIPCHK(hipMemcpyAsync(in.as<uint32_t>() + off, c->pinned, 4 * m, hipMemcpyHostToDevice, c->stream));
+      HIPCHK(hipStreamSynchronize(c->stream));
+    }
+  }
+  const int st = ctx_from_values(c, in.as<uint32_t>(), n, run_opt, out_id);
+  pool_put(c, in);
+  return st;
 }
 
 // op RBG_OR_INPLACE: x1.or(x2) in place (RB/RoaringBitmap.java:2481-2523), the OR with Container.ior's
@@ -2512,6 +2671,65 @@ int rbg_point_query(int op, const uint8_t* buf, size_t len, const uint32_t* q, s
   CHK(ctx_load_separate(c, &buf, &len, 1, &id));
   g.ids = {id};
   return ctx_point_host(c, op, id, 0, q, n, out);
+}
+
+int rbg_ctx_from_values(rbg_ctx* ctx, const uint32_t* values, size_t n, int run_optimize, int32_t* batch) {
+  if (!ctx || !batch || (n && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  CHK(enter(&ctx->c));
+  return ctx_from_values_host(&ctx->c, values, n, run_optimize != 0, batch);
+}
+
+int rbg_ctx_from_values_device(rbg_ctx* ctx, const void* values_dev, size_t n, int run_optimize, int32_t* batch) {
+  if (!ctx || !batch || (n && !values_dev)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  CHK(enter(&ctx->c));
+  return ctx_from_values(&ctx->c, reinterpret_cast<const uint32_t*>(values_dev), n, run_optimize != 0, batch);
+}
+
+int rbg_ctx_to_values(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t count, uint32_t* out,
+                      uint64_t* n_out) {
+  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
+  CHK(enter(&ctx->c));
+  return ctx_to_values_host(&ctx->c, batch, i, first, count, out, n_out);
+}
+
+int rbg_ctx_to_values_device(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t count, int out64,
+                             void* out_dev, uint64_t* n_out) {
+  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
+  CHK(enter(&ctx->c));
+  return ctx_to_values(&ctx->c, batch, i, first, count, out64 != 0, out_dev, n_out);
+}
+
+int rbg_build_values(const uint32_t* values, size_t n, int run_optimize, rbg_buffer* out) {
+  if (!out || (n && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  Ctx* c;
+  CHK(tl_ctx(&c));
+  BatchGuard g{c, {}};
+  int32_t id;
+  CHK(ctx_from_values_host(c, values, n, run_optimize != 0, &id));
+  g.ids = {id};
+  return ctx_batch_fetch(c, id, 0, out);
+}
+
+int rbg_expand_values(const uint8_t* buf, size_t len, rbg_buffer* out) {
+  if (!out || (!buf && len)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  Ctx* c;
+  CHK(tl_ctx(&c));
+  BatchGuard g{c, {}};
+  int32_t id;
+  CHK(ctx_load_separate(c, &buf, &len, 1, &id));
+  g.ids = {id};
+  const uint64_t card = (uint64_t)c->batches[id]->long_card;
+  uint8_t* p = (uint8_t*)std::malloc(card * 4 + 4);
+  if (!p) return RBG_ERR_OUT_OF_MEMORY;
+  uint64_t got = 0;
+  const int st = ctx_to_values_host(c, id, 0, 0, card, reinterpret_cast<uint32_t*>(p), &got);
+  if (st != RBG_OK) {
+    std::free(p);
+    return st;
+  }
+  out->data = p;
+  out->len = (size_t)got * 4;
+  return RBG_OK;
 }
 
 // x.limit(maxcardinality) (RB/RoaringBitmap.java:2457-2476).  The cut is planned from the serialized

@@ -508,6 +508,29 @@ void launch_rd_fill(hipStream_t s, const CDesc* desc, const uint8_t* payload, ui
 // out[i] = op(q[i]) for n queries, in query order (-1: no such value)
 void launch_point(hipStream_t s, int op, PointArgs a, const uint32_t* q, uint64_t n, long long* out);
 
+// expand.hip: the values of ranks [first, first + count) of the bitmap (RoaringBitmap.toArray,
+// RB/RoaringBitmap.java:3224; BatchIterator.nextBatch), ascending, into out[0 .. count): u32, or i64
+// zero-extended (out64).  first + count <= cardinality; a needs the batch's rank directory.
+void launch_to_values(hipStream_t s, PointArgs a, uint64_t first, uint64_t count, bool out64, void* out);
+
+// build.hip: a one-bitmap key-major batch from n u32 values in device memory (any order, duplicates
+// allowed), RoaringBitmap.add(int...) / bitmapOf (RB/RoaringBitmap.java:483-570) [+ runOptimize].
+// flag: 65,536 bytes, zeroed by the caller; keys: min(n, 65536) u16; key_off: 65,537 u32; *n_ctr = C
+void launch_bld_keys(hipStream_t s, const uint32_t* v, uint64_t n, uint8_t* flag, uint16_t* keys, uint32_t* key_off,
+                     unsigned long long* n_ctr);
+// ws: C bitmaps of 8 KiB, zeroed by the caller; precheck: read a word before its atomic and skip the
+// atomic when the bits are set already
+void launch_bld_scatter(hipStream_t s, const uint32_t* v, uint64_t n, const uint32_t* key_off, uint32_t* ws,
+                        bool precheck);
+constexpr size_t kBldInfoBytes = 8;  // per container: the plan's (card, nruns, kind)
+// size[i] = slot bytes of container i; totals (u64, zeroed by the caller) += {#A, #B, #R, serialized
+// payload bytes, cardinality}
+void launch_bld_plan(hipStream_t s, const uint8_t* ws, uint64_t n_ctr, int run_optimize, void* info, uint64_t* size,
+                     unsigned long long* totals);
+// off: the exclusive scan of size[]; also writes bm_off = {0, C}
+void launch_bld_write(hipStream_t s, const uint8_t* ws, uint64_t n_ctr, const void* info, const uint64_t* off,
+                      const uint16_t* keys, CDesc* desc, uint32_t* bm, uint32_t* bm_off, uint8_t* payload);
+
 // decode.hip: portable-format decode on the device
 enum DecErr : uint32_t {
   DEC_OK = 0,

@@ -286,6 +286,96 @@ class Engine:
                                         out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
         return out
 
+    def _handshake(self, device):
+        """Orders the engine stream after torch's current stream on `device`; returns a function that,
+        called after the engine work is enqueued, makes the current stream wait for it.  As in
+        point_query: tensors made on the current stream are ready for the engine's kernels, torch's
+        allocator (which orders reuse on the current stream alone) cannot hand their memory out while
+        those kernels run, and the outputs are ready for work enqueued on the current stream."""
+        import torch
+        cur = torch.cuda.current_stream(device)
+        es = torch.cuda.ExternalStream(self.stream_ptr, device=device)
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        es.wait_event(ev)
+
+        def done():
+            d = torch.cuda.Event()
+            d.record(es)
+            cur.wait_event(d)
+        return done
+
+    def _check_tensor(self, what, t):
+        if t.device.type != "cuda" or t.device.index != self.device:
+            raise ValueError(f"{what}: the tensor must be on device {self.device}")
+
+    def from_values(self, values, run_optimize=False) -> int:
+        """A resident bitmap from its values, built on the device (rbg_ctx_from_values): RoaringBitmap.bitmapOf
+        / add(int...), with run_optimize followed by runOptimize() -> batch id of a one-bitmap batch, the same
+        as load([RoaringBitmap.from_values(values, run_optimize)]).  The values need not be sorted or distinct.
+        A numpy array or sequence of values below 2^32 is uploaded; a torch tensor on this engine's GPU is read
+        in place (rbg_ctx_from_values_device), int64 (the low 32 bits of every element are read, so -1 is
+        0xFFFFFFFF) or uint32, with point_query's stream handshake.  Synchronous either way: the container
+        count and the batch totals are read back."""
+        out = ctypes.c_int32()
+        if type(values).__module__.split(".")[0] == "torch":
+            import torch
+            self._check_tensor("from_values", values)
+            if values.dtype == torch.int64:  # the low 32 bits of every element (little-endian words)
+                v = values.contiguous().reshape(-1).view(torch.int32)[::2].contiguous()
+            elif values.dtype == torch.uint32:
+                v = values.contiguous()
+            else:
+                raise ValueError("from_values: an int64 or uint32 tensor is required")
+            v = v.reshape(-1)
+            done = self._handshake(values.device)
+            check(lib().rbg_ctx_from_values_device(self._ctx, ctypes.c_void_p(v.data_ptr()) if v.numel() else None,
+                                                   v.numel(), int(bool(run_optimize)), ctypes.byref(out)))
+            done()
+            return out.value
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        check(lib().rbg_ctx_from_values(self._ctx, v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size,
+                                        int(bool(run_optimize)), ctypes.byref(out)))
+        return out.value
+
+    def to_values(self, batch, ia=0, first=0, count=None, dtype=None):
+        """The values of ranks [first, first + count) of a resident bitmap (count None: to the end), ascending
+        and unsigned: toArray() and the window BatchIterator.nextBatch / limit walk (rbg_ctx_to_values).
+        dtype None or numpy's uint32 -> numpy uint32 array, synchronous.  dtype torch.uint32 or torch.int64
+        -> a torch tensor on this engine's GPU, written through the device entry point on the engine stream
+        with no host synchronisation (but for the first use of a batch, which builds its rank directory);
+        torch's current stream waits for it, as with point_query's result."""
+        first = int(first)
+        count = (1 << 64) - 1 if count is None else int(count)
+        if first < 0 or count < 0:
+            raise ValueError("to_values: first and count must not be negative")
+        n_out = ctypes.c_uint64()
+        # the window's size first (a null buffer: no device work): count may reach past the cardinality
+        check(lib().rbg_ctx_to_values_device(self._ctx, int(batch), int(ia), first, count, 0, None,
+                                             ctypes.byref(n_out)))
+        n = int(n_out.value)
+        if dtype is not None and type(dtype).__module__.split(".")[0] == "torch":
+            import torch
+            if dtype not in (torch.uint32, torch.int64):
+                raise ValueError("to_values: dtype torch.uint32 or torch.int64")
+            dev = torch.device("cuda", self.device)
+            out = torch.empty(n, dtype=dtype, device=dev)
+            if n == 0:
+                return out
+            done = self._handshake(dev)
+            check(lib().rbg_ctx_to_values_device(self._ctx, int(batch), int(ia), first, n,
+                                                 int(dtype == torch.int64), ctypes.c_void_p(out.data_ptr()),
+                                                 ctypes.byref(n_out)))
+            done()
+            return out
+        if dtype is not None and np.dtype(dtype) != np.uint32:
+            raise ValueError("to_values: a numpy result is uint32")
+        out = np.empty(n, dtype=np.uint32)
+        if n:
+            check(lib().rbg_ctx_to_values(self._ctx, int(batch), int(ia), first, n,
+                                          out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(n_out)))
+        return out
+
     def batch_counts(self, batch) -> np.ndarray:
         """containers per input bitmap of a batch"""
         n = self.batch_stats(batch)["bitmaps"]

@@ -199,11 +199,13 @@ class RoaringBitmap:
         return cls.from_values(values)
 
     @classmethod
-    def from_values(cls, values, run_optimize=False):
-        v = np.ascontiguousarray(np.asarray(values, dtype=np.int64).astype(np.uint32))
+    def from_values(cls, values, run_optimize=False, gpu=False):
+        """bitmapOf(values) [+ runOptimize()], built on the host (rbg_from_values); gpu=True: built on the
+        device (rbg_build_values), the same bytes."""
+        v = np.ascontiguousarray(np.asarray(values, dtype=np.int64).astype(np.uint32)).reshape(-1)
         b = _lib.rbg_buffer()
-        check(lib().rbg_from_values(v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, int(run_optimize),
-                                    ctypes.byref(b)))
+        f = lib().rbg_build_values if gpu else lib().rbg_from_values
+        check(f(v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, int(run_optimize), ctypes.byref(b)))
         return cls(take(b))
 
     @classmethod
@@ -272,9 +274,12 @@ class RoaringBitmap:
         check(lib().rbg_inspect(self._buf, len(self._buf), None, None, stats))
         return tuple(stats)
 
-    def toArray(self) -> np.ndarray:
+    def toArray(self, gpu=False) -> np.ndarray:
+        """RoaringBitmap.toArray() (RB/RoaringBitmap.java:3224) on the host (rbg_to_values); gpu=True: expanded
+        on the device (rbg_expand_values), the same values."""
         b = _lib.rbg_buffer()
-        check(lib().rbg_to_values(self._buf, len(self._buf), ctypes.byref(b)))
+        f = lib().rbg_expand_values if gpu else lib().rbg_to_values
+        check(f(self._buf, len(self._buf), ctypes.byref(b)))
         raw = take(b)
         return np.frombuffer(raw, dtype=np.uint32).copy()
 
