@@ -112,5 +112,73 @@ def perturbed_pair(rng, keys):
     return encode(c1), encode(c2)
 
 
+def sparse_keys(rng):
+    """9,000 to 10,000 sorted keys: more tasks than the 8,192 waves an MI355X holds, so some wave of every
+    one-wave-per-task kernel takes a second task.  0..299 dense (result tiles 64, 128, 192, 256 and the plan
+    workgroup 0 / 1 border), a dense block of 6,000 keys in the middle, blocks of 1, 2, 3 and 5 adjacent
+    keys at random places, keys 65534 and 65535, and a hole of 316 keys around one whole 256-key plan
+    workgroup (2 or 3) with a key on either side of the hole."""
+    g = int(rng.integers(2, 4))
+    hole_lo, hole_hi = 256 * g - 30, 256 * (g + 1) + 30  # [hole_lo, hole_hi) holds no key
+    mid = int(rng.integers(26000, 34000))
+    have = np.zeros(65536, dtype=bool)
+    have[:300] = True
+    have[mid:mid + 6000] = True
+    have[[hole_lo - 1, hole_hi, 65534, 65535]] = True
+    target = int(rng.integers(9300, 9700))
+    while int(have.sum()) < target:
+        n = (1, 2, 3, 5)[int(rng.integers(4))]
+        k = int(rng.integers(0, 65536 - n))
+        if k + n <= hole_lo or k >= hole_hi:
+            have[k:k + n] = True
+    return np.nonzero(have)[0]
+
+
+def empty_workgroup(keys):
+    """The first 256-key plan workgroup without a key that has keys on both sides, or None."""
+    per = np.bincount(np.asarray(keys) >> 8, minlength=256)
+    busy = np.nonzero(per)[0]
+    for w in range(int(busy[0]) + 1, int(busy[-1])):
+        if per[w] == 0:
+            return w
+    return None
+
+
+def tiny_values(rng, r):
+    """1 to 8 values: below 2,000 only (r < 1/3), above 63,000 only (r < 2/3), or both"""
+    n = int(rng.integers(1, 9))
+    if r < 1 / 3:
+        v = rng.integers(0, 2000, n)
+    elif r < 2 / 3:
+        v = rng.integers(63000, 65536, n)
+    else:
+        n = max(n, 2)
+        nl = int(rng.integers(1, n))
+        v = np.concatenate([rng.integers(0, 2000, nl), rng.integers(63000, 65536, n - nl)])
+    return np.unique(v).astype(np.uint16)
+
+
+def sparse_bitmap(rng, keys, heavy_every=97, run_every=0):
+    """A many-key bitmap of tiny array containers (see tiny_values: an addOffset of a few hundred leaves one part
+    empty, a whole output key empty, or both parts live); every heavy_every-th key holds a random MODES
+    container, so bitmaps, run containers above 2,047 runs and full containers land on late tasks too.
+    run_every: every run_every-th tiny container is a run container of one or two short runs."""
+    ctrs = []
+    for i, k in enumerate(keys):
+        if i % heavy_every == heavy_every - 1:
+            kind, vals = container(rng, MODES[int(rng.integers(len(MODES)))])
+        elif run_every and i % run_every == 0:
+            s = int(rng.integers(0, 2000))
+            vals = np.arange(s, s + int(rng.integers(1, 7)))
+            if rng.random() < 0.5:
+                s = int(rng.integers(63000, 65500))
+                vals = np.concatenate([vals, np.arange(s, s + int(rng.integers(1, 7)))])
+            kind, vals = R, vals.astype(np.uint16)
+        else:
+            kind, vals = A, tiny_values(rng, rng.random())
+        ctrs.append((int(k), kind, vals))
+    return encode(ctrs)
+
+
 def random_values(rng, n, universe=1 << 32):
     return rng.integers(0, universe, size=n, dtype=np.int64).astype(np.uint32)
