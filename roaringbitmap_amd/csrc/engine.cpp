@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -46,6 +47,10 @@ static void set_err(const std::string& s) { g_err = s; }
 constexpr size_t kSlack = 256;  // every device buffer carries read slack (group_copy)
 constexpr int kMaxKeys = 65536;
 constexpr size_t kLbHeader = 256;  // look-back state: error @64, result card @96
+// The largest serialized container a kernel stages in its scratch slot (a bitmap, 8192 B, or a run
+// container of 2048 runs; kSlotBytes, device.hpp, is this rounded up).  Every op's payload bound counts
+// on it: each result container is staged (<= kStagedMax B) or a clone of one input container.
+constexpr size_t kStagedMax = 8194;
 // tile statuses (kMaxTiles, device.hpp) follow the 65536 task statuses, tile cardinalities them
 
 // RBG_DEBUG_SYNC=1: synchronise and report after every pipeline stage (debugging aid)
@@ -67,12 +72,6 @@ static void dbg(hipStream_t s, const char* what) {
   last = now;
   std::fflush(stderr);
 }  // look-back state: ticket @0, error word @64, statuses @256
-
-// On an out-of-memory hipMalloc, the device buffers kept for reuse (Ctx::pool) are freed and the
-// allocation retried: first the pool of the context the calling thread works on, then, if that was
-// not enough, those of every other context on the device (defined after Ctx).  Every pooled buffer
-// freed this way is counted (rbg_pool_evictions), so memory pressure shows.
-static size_t release_pools_on(int device, int stage);
 
 struct DevBuf {
   void* p = nullptr;
@@ -97,31 +96,7 @@ struct DevBuf {
   ~DevBuf() {
     if (p) (void)hipFree(p);
   }
-  int ensure(size_t bytes) {
-    if (cap >= bytes && p) return RBG_OK;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    hipError_t e = hipMalloc(&p, bytes + kSlack);
-    if (e == hipErrorOutOfMemory) {
-      int dev = 0;
-      (void)hipGetLastError();
-      for (int stage = 0; stage < 2 && e == hipErrorOutOfMemory; stage++) {
-        if (hipGetDevice(&dev) != hipSuccess) break;
-        if (release_pools_on(dev, stage) > 0) {
-          e = hipMalloc(&p, bytes + kSlack);
-          if (e == hipErrorOutOfMemory) (void)hipGetLastError();
-        }
-      }
-    }
-    if (e != hipSuccess) {
-      p = nullptr;
-      set_err(std::string("hipMalloc(") + std::to_string(bytes) + ") failed: " + hipGetErrorString(e));
-      return e == hipErrorOutOfMemory ? RBG_ERR_OUT_OF_MEMORY : RBG_ERR_DEVICE;
-    }
-    cap = bytes;
-    return RBG_OK;
-  }
+  int ensure(size_t bytes);  // defined after Ctx: an out-of-memory allocation empties the contexts' pools
   template <class T>
   T* as() const {
     return reinterpret_cast<T*>(p);
@@ -147,7 +122,7 @@ struct Batch {
   int64_t n_kind[3] = {0, 0, 0};
   int64_t ser_bytes = 0;
   int64_t long_card = 0;
-  size_t max_ser = 0;  // Σ serialized payload of containers larger than 8194 B (long run inputs)
+  size_t max_ser = 0;  // Σ serialized payload of containers larger than kStagedMax (long run inputs)
   int32_t bsi_min = 0, bsi_max = 0;  // synthetic C5: min / max of the indexed values
   bool pair_cap_known = false;        // batched andCardinality: item capacity computed
   // made by runOptimize: kinds / payload bytes / run flags still in ro_stats (device: 5 u64 totals,
@@ -298,6 +273,36 @@ static size_t release_pools_on(int device, int stage) {
   }
   g_pool_evictions += n;
   return n;
+}
+
+// On an out-of-memory hipMalloc, the device buffers kept for reuse (Ctx::pool) are freed and the
+// allocation retried: first the pool of the context the calling thread works on, then, if that was
+// not enough, those of every other context on the device (release_pools_on).  Every pooled buffer
+// freed this way is counted (rbg_pool_evictions), so memory pressure shows.
+int DevBuf::ensure(size_t bytes) {
+  if (cap >= bytes && p) return RBG_OK;
+  if (p) (void)hipFree(p);
+  p = nullptr;
+  cap = 0;
+  hipError_t e = hipMalloc(&p, bytes + kSlack);
+  if (e == hipErrorOutOfMemory) {
+    int dev = 0;
+    (void)hipGetLastError();
+    for (int stage = 0; stage < 2 && e == hipErrorOutOfMemory; stage++) {
+      if (hipGetDevice(&dev) != hipSuccess) break;
+      if (release_pools_on(dev, stage) > 0) {
+        e = hipMalloc(&p, bytes + kSlack);
+        if (e == hipErrorOutOfMemory) (void)hipGetLastError();
+      }
+    }
+  }
+  if (e != hipSuccess) {
+    p = nullptr;
+    set_err(std::string("hipMalloc(") + std::to_string(bytes) + ") failed: " + hipGetErrorString(e));
+    return e == hipErrorOutOfMemory ? RBG_ERR_OUT_OF_MEMORY : RBG_ERR_DEVICE;
+  }
+  cap = bytes;
+  return RBG_OK;
 }
 
 // entry of a session call: the context's device, and the context out-of-memory retries empty first
@@ -850,8 +855,16 @@ static int ctx_serialize(Ctx* c) {
 }
 
 
-// operand range of bitmap i of a batch (must be contiguous: one-bitmap batch)
-static int operand(Batch* b, size_t i, const uint16_t** keys, const CDesc** desc, int* n) {
+// Bitmap i of a batch as the operand of a per-key op: the batch (statistics read), its container table
+// and container count.  The range must be contiguous: a one-bitmap key-major batch.
+struct Operand {
+  Batch* b;
+  const CDesc* desc;
+  int n;
+};
+static int resolve(Ctx* c, int32_t id, size_t i, Operand* op) {
+  Batch* b;
+  CHK(get_batch(c, id, &b));
   if (i >= b->n_bm) {
     set_err("bitmap index out of range");
     return RBG_ERR_ILLEGAL_ARGUMENT;
@@ -860,13 +873,53 @@ static int operand(Batch* b, size_t i, const uint16_t** keys, const CDesc** desc
     set_err("pairwise operands must be single-bitmap key-major batches with slot-aligned payloads");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  *keys = b->keys.as<uint16_t>();
-  *desc = b->desc.as<CDesc>();
-  *n = (int)b->n_ctr;
+  *op = Operand{b, b->desc.as<CDesc>(), (int)b->n_ctr};
   return RBG_OK;
 }
 
-// The rank directory of a batch operand() accepts (rankdir.hip): the container prefix cum, and per bitmap
+// Bracket of an op that is one compute launch: op_begin after prepare_output (the batches the result's
+// pass-through records point into, the first two phase marks), op_end after the launch (the placement
+// deferred, the last two marks, the launch's error).
+static void op_begin(Ctx* c, std::initializer_list<int32_t> src) {
+  c->pending_src = src;
+  c->mark(0);
+  c->mark(1);
+}
+static int op_end(Ctx* c) {
+  c->mark(2);
+  defer_place(c);
+  c->mark(3);
+  HIPCHK(hipGetLastError());
+  return RBG_OK;
+}
+
+// An op whose kernel may keep run containers above 2047 runs reserves them in the context's big-run
+// arena (Ctx::big; big_ctl = {bytes reserved, overflow flag}).  pass(BigRuns) enqueues one complete
+// attempt, its prepare_output included (the payload bound counts big.cap).  The arena is checked after
+// the pass (a synchronisation); a pass that overflowed counted every reservation, so the arena is grown
+// to that size and the pass run once more.  use_arena false: the pass runs once with no arena, nothing
+// is read back.
+template <class Pass>
+static int with_big_runs(Ctx* c, bool use_arena, const char* what, Pass&& pass) {
+  if (!use_arena) return pass(BigRuns{nullptr, nullptr, 0});
+  if (!c->big_ctl.p) CHK(c->big_ctl.ensure(16));
+  if (!c->big.p) CHK(c->big.ensure(16ull << 20));
+  for (int attempt = 0;; attempt++) {
+    HIPCHK(hipMemsetAsync(c->big_ctl.p, 0, 16, c->stream));
+    CHK(pass(BigRuns{c->big.as<uint8_t>(), c->big_ctl.as<unsigned long long>(), c->big.cap}));
+    unsigned long long used[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(used, c->big_ctl.p, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (!used[1]) return RBG_OK;
+    if (attempt) {
+      set_err(std::string(what) + ": the run-container arena overflowed twice");
+      return RBG_ERR_DEVICE;
+    }
+    CHK(c->big.ensure(used[0] + (used[0] >> 3) + 4096));
+  }
+}
+
+// The rank directory of a batch resolve() accepts (rankdir.hip): the container prefix cum, and per bitmap
 // / run container a u16 directory in an aux arena.  Sizes in one pass, two device scans, then the fill;
 // the host reads back the arena's size alone (8 bytes, once per batch) to allocate it exactly.
 // A build that fails part way leaves rd_ready false and whatever buffers it took on the batch: the next
@@ -897,15 +950,12 @@ static int ctx_rankdir(Ctx* c, Batch* b) {
 // n point queries (device memory, u32) against bitmap i of a batch into out (device memory, i64), in
 // query order, enqueued on the context stream
 static int ctx_point(Ctx* c, int op, int32_t batch, size_t i, const uint32_t* q_dev, size_t n, long long* out_dev) {
-  Batch* B;
-  CHK(get_batch(c, batch, &B));
-  const uint16_t* keys;
-  const CDesc* desc;
-  int nc;
-  CHK(operand(B, i, &keys, &desc, &nc));
+  Operand o;
+  CHK(resolve(c, batch, i, &o));
+  Batch* B = o.b;
   CHK(ctx_rankdir(c, B));
-  const PointArgs pa{B->key_off.as<uint32_t>(), desc, B->payload.as<uint8_t>(), B->rd_cum.as<uint64_t>(),
-                     B->rd_off.as<uint64_t>(), B->rd_aux.as<uint8_t>(), (uint32_t)nc};
+  const PointArgs pa{B->key_off.as<uint32_t>(), o.desc, B->payload.as<uint8_t>(), B->rd_cum.as<uint64_t>(),
+                     B->rd_off.as<uint64_t>(), B->rd_aux.as<uint8_t>(), (uint32_t)o.n};
   // RBG_PQ_NODIR=1 (measurement only, read at every call): rank with a bitmap's popcounts from word 0
   if (op == PT_RANK) {
     const char* e = std::getenv("RBG_PQ_NODIR");
@@ -939,12 +989,9 @@ static int ctx_point_host(Ctx* c, int op, int32_t batch, size_t i, const uint32_
 // from the batch's cardinality.
 static int ctx_to_values(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t count, bool out64, void* out_dev,
                          uint64_t* n_out) {
-  Batch* B;
-  CHK(get_batch(c, batch, &B));
-  const uint16_t* keys;
-  const CDesc* desc;
-  int nc;
-  CHK(operand(B, i, &keys, &desc, &nc));
+  Operand o;
+  CHK(resolve(c, batch, i, &o));
+  Batch* B = o.b;
   const uint64_t card = (uint64_t)B->long_card;
   const uint64_t cnt = first < card ? std::min<uint64_t>(count, card - first) : 0;
   if (n_out) *n_out = cnt;
@@ -954,8 +1001,8 @@ static int ctx_to_values(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
   CHK(ctx_rankdir(c, B));
-  const PointArgs pa{B->key_off.as<uint32_t>(), desc, B->payload.as<uint8_t>(), B->rd_cum.as<uint64_t>(),
-                     B->rd_off.as<uint64_t>(), B->rd_aux.as<uint8_t>(), (uint32_t)nc};
+  const PointArgs pa{B->key_off.as<uint32_t>(), o.desc, B->payload.as<uint8_t>(), B->rd_cum.as<uint64_t>(),
+                     B->rd_off.as<uint64_t>(), B->rd_aux.as<uint8_t>(), (uint32_t)o.n};
   launch_to_values(c->stream, pa, first, cnt, out64, out_dev);
   HIPCHK(hipGetLastError());
   return RBG_OK;
@@ -1058,7 +1105,7 @@ static int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt
   const bool has_run = h[3] != 0;
   b.ser_bytes = (int64_t)(header_size(C, has_run) + h[4]);
   b.long_card = (int64_t)h[5];
-  b.max_ser = 0;  // no container above 8194 serialized bytes
+  b.max_ser = 0;  // no container above kStagedMax serialized bytes
   b.h_bm_off = {0, (uint32_t)C};
   b.h_bm_nctr = {(uint32_t)C};
   b.h_bm_card = {b.long_card};
@@ -1163,50 +1210,28 @@ static int pipe_ranges() {
 // ImmutableRoaringBitmap.and / andNot and MutableRoaringBitmap's static and / andNot
 // (RB/buffer/ImmutableRoaringBitmap.java:299-325, 441-471; RB/buffer/MutableRoaringBitmap.java:235-301):
 // the pairwise plan, then k_pair_buf (the buffer package's container types).  A run result above
-// 2047 runs goes to the big-run arena; the arena is checked after the op and the op rerun once with
-// the size the first pass reserved (as the buffer naive_and chain, ctx_wide).
+// 2047 runs goes to the big-run arena (with_big_runs).
 static int ctx_pairwise_buffer(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, int key_lo, int key_hi) {
   key_lo = std::max(0, key_lo);
   key_hi = std::min(kMaxKeys, key_hi);
-  Batch *A, *B;
-  CHK(get_batch(c, ia, &A));
-  CHK(get_batch(c, ib, &B));
-  const uint16_t *ka, *kb;
-  const CDesc *da, *db;
-  int na, nb;
-  CHK(operand(A, ma, &ka, &da, &na));
-  CHK(operand(B, mb, &kb, &db, &nb));
+  Operand A, B;
+  CHK(resolve(c, ia, ma, &A));
+  CHK(resolve(c, ib, mb, &B));
   hipStream_t s = c->stream;
-  const size_t ub = std::max<size_t>(1, op == OP_AND ? (size_t)std::min(na, nb) : (size_t)na);
-  if (!c->big_ctl.p) CHK(c->big_ctl.ensure(16));
-  if (!c->big.p) CHK(c->big.ensure(16ull << 20));
-  for (int attempt = 0;; attempt++) {
+  const size_t ub = std::max<size_t>(1, op == OP_AND ? (size_t)std::min(A.n, B.n) : (size_t)A.n);
+  return with_big_runs(c, true, "buffer and / andNot", [&](const BigRuns& big) -> int {
     OutCtx oc;
-    CHK(prepare_output(c, ub, A->payload_bytes + B->payload_bytes + (size_t)8194 * ub + c->big.cap, &oc, false));
+    CHK(prepare_output(c, ub, A.b->payload_bytes + B.b->payload_bytes + kStagedMax * ub + big.cap, &oc, false));
     c->pending_src = {ia, ib};
     c->mark(0);
-    launch_plan_pairwise(s, op, key_lo, key_hi, A->key_off.as<uint32_t>(), da, A->payload.as<uint8_t>(),
-                         B->key_off.as<uint32_t>(), db, B->payload.as<uint8_t>(), c->wg_epoch.as<uint64_t>(),
+    launch_plan_pairwise(s, op, key_lo, key_hi, A.b->key_off.as<uint32_t>(), A.desc, A.b->payload.as<uint8_t>(),
+                         B.b->key_off.as<uint32_t>(), B.desc, B.b->payload.as<uint8_t>(), c->wg_epoch.as<uint64_t>(),
                          next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), c->zlb, c->ztile, oc.err);
-    HIPCHK(hipMemsetAsync(c->big_ctl.p, 0, 16, s));
     c->mark(1);
     launch_pair_buf(s, op, grid_for(ub, 65536), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(),
-                    A->payload.as<uint8_t>(), B->payload.as<uint8_t>(), oc,
-                    BigRuns{c->big.as<uint8_t>(), c->big_ctl.as<unsigned long long>(), c->big.cap});
-    c->mark(2);
-    defer_place(c);
-    c->mark(3);
-    HIPCHK(hipGetLastError());
-    unsigned long long used[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(used, c->big_ctl.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (!used[1]) return RBG_OK;
-    if (attempt) {
-      set_err("buffer and / andNot: the run-container arena overflowed twice");
-      return RBG_ERR_DEVICE;
-    }
-    CHK(c->big.ensure(used[0] + (used[0] >> 3) + 4096));
-  }
+                    A.b->payload.as<uint8_t>(), B.b->payload.as<uint8_t>(), oc, big);
+    return op_end(c);
+  });
 }
 
 // RoaringBitmap.orNot(x1, x2, rangeEnd) (static, RB/RoaringBitmap.java:1521-1603) and x1.orNot(x2,
@@ -1218,33 +1243,23 @@ static int ctx_ornot(Ctx* c, int32_t ia, size_t ma, int32_t ib, size_t mb, int64
     set_err("rangeEnd should be in [0, 0xffffffff + 1]");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  Batch *A, *B;
-  CHK(get_batch(c, ia, &A));
-  CHK(get_batch(c, ib, &B));
-  const uint16_t *ka, *kb;
-  const CDesc *da, *db;
-  int na, nb;
-  CHK(operand(A, ma, &ka, &da, &na));
-  CHK(operand(B, mb, &kb, &db, &nb));
+  Operand A, B;
+  CHK(resolve(c, ia, ma, &A));
+  CHK(resolve(c, ib, mb, &B));
   const int max_key = range_end == 0 ? -1 : (int)((range_end - 1) >> 16);
   const int last_run = (range_end & 0xFFFF) == 0 ? 0x10000 : (int)(range_end & 0xFFFF);
   hipStream_t s = c->stream;
-  const size_t ub = std::max<size_t>(1, std::min<size_t>(kMaxKeys, (size_t)(max_key + 1) + (size_t)na));
+  const size_t ub = std::max<size_t>(1, std::min<size_t>(kMaxKeys, (size_t)(max_key + 1) + (size_t)A.n));
   if (!c->ornot_plan.p) CHK(c->ornot_plan.ensure(sizeof(OrNotPlan)));
   OutCtx oc;
-  CHK(prepare_output(c, ub, A->payload_bytes + B->payload_bytes + (size_t)8194 * ub, &oc, false));
-  c->pending_src = {ia, ib};
-  c->mark(0);
-  c->mark(1);
-  launch_ornot(s, A->key_off.as<uint32_t>(), da, A->payload.as<uint8_t>(), na, B->key_off.as<uint32_t>(), db,
-               B->payload.as<uint8_t>(), nb, max_key, last_run, flags, c->ornot_plan.as<OrNotPlan>(),
+  CHK(prepare_output(c, ub, A.b->payload_bytes + B.b->payload_bytes + kStagedMax * ub, &oc, false));
+  op_begin(c, {ia, ib});
+  launch_ornot(s, A.b->key_off.as<uint32_t>(), A.desc, A.b->payload.as<uint8_t>(), A.n, B.b->key_off.as<uint32_t>(),
+               B.desc, B.b->payload.as<uint8_t>(), B.n, max_key, last_run, flags, c->ornot_plan.as<OrNotPlan>(),
                c->wg_epoch.as<uint64_t>(), next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb,
                c->ztile, grid_for(ub, 65536));
-  c->mark(2);
-  defer_place(c);
-  c->mark(3);
-  HIPCHK(hipGetLastError());
-  if (max_key < 0 && na == 0 && nb > 0) {
+  CHK(op_end(c));
+  if (max_key < 0 && A.n == 0 && B.n > 0) {
     OrNotPlan pl;
     HIPCHK(hipMemcpyAsync(&pl, c->ornot_plan.p, sizeof(pl), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
@@ -1257,24 +1272,43 @@ static int ctx_ornot(Ctx* c, int32_t ia, size_t ma, int32_t ib, size_t mb, int64
   return RBG_OK;
 }
 
-// static add / remove / flip(rb, rangeStart, rangeEnd) (RB/RoaringBitmap.java:298-345, 995-1040, 626-668;
-// buf: MutableRoaringBitmap's, RB/buffer/MutableRoaringBitmap.java:152-205, 649-700, 455-505), rangemut.hip.
-// rangeSanityCheck (:204-213); rangeEnd <= rangeStart gives a clone.  A run result above 2047 runs goes
-// to the big-run arena; the arena is checked after the op and the op rerun once with the size the first
-// pass reserved (as ctx_pairwise_buffer).
-static int ctx_range_mut(Ctx* c, int op, int32_t ia, size_t ma, int64_t start, int64_t end, bool buf) {
-  if (op < RMUT_ADD || (op > RMUT_ADD_INPLACE && op != RMUT_RANGE)) return RBG_ERR_ILLEGAL_ARGUMENT;
+// rangeSanityCheck (RB/RoaringBitmap.java:204-213)
+static int check_range(int64_t start, int64_t end) {
   if (start < 0 || start > 0xFFFFFFFFll || end < 0 || end > 0x100000000ll) {
     set_err("rangeStart=" + std::to_string(start) + " should be in [0, 0xffffffff], rangeEnd=" + std::to_string(end) +
             " in [0, 0xffffffff + 1]");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  Batch* A;
-  CHK(get_batch(c, ia, &A));
-  const uint16_t* ka;
-  const CDesc* da;
-  int na;
-  CHK(operand(A, ma, &ka, &da, &na));
+  return RBG_OK;
+}
+
+// One k_rmut launch over operand A (batch ia) into at most ub result containers (rangemut.hip): the
+// range mutations, removeRunCompression and limit.  A run result above 2047 runs goes to the big-run
+// arena (with_big_runs).  The kernel reaches the arena only for the first and the last key of a range and
+// for limit's cut key (the keys between are cloned, emptied or replaced by the full run): at most two
+// containers of at most 131,074 B in one call, which the arena's initial 16 MiB always holds, so the
+// runner's second pass is never taken from here.
+static int run_rmut(Ctx* c, int32_t ia, const Operand& A, RmutArgs ra, bool buf, size_t ub, bool use_arena,
+                    const char* what) {
+  return with_big_runs(c, use_arena, what, [&](const BigRuns& big) -> int {
+    OutCtx oc;
+    CHK(prepare_output(c, ub, A.b->payload_bytes + kStagedMax * ub + big.cap, &oc, false));
+    op_begin(c, {ia});
+    launch_rmut(c->stream, A.b->key_off.as<uint32_t>(), A.desc, A.b->payload.as<uint8_t>(), ra, buf,
+                c->wg_epoch.as<uint64_t>(), next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb,
+                c->ztile, big, grid_for(ub, 65536));
+    return op_end(c);
+  });
+}
+
+// static add / remove / flip(rb, rangeStart, rangeEnd) (RB/RoaringBitmap.java:298-345, 995-1040, 626-668;
+// buf: MutableRoaringBitmap's, RB/buffer/MutableRoaringBitmap.java:152-205, 649-700, 455-505), rangemut.hip.
+// rangeSanityCheck (:204-213); rangeEnd <= rangeStart gives a clone.
+static int ctx_range_mut(Ctx* c, int op, int32_t ia, size_t ma, int64_t start, int64_t end, bool buf) {
+  if (op < RMUT_ADD || (op > RMUT_ADD_INPLACE && op != RMUT_RANGE)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  CHK(check_range(start, end));
+  Operand A;
+  CHK(resolve(c, ia, ma, &A));
   RmutArgs ra{op, 1, 0, 0, 0};  // end <= start: no key in the range, every container cloned
   if (end > start) {  // (char) casts: Util.highbits / lowbits
     ra.hbs = (int)((uint64_t)start >> 16 & 0xFFFF);
@@ -1283,94 +1317,49 @@ static int ctx_range_mut(Ctx* c, int op, int32_t ia, size_t ma, int64_t start, i
     ra.lbl = (int)((end - 1) & 0xFFFF);
   }
   const size_t in_range = end > start ? (size_t)(ra.hbl - ra.hbs + 1) : 0;
-  const size_t ub = std::max<size_t>(1, std::min<size_t>(kMaxKeys, (size_t)na + in_range));
-  hipStream_t s = c->stream;
-  if (!c->big_ctl.p) CHK(c->big_ctl.ensure(16));
-  if (!c->big.p) CHK(c->big.ensure(16ull << 20));
-  for (int attempt = 0;; attempt++) {
-    OutCtx oc;
-    CHK(prepare_output(c, ub, A->payload_bytes + (size_t)8194 * ub + c->big.cap, &oc, false));
-    c->pending_src = {ia};
-    c->mark(0);
-    HIPCHK(hipMemsetAsync(c->big_ctl.p, 0, 16, s));
-    c->mark(1);
-    launch_rmut(s, A->key_off.as<uint32_t>(), da, A->payload.as<uint8_t>(), ra, buf, c->wg_epoch.as<uint64_t>(),
-                next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb, c->ztile,
-                BigRuns{c->big.as<uint8_t>(), c->big_ctl.as<unsigned long long>(), c->big.cap}, grid_for(ub, 65536));
-    c->mark(2);
-    defer_place(c);
-    c->mark(3);
-    HIPCHK(hipGetLastError());
-    unsigned long long used[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(used, c->big_ctl.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (!used[1]) return RBG_OK;
-    if (attempt) {
-      set_err("range add / remove: the run-container arena overflowed twice");
-      return RBG_ERR_DEVICE;
-    }
-    CHK(c->big.ensure(used[0] + (used[0] >> 3) + 4096));
-  }
+  const size_t ub = std::max<size_t>(1, std::min<size_t>(kMaxKeys, (size_t)A.n + in_range));
+  return run_rmut(c, ia, A, ra, buf, ub, true, "range add / remove");
 }
 
 // x.removeRunCompression() (RB/RoaringBitmap.java:2738-2749; the buffer package's alike): every run
-// container through toBitmapOrArrayContainer (RB/RunContainer.java:2300-2323), the rest cloned; rangemut.hip
+// container through toBitmapOrArrayContainer (RB/RunContainer.java:2300-2323), the rest cloned; rangemut.hip.
+// RunContainer.toBitmapOrArrayContainer never makes a run container: no big-run arena (RMUT_DERUN's kernel
+// has no path to it)
 static int ctx_remove_run_compression(Ctx* c, int32_t ia, size_t ma) {
-  Batch* A;
-  CHK(get_batch(c, ia, &A));
-  const uint16_t* ka;
-  const CDesc* da;
-  int na;
-  CHK(operand(A, ma, &ka, &da, &na));
-  const RmutArgs ra{RMUT_DERUN, 1, 0, 0, 0};
-  const size_t ub = std::max<size_t>(1, (size_t)na);
-  hipStream_t s = c->stream;
-  OutCtx oc;
-  CHK(prepare_output(c, ub, A->payload_bytes + (size_t)8194 * ub, &oc, false));
-  c->pending_src = {ia};
-  c->mark(0);
-  c->mark(1);
-  // RunContainer.toBitmapOrArrayContainer never makes a run container: no big-run arena (RMUT_DERUN's kernel
-  // has no path to it)
-  launch_rmut(s, A->key_off.as<uint32_t>(), da, A->payload.as<uint8_t>(), ra, false, c->wg_epoch.as<uint64_t>(),
-              next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb, c->ztile,
-              BigRuns{nullptr, nullptr, 0}, grid_for(ub, 65536));
-  c->mark(2);
-  defer_place(c);
-  c->mark(3);
-  HIPCHK(hipGetLastError());
-  return RBG_OK;
+  Operand A;
+  CHK(resolve(c, ia, ma, &A));
+  return run_rmut(c, ia, A, RmutArgs{RMUT_DERUN, 1, 0, 0, 0}, false, std::max<size_t>(1, (size_t)A.n), false,
+                  "removeRunCompression");
+}
+
+// The device half of x.limit(maxcardinality) (RB/RoaringBitmap.java:2457-2476; the cut is planned on the
+// host, rbg_limit): keys before cut_key cloned, its container cut to the leftover by k_rmut<RMUT_LIMIT>,
+// the rest dropped.
+static int ctx_limit(Ctx* c, int32_t ia, size_t ma, int cut_key, int leftover) {
+  Operand A;
+  CHK(resolve(c, ia, ma, &A));
+  return run_rmut(c, ia, A, RmutArgs{RMUT_LIMIT, cut_key, leftover, 0, 0}, false, std::max<size_t>(1, (size_t)A.n),
+                  true, "limit");
 }
 
 // RoaringBitmap.addOffset(x, offset) (RB/RoaringBitmap.java:230-288; MutableRoaringBitmap.addOffset,
 // RB/buffer/MutableRoaringBitmap.java:84-142, the same bytes), addoffset.hip.  The container offset is
 // the floor of offset / 65536 (:233-234); outside [-65536, 65535] the result is empty (:235-237).
 static int ctx_add_offset(Ctx* c, int32_t ia, size_t ma, int64_t offset) {
-  Batch* A;
-  CHK(get_batch(c, ia, &A));
-  const uint16_t* ka;
-  const CDesc* da;
-  int na;
-  CHK(operand(A, ma, &ka, &da, &na));
+  Operand A;
+  CHK(resolve(c, ia, ma, &A));
   const int64_t co = offset < 0 ? (offset - 65535) / 65536 : offset / 65536;
   AoffArgs aa{0, 0, 1};
   if (co >= -65536 && co < 65536) aa = AoffArgs{(int)co, (int)(offset - co * 65536), 0};
-  // each input container gives at most two output containers, each staged (<= 8194 B) or a clone
-  const size_t ub = std::max<size_t>(1, std::min<size_t>(kMaxKeys, 2 * (size_t)na));
-  hipStream_t s = c->stream;
+  // each input container gives at most two output containers, each staged (<= kStagedMax) or a clone
+  const size_t ub = std::max<size_t>(1, std::min<size_t>(kMaxKeys, 2 * (size_t)A.n));
   OutCtx oc;
-  CHK(prepare_output(c, ub, A->payload_bytes + (size_t)8194 * ub, &oc, false));
-  c->pending_src = {ia};
-  c->mark(0);
-  c->mark(1);
-  launch_aoff(s, A->key_off.as<uint32_t>(), da, A->payload.as<uint8_t>(), aa, c->wg_epoch.as<uint64_t>(),
-              next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb, c->ztile,
-              grid_for(ub, 65536));
-  c->mark(2);
-  defer_place(c);
-  c->mark(3);
-  HIPCHK(hipGetLastError());
-  return RBG_OK;
+  CHK(prepare_output(c, ub, A.b->payload_bytes + kStagedMax * ub, &oc, false));
+  op_begin(c, {ia});
+  launch_aoff(c->stream, A.b->key_off.as<uint32_t>(), A.desc, A.b->payload.as<uint8_t>(), aa,
+              c->wg_epoch.as<uint64_t>(), next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb,
+              c->ztile, grid_for(ub, 65536));
+  return op_end(c);
 }
 
 static int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, bool card_only, int key_lo = 0,
@@ -1397,14 +1386,12 @@ static int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_
   if (op < 0 || op > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
   key_lo = std::max(0, key_lo);
   key_hi = std::min(kMaxKeys, key_hi);
-  Batch *A, *B;
-  CHK(get_batch(c, ia, &A));
-  CHK(get_batch(c, ib, &B));
-  const uint16_t *ka, *kb;
-  const CDesc *da, *db;
-  int na, nb;
-  CHK(operand(A, ma, &ka, &da, &na));
-  CHK(operand(B, mb, &kb, &db, &nb));
+  Operand oa, ob;
+  CHK(resolve(c, ia, ma, &oa));
+  CHK(resolve(c, ib, mb, &ob));
+  Batch *A = oa.b, *B = ob.b;
+  const CDesc *da = oa.desc, *db = ob.desc;
+  const int na = oa.n, nb = ob.n;
   hipStream_t s = c->stream;
   const int plan_op = card_only ? OP_AND : op;
   size_t ub;
@@ -1421,7 +1408,7 @@ static int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_
   const size_t nkeys = key_hi > key_lo ? (size_t)(key_hi - key_lo) : 0;
   const bool direct = nkeys > 0 && 2 * ub >= nkeys && !force_plan;
   OutCtx oc;
-  CHK(prepare_output(c, direct ? std::max(ub, nkeys) : ub, A->payload_bytes + B->payload_bytes + (size_t)8194 * ub,
+  CHK(prepare_output(c, direct ? std::max(ub, nkeys) : ub, A->payload_bytes + B->payload_bytes + kStagedMax * ub,
                      &oc, card_only));
   c->pending_src = {ia, ib};
   c->mark(0);
@@ -1471,7 +1458,30 @@ static int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_
   return RBG_OK;
 }
 
-static int batch_host_index(Ctx* c, Batch* b);
+
+// Host index of a batch's containers, built once per batch: the container table and,
+// per input bitmap, its container positions (in key order).
+static int batch_host_index(Ctx* c, Batch* b) {
+  if (b->h_index) return RBG_OK;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  b->h_desc.resize(b->n_ctr);
+  if (b->n_ctr) HIPCHK(hipMemcpy(b->h_desc.data(), b->desc.p, sizeof(CDesc) * b->n_ctr, hipMemcpyDeviceToHost));
+  b->h_pos_off.assign(b->n_bm + 1, 0);
+  b->h_pos.resize(b->n_ctr);
+  if ((b->n_bm == 1 || !b->key_major) && b->h_bm_off.size() == b->n_bm + 1) {
+    for (size_t i = 0; i <= b->n_bm; i++) b->h_pos_off[i] = b->h_bm_off[i];
+    for (size_t p = 0; p < b->n_ctr; p++) b->h_pos[p] = (uint32_t)p;
+  } else {  // key-major: counting sort of the positions by input bitmap (stable, so key order)
+    std::vector<uint32_t> bm(b->n_ctr);
+    if (b->n_ctr) HIPCHK(hipMemcpy(bm.data(), b->bm.p, 4 * b->n_ctr, hipMemcpyDeviceToHost));
+    for (uint32_t x : bm) b->h_pos_off[x + 1]++;
+    for (size_t i = 0; i < b->n_bm; i++) b->h_pos_off[i + 1] += b->h_pos_off[i];
+    std::vector<uint32_t> fill(b->h_pos_off.begin(), b->h_pos_off.end() - 1);
+    for (size_t p = 0; p < b->n_ctr; p++) b->h_pos[fill[bm[p]]++] = (uint32_t)p;
+  }
+  b->h_index = true;
+  return RBG_OK;
+}
 
 // Chain order of horizontal_or / horizontal_xor (RB/FastAggregation.java:124-289): the
 // reference drains a java.util.PriorityQueue of one container pointer per bitmap, ordered
@@ -1667,7 +1677,7 @@ static int ctx_pq(Ctx* c, int op, Batch* B, int32_t id, int key_lo, int key_hi) 
   const size_t N = B->n_bm;
   const size_t ub = std::min<size_t>(kMaxKeys, std::max<size_t>(B->n_ctr, 1));
   OutCtx oc;
-  CHK(prepare_output(c, ub, (size_t)8194 * ub + B->max_ser, &oc, false));
+  CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser, &oc, false));
   c->pending_src = {id};
   c->mark(0);
   // one task per union key (an empty aggregate has none: new RoaringBitmap())
@@ -1955,19 +1965,14 @@ static int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const in
     plan_mode = 2;
   }
   // the buffer naive_and chain may keep run containers of more than 2047 runs: they go to the
-  // big-run arena, checked after the op (rerun once with the size the first pass reserved)
+  // big-run arena (with_big_runs)
   const bool big_runs = buffer && mode == WIDE_AND_NAIVE && N > 0;
-  if (big_runs) {
-    if (!c->big_ctl.p) CHK(c->big_ctl.ensure(16));
-    if (!c->big.p) CHK(c->big.ensure(16ull << 20));
-  }
-  for (int attempt = 0;; attempt++) {
+  return with_big_runs(c, big_runs, "naive_and", [&](const BigRuns& big) -> int {
     const size_t ub = std::min<size_t>(kMaxKeys, std::max<size_t>(B->n_ctr, 1));
     OutCtx oc;
-    // each result container is staged (<= 8194 B) or a clone of one input container
-    CHK(prepare_output(c, ub, (size_t)8194 * ub + B->max_ser + (big_runs ? c->big.cap : 0), &oc, card_only));
+    CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser + big.cap, &oc, card_only));
     // OR results are bitmaps whenever more than 4096 values survive: write those in place
-    // (8192 t < 8194 ub, inside the payload region)
+    // (8192 t < kStagedMax ub, inside the payload region)
     if (!card_only && (mode == WIDE_OR || mode == WIDE_LAZY_CHAIN)) oc.spec = c->pending.spec = 1;
     c->pending_src = {id};
     if (!skip.empty()) {
@@ -1993,10 +1998,7 @@ static int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const in
     wa.chain = chain;
     wa.rd_bytes = c->prof_cap > 0 && c->rd_ctr.p ? c->rd_ctr.as<unsigned long long>() : nullptr;
     wa.buffer = buffer ? 1u : 0u;
-    if (big_runs) {
-      HIPCHK(hipMemsetAsync(c->big_ctl.p, 0, 16, s));
-      wa.big = BigRuns{c->big.as<uint8_t>(), c->big_ctl.as<unsigned long long>(), c->big.cap};
-    }
+    wa.big = big;
     c->mark(1);
     launch_wide(s, mode, grid_for(ub, 65536), c->tasks.as<Task>(), c->ntasks.as<uint32_t>(), wa, oc,
                 c->task_card.as<uint32_t>());
@@ -2009,18 +2011,8 @@ static int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const in
     }
     c->mark(3);
     HIPCHK(hipGetLastError());
-    if (!big_runs) break;
-    unsigned long long used[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(used, c->big_ctl.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (!used[1]) break;
-    if (attempt) {
-      set_err("naive_and: the run-container arena overflowed twice");
-      return RBG_ERR_DEVICE;
-    }
-    CHK(c->big.ensure(used[0] + (used[0] >> 3) + 4096));  // the first pass counted every reservation
-  }
-  return RBG_OK;
+    return RBG_OK;
+  });
 }
 
 // compareUsingMinMax (BSI/:515-579): 0 = run the circuit, 1 = all, 2 = empty
@@ -2066,7 +2058,7 @@ static int ctx_bsi(Ctx* c, int32_t id, int op, int nbits, int has_found, int32_t
   }
   const size_t ub = std::min<size_t>(kMaxKeys, std::max<size_t>(B->n_ctr, 1));
   OutCtx oc;
-  CHK(prepare_output(c, ub, (size_t)8194 * ub + B->max_ser, &oc, op == BSI_SUM_ONLY));
+  CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser, &oc, op == BSI_SUM_ONLY));
   c->pending_src = {id};
   const uint32_t need = mode == -1 ? 0xFFFFFFFFu : (op == BSI_SUM_ONLY ? (uint32_t)(nbits + 1) : 0u);
   BsiScratch sc{};
@@ -2198,7 +2190,7 @@ static int owen_order(Ctx* c, int M, uint32_t nt) {
 }
 
 // op: RBG_BSI_* (compare) or RBG_BSI_RANGE_NEQ_DIRECT; the batch is [ebM, bA[0..nbits-1], foundSet?].
-// Synchronous: the big-run arena is checked after the op (and the op rerun with a larger arena).
+// Synchronous: the big-run arena is checked after the op (with_big_runs).
 static int ctx_bsi_buffer(Ctx* c, int32_t id, int op, int nbits, int has_found, int32_t start, int32_t end,
                           int32_t min_value, int32_t max_value) {
   Batch* B;
@@ -2243,11 +2235,9 @@ static int ctx_bsi_buffer(Ctx* c, int32_t id, int op, int nbits, int has_found, 
   }
   const int M = __builtin_popcount(zeros);
   const size_t ub = std::min<size_t>(kMaxKeys, std::max<size_t>(B->n_ctr, 1));
-  if (!c->big_ctl.p) CHK(c->big_ctl.ensure(16));
-  if (!c->big.p) CHK(c->big.ensure(16ull << 20));
-  for (int attempt = 0;; attempt++) {
+  return with_big_runs(c, true, "bsi", [&](const BigRuns& big) -> int {
     OutCtx oc;
-    CHK(prepare_output(c, ub, (size_t)8194 * ub + B->max_ser + c->big.cap, &oc, false));
+    CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser + big.cap, &oc, false));
     c->pending_src = {id};
     const uint32_t need = mode == -1 ? 0xFFFFFFFFu : 0xFFFFFFFEu;  // every key of any input
     c->mark(0);
@@ -2255,7 +2245,6 @@ static int ctx_bsi_buffer(Ctx* c, int32_t id, int op, int nbits, int has_found, 
                     c->flag.as<uint8_t>(), c->wg_count.as<uint32_t>(), c->zlb, c->ztile, nullptr, nullptr);
     launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(), c->tasks.as<Task>(),
                    c->ntasks.as<uint32_t>());
-    HIPCHK(hipMemsetAsync(c->big_ctl.p, 0, 16, s));
     c->mark(1);
     WideArgs wa{};
     wa.desc = B->desc.as<CDesc>();
@@ -2271,7 +2260,7 @@ static int ctx_bsi_buffer(Ctx* c, int32_t id, int op, int nbits, int has_found, 
     p.found_input = nbits + 1;
     p.owen_zeros = zeros;
     p.owen_ones = ones;
-    p.big = BigRuns{c->big.as<uint8_t>(), c->big_ctl.as<unsigned long long>(), c->big.cap};
+    p.big = big;
     const int grid = grid_for(ub, 65536);
     if (mode >= 0 && M >= 3) {  // the chain order needs horizontal_or's queue: every orInput's type first
       CHK(c->owen_tb.ensure((size_t)16 * 32 * ub));
@@ -2287,20 +2276,8 @@ static int ctx_bsi_buffer(Ctx* c, int32_t id, int op, int nbits, int has_found, 
       p.owen_order = c->owen_ord.as<uint8_t>();
     }
     if (mode >= 0) launch_bsi_buf(s, grid, c->tasks.as<Task>(), c->ntasks.as<uint32_t>(), wa, p, oc);
-    c->mark(2);
-    defer_place(c);
-    c->mark(3);
-    HIPCHK(hipGetLastError());
-    unsigned long long used[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(used, c->big_ctl.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (!used[1]) return RBG_OK;
-    if (attempt) {
-      set_err("bsi: the run-container arena overflowed twice");
-      return RBG_ERR_DEVICE;
-    }
-    CHK(c->big.ensure(used[0] + (used[0] >> 3) + 4096));  // the first pass counted every reservation
-  }
+    return op_end(c);
+  });
 }
 
 // (sum, count) of the last BSI call: k_bsi_sum_final's Java longs, read back
@@ -2446,838 +2423,19 @@ static int ctx_fetch(Ctx* c, rbg_buffer* out) {
   return RBG_OK;
 }
 
-// ---------------------------------------------------------------------------
-// thread-local one-shot contexts
-// ---------------------------------------------------------------------------
-static std::mutex g_dev_mu;
-static uint64_t g_dev_mask = 1;
-
-struct TLCtx {
-  std::unique_ptr<Ctx> ctx;
-  int device = -1;
-};
-static thread_local TLCtx tl;
-
-static int tl_ctx(Ctx** out) {
-  int dev;
-  {
-    std::lock_guard<std::mutex> g(g_dev_mu);
-    uint64_t m = g_dev_mask;
-    dev = m ? __builtin_ctzll(m) : 0;
-  }
-  if (!tl.ctx || tl.device != dev) {
-    std::unique_ptr<Ctx> c(new Ctx());
-    CHK(ctx_init(c.get(), dev));
-    tl.ctx = std::move(c);
-    tl.device = dev;
-  }
-  CHK(enter(tl.ctx.get()));
-  *out = tl.ctx.get();
-  return RBG_OK;
-}
-
-
-}  // namespace rbg
-
-using namespace rbg;
-
-struct rbg_ctx {
-  Ctx c;
-};
-
-extern "C" {
-
-int rbg_version(void) { return 1; }
-
-void rbg_trim(void) {
-  std::lock_guard<std::mutex> g(g_out_mu);
-  for (const auto& e : g_out_cache) std::free(e.first);
-  g_out_cache.clear();
-}
-
-uint64_t rbg_pool_evictions(void) { return g_pool_evictions.load(); }
-const char* rbg_last_error(void) { return g_err.c_str(); }
-
-void rbg_free(rbg_buffer* buf) {
-  if (!buf) return;
-  if (buf->data) {
-    std::lock_guard<std::mutex> g(g_out_mu);
-    const auto it = g_out_live.find(buf->data);
-    if (it != g_out_live.end()) {  // a large result buffer: kept for reuse (the oldest kept one freed)
-      g_out_cache.emplace_back(it->first, it->second);
-      g_out_live.erase(it);
-      while (g_out_cache.size() > kOutCacheMax || (!g_out_cache.empty() && out_cache_bytes() > kOutCacheBytes)) {
-        std::free(g_out_cache.front().first);
-        g_out_cache.erase(g_out_cache.begin());
-      }
-      buf->data = nullptr;
-      buf->len = 0;
-      return;
-    }
-  }
-  std::free(buf->data);
-  buf->data = nullptr;
-  buf->len = 0;
-}
-
-int rbg_set_devices(uint64_t mask) {
-  int n = 0;
-  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
-    set_err("no HIP device");
-    return RBG_ERR_DEVICE;
-  }
-  uint64_t usable = mask & ((n >= 64) ? ~0ULL : ((1ULL << n) - 1));
-  if (!usable) {
-    set_err("device mask selects no present device");
-    return RBG_ERR_DEVICE;
-  }
-  std::lock_guard<std::mutex> g(g_dev_mu);
-  g_dev_mask = usable;
-  return __builtin_popcountll(usable);
-}
-
-int rbg_pairwise(int op, const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, rbg_buffer* out) {
-  if (!out || op < 0 || op > RBG_ANDNOT_BUFFER) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  const uint8_t* bufs[2] = {a, b};
-  const size_t lens[2] = {a_len, b_len};
-  int32_t ids[2];
-  CHK(ctx_load_separate(c, bufs, lens, 2, ids));  // one upload for both operands
-  g.ids = {ids[0], ids[1]};
-  CHK(ctx_pairwise(c, op, ids[0], 0, ids[1], 0, false, 0, kMaxKeys, op <= RBG_ANDNOT ? pipe_ranges() : 0));
-  return ctx_fetch(c, out);
-}
-
-static int ctx_batch_fetch(Ctx* c, int32_t batch, size_t i, rbg_buffer* out);
-int rbg_pairwise_inplace(int op, const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int same_object,
-                         rbg_buffer* out) {
-  if (!out || op < 0 || op > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (same_object) {
-    // x1.and(x1) / x1.or(x1) return at once (x1 unchanged); x1.xor(x1) / x1.andNot(x1) clear it
-    // (RB/RoaringBitmap.java:1271, 2482, 3297-3300, 1347-1350)
-    if (op == RBG_XOR || op == RBG_ANDNOT) {
-      static const uint8_t kEmpty[8] = {0x3A, 0x30, 0, 0, 0, 0, 0, 0};
-      uint8_t* p = (uint8_t*)std::malloc(8);
-      if (!p) return RBG_ERR_OUT_OF_MEMORY;
-      std::memcpy(p, kEmpty, 8);
-      out->data = p;
-      out->len = 8;
-      return RBG_OK;
-    }
-    // x1 unchanged: validated on the host like any input, then its own bytes back (no device call)
-    HostBitmap hb;
-    std::string err;
-    const int st = parse(a, a_len, &hb, &err);
-    if (st) {
-      set_err(err);
-      return st;
-    }
-    uint8_t* p = out_alloc(hb.consumed);
-    if (!p) return RBG_ERR_OUT_OF_MEMORY;
-    std::memcpy(p, a, hb.consumed);
-    out->data = p;
-    out->len = hb.consumed;
-    return RBG_OK;
-  }
-  // x1.and / xor / andNot(x2) in place type like the static ops (Container.iand / ixor / iandNot
-  // end in the same container types, DESIGN.md §4); x1.or(x2) is Container.ior's
-  return rbg_pairwise(op == RBG_OR ? RBG_OR_INPLACE : op, a, a_len, b, b_len, out);
-}
-
-int rbg_ornot(const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int64_t range_end, int flags,
-              rbg_buffer* out) {
-  if (!out || flags < 0 || flags > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  const uint8_t* bufs[2] = {a, b};
-  const size_t lens[2] = {a_len, b_len};
-  int32_t ids[2];
-  CHK(ctx_load_separate(c, bufs, lens, 2, ids));
-  g.ids = {ids[0], ids[1]};
-  CHK(ctx_ornot(c, ids[0], 0, ids[1], 0, range_end, flags));
-  return ctx_fetch(c, out);
-}
-
-int rbg_ctx_ornot(rbg_ctx* ctx, int32_t a, size_t ia, int32_t b, size_t ib, int64_t range_end, int flags) {
-  if (!ctx || flags < 0 || flags > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_ornot(&ctx->c, a, ia, b, ib, range_end, flags);
-}
-
-int rbg_range_mut(int op, const uint8_t* a, size_t a_len, int64_t range_start, int64_t range_end, rbg_buffer* out) {
-  if (!out || op < 0 || op > (RBG_RMUT_ADD_INPLACE | RBG_RMUT_BUFFER))
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load_separate(c, &a, &a_len, 1, &id));
-  g.ids = {id};
-  CHK(ctx_range_mut(c, op & 3, id, 0, range_start, range_end, (op & RBG_RMUT_BUFFER) != 0));
-  return ctx_fetch(c, out);
-}
-
-int rbg_ctx_range_mut(rbg_ctx* ctx, int op, int32_t batch, size_t i, int64_t range_start, int64_t range_end) {
-  if (!ctx || op < 0 || op > (RBG_RMUT_ADD_INPLACE | RBG_RMUT_BUFFER))
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_range_mut(&ctx->c, op & 3, batch, i, range_start, range_end, (op & RBG_RMUT_BUFFER) != 0);
-}
-
-int rbg_add_offset(const uint8_t* a, size_t a_len, int64_t offset, rbg_buffer* out) {
-  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load_separate(c, &a, &a_len, 1, &id));
-  g.ids = {id};
-  CHK(ctx_add_offset(c, id, 0, offset));
-  return ctx_fetch(c, out);
-}
-
-/* ---- point queries (rankdir.hip) ---- */
-static bool point_op_ok(int op) { return op >= RBG_PQ_RANK && op <= RBG_PQ_PREV; }
-
-int rbg_ctx_point_query(rbg_ctx* ctx, int op, int32_t batch, size_t i, const uint32_t* q, size_t n, int64_t* out) {
-  if (!ctx || !point_op_ok(op)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (n == 0) return RBG_OK;
-  if (!q || !out) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_point_host(&ctx->c, op, batch, i, q, n, out);
-}
-
-int rbg_ctx_point_query_device(rbg_ctx* ctx, int op, int32_t batch, size_t i, const void* q_dev, size_t n,
-                               void* out_dev) {
-  if (!ctx || !point_op_ok(op)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (n == 0) return RBG_OK;
-  if (!q_dev || !out_dev) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_point(&ctx->c, op, batch, i, reinterpret_cast<const uint32_t*>(q_dev), n,
-                   reinterpret_cast<long long*>(out_dev));
-}
-
-int rbg_point_query(int op, const uint8_t* buf, size_t len, const uint32_t* q, size_t n, int64_t* out) {
-  if (!point_op_ok(op)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (n == 0) return RBG_OK;
-  if (!buf || !q || !out) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load_separate(c, &buf, &len, 1, &id));
-  g.ids = {id};
-  return ctx_point_host(c, op, id, 0, q, n, out);
-}
-
-int rbg_ctx_from_values(rbg_ctx* ctx, const uint32_t* values, size_t n, int run_optimize, int32_t* batch) {
-  if (!ctx || !batch || (n && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_from_values_host(&ctx->c, values, n, run_optimize != 0, batch);
-}
-
-int rbg_ctx_from_values_device(rbg_ctx* ctx, const void* values_dev, size_t n, int run_optimize, int32_t* batch) {
-  if (!ctx || !batch || (n && !values_dev)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_from_values(&ctx->c, reinterpret_cast<const uint32_t*>(values_dev), n, run_optimize != 0, batch);
-}
-
-int rbg_ctx_to_values(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t count, uint32_t* out,
-                      uint64_t* n_out) {
-  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_to_values_host(&ctx->c, batch, i, first, count, out, n_out);
-}
-
-int rbg_ctx_to_values_device(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t count, int out64,
-                             void* out_dev, uint64_t* n_out) {
-  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_to_values(&ctx->c, batch, i, first, count, out64 != 0, out_dev, n_out);
-}
-
-int rbg_build_values(const uint32_t* values, size_t n, int run_optimize, rbg_buffer* out) {
-  if (!out || (n && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_from_values_host(c, values, n, run_optimize != 0, &id));
-  g.ids = {id};
-  return ctx_batch_fetch(c, id, 0, out);
-}
-
-int rbg_expand_values(const uint8_t* buf, size_t len, rbg_buffer* out) {
-  if (!out || (!buf && len)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load_separate(c, &buf, &len, 1, &id));
-  g.ids = {id};
-  const uint64_t card = (uint64_t)c->batches[id]->long_card;
-  uint8_t* p = (uint8_t*)std::malloc(card * 4 + 4);
+// a malloc'd copy of n bytes as a result buffer (rbg_free releases it)
+static int emit_bytes(const uint8_t* src, size_t n, rbg_buffer* out) {
+  uint8_t* p = (uint8_t*)std::malloc(n ? n : 1);
   if (!p) return RBG_ERR_OUT_OF_MEMORY;
-  uint64_t got = 0;
-  const int st = ctx_to_values_host(c, id, 0, 0, card, reinterpret_cast<uint32_t*>(p), &got);
-  if (st != RBG_OK) {
-    std::free(p);
-    return st;
-  }
+  if (n) std::memcpy(p, src, n);
   out->data = p;
-  out->len = (size_t)got * 4;
+  out->len = n;
   return RBG_OK;
 }
-
-// x.limit(maxcardinality) (RB/RoaringBitmap.java:2457-2476).  The cut is planned from the serialized
-// header's cardinalities on the host (the reference's own loop walks getCardinality per container):
-// keys before it cloned, its container cut to the leftover by k_rmut<RMUT_LIMIT>, the rest dropped.
-int rbg_limit(const uint8_t* a, size_t a_len, int32_t maxcard, rbg_buffer* out) {
-  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
-  HostBitmap hb;
-  std::string err;
-  const int pst = parse(a, a_len, &hb, &err);
-  if (pst) {
-    set_err(err);
-    return pst;
-  }
-  int cut_key = 65536, leftover = 0;
-  int64_t cur = 0;
-  for (size_t i = 0; cur < maxcard && i < hb.ctrs.size(); i++) {
-    const int64_t cc = hb.ctrs[i].card;
-    if (cc + cur <= maxcard) {
-      cur += cc;
-    } else {
-      cut_key = hb.ctrs[i].key;
-      leftover = (int)(maxcard - cur);
-      break;
-    }
-  }
-  if (leftover == 0) {  // the containers that fit whole: those before the first that does not
-    cut_key = 0;
-    for (size_t i = 0, acc = 0; i < hb.ctrs.size() && (int64_t)(acc + hb.ctrs[i].card) <= (int64_t)maxcard; i++) {
-      acc += hb.ctrs[i].card;
-      cut_key = hb.ctrs[i].key + 1;
-    }
-  }
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load_separate(c, &a, &a_len, 1, &id));
-  g.ids = {id};
-  Batch* A;
-  CHK(get_batch(c, id, &A));
-  const uint16_t* ka;
-  const CDesc* da;
-  int na;
-  CHK(operand(A, 0, &ka, &da, &na));
-  const RmutArgs ra{RMUT_LIMIT, cut_key, leftover, 0, 0};
-  const size_t ub = std::max<size_t>(1, (size_t)na);
-  hipStream_t s = c->stream;
-  if (!c->big_ctl.p) CHK(c->big_ctl.ensure(16));
-  if (!c->big.p) CHK(c->big.ensure(16ull << 20));
-  for (int attempt = 0;; attempt++) {
-    OutCtx oc;
-    CHK(prepare_output(c, ub, A->payload_bytes + (size_t)8194 * ub + c->big.cap, &oc, false));
-    c->pending_src = {id};
-    c->mark(0);
-    HIPCHK(hipMemsetAsync(c->big_ctl.p, 0, 16, s));
-    c->mark(1);
-    launch_rmut(s, A->key_off.as<uint32_t>(), da, A->payload.as<uint8_t>(), ra, false, c->wg_epoch.as<uint64_t>(),
-                next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb, c->ztile,
-                BigRuns{c->big.as<uint8_t>(), c->big_ctl.as<unsigned long long>(), c->big.cap}, grid_for(ub, 65536));
-    c->mark(2);
-    defer_place(c);
-    c->mark(3);
-    HIPCHK(hipGetLastError());
-    unsigned long long used[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(used, c->big_ctl.p, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (!used[1]) break;
-    if (attempt) {
-      set_err("limit: the run-container arena overflowed twice");
-      return RBG_ERR_DEVICE;
-    }
-    CHK(c->big.ensure(used[0] + (used[0] >> 3) + 4096));
-  }
-  return ctx_fetch(c, out);
-}
-
-// RoaringBitmap.bitmapOfRange(min, max) (RB/RoaringBitmap.java:588-615): k_rmut<RMUT_RANGE> over an empty
-// bitmap (every container written as a run container)
-int rbg_bitmap_of_range(int64_t min, int64_t max, rbg_buffer* out) {
-  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
-  static const uint8_t kEmpty[8] = {0x3A, 0x30, 0, 0, 0, 0, 0, 0};
-  const uint8_t* a = kEmpty;
-  size_t a_len = 8;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load_separate(c, &a, &a_len, 1, &id));
-  g.ids = {id};
-  CHK(ctx_range_mut(c, RMUT_RANGE, id, 0, min, max, false));
-  return ctx_fetch(c, out);
-}
-
-int rbg_remove_run_compression(const uint8_t* a, size_t a_len, rbg_buffer* out) {
-  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load_separate(c, &a, &a_len, 1, &id));
-  g.ids = {id};
-  CHK(ctx_remove_run_compression(c, id, 0));
-  return ctx_fetch(c, out);
-}
-
-int rbg_ctx_add_offset(rbg_ctx* ctx, int32_t batch, size_t i, int64_t offset) {
-  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_add_offset(&ctx->c, batch, i, offset);
-}
-
-int rbg_pairwise_card(int op, const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int32_t* out) {
-  if (!out || op < 0 || op > RBG_CONTAINS) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t ia, ib;
-  CHK(ctx_load(c, &a, &a_len, 1, &ia));
-  g.ids.push_back(ia);
-  CHK(ctx_load(c, &b, &b_len, 1, &ib));
-  g.ids.push_back(ib);
-  CHK(ctx_pairwise(c, OP_AND, ia, 0, ib, 0, true));
-  ResultInfo ri;
-  CHK(ctx_info(c, &ri));
-  const uint32_t ac = ri.card32;
-  const uint32_t ca = (uint32_t)(uint64_t)c->batches[ia]->long_card;  // RoaringBitmap.getCardinality (int)
-  const uint32_t cb = (uint32_t)(uint64_t)c->batches[ib]->long_card;
-  switch (op) {
-    case RBG_CARD_AND: *out = (int32_t)ac; break;
-    case RBG_CARD_OR: *out = (int32_t)(ca + cb - ac); break;         // RB/RoaringBitmap.java:916-920
-    case RBG_CARD_XOR: *out = (int32_t)(ca + cb - 2u * ac); break;   // :931-933
-    case RBG_CARD_ANDNOT: *out = (int32_t)(ca - ac); break;          // :944-985 (both branches, mod 2^32)
-    case RBG_CONTAINS:  // b is a subset of a (:2781-2802): every value of b in a AND b, counted in 64 bits
-      *out = ri.long_card == c->batches[ib]->long_card ? 1 : 0;
-      break;
-    default: *out = ri.any ? 1 : 0; break;                           // intersects :698-720
-  }
-  return RBG_OK;
-}
-
-int rbg_wide(int op, const uint8_t* const* bufs, const size_t* lens, const int32_t* ids, size_t n, rbg_buffer* out) {
-  if (!out || op < 0 || op > RBG_WIDE_BUFFER_AND_ITER) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load(c, bufs, lens, n, &id, wide_reads_packed(op, n)));
-  g.ids.push_back(id);
-  int hc;
-  bool hv;
-  CHK(ctx_wide(c, op, id, 0, 65536, ids, false, &hc, &hv));
-  return ctx_fetch(c, out);
-}
-
-static int ctx_select_range(Ctx* c, int32_t id, int64_t start, int64_t end, int32_t* out_id, bool buf = false);
-// rangeSanityCheck (RB/RoaringBitmap.java:204-213)
-static int check_range(int64_t start, int64_t end) {
-  if (start < 0 || start > 0xFFFFFFFFll || end < 0 || end > 0x100000000ll) {
-    set_err("rangeStart=" + std::to_string(start) + " should be in [0, 0xffffffff], rangeEnd=" + std::to_string(end) +
-            " in [0, 0xffffffff + 1]");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  return RBG_OK;
-}
-
-int rbg_range_op(int op, const uint8_t* const* bufs, const size_t* lens, size_t n, int64_t range_start,
-                 int64_t range_end, rbg_buffer* out) {
-  if (!out || op < RBG_RANGE_AND || op > RBG_RANGE_BUFFER_ANDNOT ||
-      ((op == RBG_RANGE_ANDNOT || op == RBG_RANGE_BUFFER_ANDNOT) && n != 2))
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  const bool buf = op >= RBG_RANGE_BUFFER_AND;
-  const int base = buf ? op - RBG_RANGE_BUFFER_AND : op;
-  if (buf && base == RBG_RANGE_AND && n == 0) {
-    // BufferFastAggregation.and(long[], Iterator) with no input: an empty bitmap (:81-88)
-    CHK(check_range(range_start, range_end));
-    static const uint8_t kEmpty[8] = {0x3A, 0x30, 0, 0, 0, 0, 0, 0};
-    uint8_t* p = (uint8_t*)std::malloc(8);
-    if (!p) return RBG_ERR_OUT_OF_MEMORY;
-    std::memcpy(p, kEmpty, 8);
-    out->data = p;
-    out->len = 8;
-    return RBG_OK;
-  }
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  CHK(check_range(range_start, range_end));  // rangeSanityCheck before the selections (RB/RoaringBitmap.java:204-213)
-  if (base == RBG_RANGE_ANDNOT) {  // andNot(x1, x2, start, end): both operands selected, then andNot
-    int32_t ids[2], sel[2];
-    CHK(ctx_load_separate(c, bufs, lens, 2, ids));
-    g.ids = {ids[0], ids[1]};
-    for (int i = 0; i < 2; i++) {
-      CHK(ctx_select_range(c, ids[i], range_start, range_end, &sel[i], buf));
-      g.ids.push_back(sel[i]);
-    }
-    // the buffer package's andNot keeps R \ R's merged run container (ImmutableRoaringBitmap.andNot)
-    CHK(ctx_pairwise(c, buf ? RBG_ANDNOT_BUFFER : OP_ANDNOT, sel[0], 0, sel[1], 0, false));
-    return ctx_fetch(c, out);
-  }
-  int32_t id, sel;
-  CHK(ctx_load(c, bufs, lens, n, &id));
-  g.ids.push_back(id);
-  CHK(ctx_select_range(c, id, range_start, range_end, &sel, buf));
-  g.ids.push_back(sel);
-  // heap: and -> FastAggregation.and(Iterator) = naive_and(Iterator); or / xor -> naive_or / naive_xor.
-  // buffer: and -> BufferFastAggregation.and(Iterator) = workShyAnd for any count (no input: empty);
-  // or / xor -> naive_or / naive_xor, typed like the heap's
-  const int wop = base == RBG_RANGE_AND ? (buf ? RBG_WIDE_WORKSHY_AND : RBG_WIDE_AND_ITER)
-                  : base == RBG_RANGE_OR ? RBG_WIDE_OR
-                                         : RBG_WIDE_XOR;
-  int hc;
-  bool hv;
-  CHK(ctx_wide(c, wop, sel, 0, 65536, nullptr, false, &hc, &hv));
-  return ctx_fetch(c, out);
-}
-
-int rbg_select_range(const uint8_t* a, size_t a_len, int64_t range_start, int64_t range_end, int buffer,
-                     rbg_buffer* out) {
-  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id, sel;
-  CHK(ctx_load_separate(c, &a, &a_len, 1, &id));
-  g.ids = {id};
-  CHK(ctx_select_range(c, id, range_start, range_end, &sel, buffer != 0));
-  g.ids.push_back(sel);
-  return ctx_batch_fetch(c, sel, 0, out);
-}
-
-int rbg_ctx_select_range(rbg_ctx* ctx, int32_t batch, int64_t range_start, int64_t range_end, int32_t* out_batch) {
-  if (!ctx || !out_batch) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_select_range(&ctx->c, batch, range_start, range_end, out_batch);
-}
-
-int rbg_wide_card(int op, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* out) {
-  if (!out || op < 0 || op > 1) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load(c, bufs, lens, n, &id));
-  g.ids.push_back(id);
-  int hc = 0;
-  bool hv = false;
-  CHK(ctx_wide(c, op, id, 0, 65536, nullptr, true, &hc, &hv));
-  if (hv) {
-    *out = hc;
-    return RBG_OK;
-  }
-  ResultInfo ri;
-  CHK(ctx_info(c, &ri));
-  *out = (int32_t)ri.card32;
-  return RBG_OK;
-}
-
-static int ctx_batch_card(Ctx* c, int32_t id) {
-  Batch* B;
-  CHK(get_batch(c, id, &B));
-  if (B->packed) {
-    set_err("batched andCardinality needs slot-aligned payloads");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  if (B->n_bm % 2 != 0) {
-    set_err("batched andCardinality needs an even number of bitmaps");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  const size_t np = B->n_bm / 2;
-  CHK(c->cards.ensure(4 * std::max<size_t>(np, 1)));
-  if (B->key_major && B->n_bm > 1) {
-    // pairs need bitmap-major ranges: permuted view of a key-major batch is not supported
-    set_err("batched andCardinality needs a bitmap-major batch");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  c->mark(0);
-  c->mark(1);
-  if (!B->pair_cap_known) {
-    B->pair_items_cap = batch_pair_items_cap(B->h_bm_nctr.data(), np);
-    B->pair_cap_known = true;
-  }
-  CHK(c->pc_cnt.ensure(8 * ((np + 255) / 256) + std::max<size_t>(np, 1) + 16));  // workgroup totals + a count byte per pair
-  CHK(c->pc_part.ensure(8 * (scan_parts(std::max<size_t>(np, 1)) + 1)));
-  CHK(c->pc_items.ensure(sizeof(PairItem) * std::max<uint64_t>(B->pair_items_cap, 1)));
-  CHK(c->pc_large.ensure(4 * std::max<size_t>(np, 1)));
-  CHK(c->scalar.ensure(64));
-  launch_batch_and_card(c->stream, np, B->bm_off.as<uint32_t>(), B->keys.as<uint16_t>(), B->desc.as<CDesc>(),
-                        B->payload.as<uint8_t>(), c->cards.as<int32_t>(), c->pc_cnt.as<uint64_t>(),
-                        c->pc_part.as<uint64_t>(), c->scalar.as<uint64_t>() + 7, c->pc_items.as<PairItem>(),
-                        c->pc_large.as<uint32_t>());
-  c->mark(2);
-  c->mark(3);
-  HIPCHK(hipGetLastError());
-  c->n_cards = np;
-  c->last = 3;
-  return RBG_OK;
-}
-
-// bitmap-major upload used by batched andCardinality (pairs kept adjacent)
-static int ctx_load_bitmap_major(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* out_id) {
-  return ctx_load_impl(c, bufs, lens, n, false, out_id);
-}
-
-int rbg_batch_and_card(size_t n_pairs, const uint8_t* const* a_bufs, const size_t* a_lens,
-                       const uint8_t* const* b_bufs, const size_t* b_lens, int32_t* out) {
-  if (n_pairs && (!a_bufs || !a_lens || !b_bufs || !b_lens || !out)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (n_pairs == 0) return RBG_OK;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  std::vector<const uint8_t*> bufs(2 * n_pairs);
-  std::vector<size_t> lens(2 * n_pairs);
-  for (size_t i = 0; i < n_pairs; i++) {
-    bufs[2 * i] = a_bufs[i];
-    lens[2 * i] = a_lens[i];
-    bufs[2 * i + 1] = b_bufs[i];
-    lens[2 * i + 1] = b_lens[i];
-  }
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(ctx_load_bitmap_major(c, bufs.data(), lens.data(), 2 * n_pairs, &id));
-  g.ids.push_back(id);
-  CHK(ctx_batch_card(c, id));
-  HIPCHK(hipMemcpyAsync(out, c->cards.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return RBG_OK;
-}
-
-// ---- host-side format utilities ----
-static int emit_host(const std::vector<uint8_t>& v, rbg_buffer* out) {
-  uint8_t* p = (uint8_t*)std::malloc(v.size() ? v.size() : 1);
-  if (!p) return RBG_ERR_OUT_OF_MEMORY;
-  if (!v.empty()) std::memcpy(p, v.data(), v.size());
-  out->data = p;
-  out->len = v.size();
-  return RBG_OK;
-}
-
-int rbg_from_values(const uint32_t* values, size_t n, int run_optimize, rbg_buffer* out) {
-  if (!out || (n && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return emit_host(build_from_values(values, n, run_optimize != 0), out);
-}
-
-// RoaringBitmap.runOptimize() (RB/RoaringBitmap.java:2764-2774): the device pass
-// (runopt.hip) over a one-bitmap batch, like rbg_run_optimize_many.
-int rbg_run_optimize(const uint8_t* buf, size_t len, rbg_buffer* out) {
-  if (!out || (!buf && len)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  uint8_t answer = 0;
-  return rbg_run_optimize_many(&buf, &len, 1, out, &answer);
-}
-
-int rbg_to_values(const uint8_t* buf, size_t len, rbg_buffer* out) {
-  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
-  std::vector<uint32_t> v;
-  std::string err;
-  int st = values_of_serialized(buf, len, &v, &err);
-  if (st) {
-    set_err(err);
-    return st;
-  }
-  uint8_t* p = (uint8_t*)std::malloc(v.size() * 4 + 4);
-  if (!p) return RBG_ERR_OUT_OF_MEMORY;
-  std::memcpy(p, v.data(), v.size() * 4);
-  out->data = p;
-  out->len = v.size() * 4;
-  return RBG_OK;
-}
-
-int rbg_inspect(const uint8_t* buf, size_t len, size_t* consumed, int64_t* cardinality, int64_t* stats3) {
-  HostBitmap hb;
-  std::string err;
-  int st = parse(buf, len, &hb, &err);
-  if (st) {
-    set_err(err);
-    return st;
-  }
-  if (consumed) *consumed = hb.consumed;
-  if (cardinality) *cardinality = hb.card;
-  if (stats3) {
-    stats3[0] = stats3[1] = stats3[2] = 0;
-    for (const HostCtr& c : hb.ctrs) stats3[c.kind]++;
-  }
-  return RBG_OK;
-}
-
-// ---- session API ----
-int rbg_ctx_create(int device, rbg_ctx** out) {
-  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
-  std::unique_ptr<rbg_ctx> c(new rbg_ctx());
-  CHK(ctx_init(&c->c, device));
-  *out = c.release();
-  return RBG_OK;
-}
-void rbg_ctx_destroy(rbg_ctx* ctx) {
-  if (!ctx) return;
-  (void)hipSetDevice(ctx->c.device);
-  delete ctx;
-}
-void* rbg_ctx_stream(rbg_ctx* ctx) { return ctx ? (void*)ctx->c.stream : nullptr; }
-static int ctx_profile(rbg_ctx* ctx, int max_ops, bool compute_only) {
-  CHK(enter(&ctx->c));
-  HIPCHK(hipStreamSynchronize(ctx->c.stream));
-  ctx->c.prof_free();
-  ctx->c.prof_compute_only = compute_only;
-  if (max_ops <= 0) return RBG_OK;
-  ctx->c.prof_ev.resize(4 * (size_t)max_ops);
-  for (hipEvent_t& e : ctx->c.prof_ev) HIPCHK(hipEventCreate(&e));
-  ctx->c.prof_cap = (size_t)max_ops;
-  ctx->c.prof_n = 0;
-  CHK(ctx->c.rd_ctr.ensure(8));
-  HIPCHK(hipMemsetAsync(ctx->c.rd_ctr.p, 0, 8, ctx->c.stream));
-  return RBG_OK;
-}
-int rbg_ctx_profile(rbg_ctx* ctx, int max_ops) { return ctx_profile(ctx, max_ops, false); }
-int rbg_ctx_profile_compute(rbg_ctx* ctx, int max_ops) { return ctx_profile(ctx, max_ops, true); }
-int rbg_ctx_profile_bytes(rbg_ctx* ctx, int64_t* bytes) {
-  if (!ctx || !bytes) {
-    set_err("profile_bytes: null argument");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  Ctx& c = ctx->c;
-  CHK(enter(&c));
-  HIPCHK(hipStreamSynchronize(c.stream));
-  unsigned long long v = 0;
-  if (c.rd_ctr.p) HIPCHK(hipMemcpy(&v, c.rd_ctr.p, 8, hipMemcpyDeviceToHost));
-  *bytes = (int64_t)v;
-  return RBG_OK;
-}
-int rbg_ctx_profile_read(rbg_ctx* ctx, double* ms3, int* n_ops) {
-  Ctx& c = ctx->c;
-  CHK(enter(&c));
-  HIPCHK(hipStreamSynchronize(c.stream));
-  ms3[0] = ms3[1] = ms3[2] = 0.0;
-  for (size_t i = 0; i < c.prof_n; i++) {
-    for (int ph = 0; ph < 3; ph++) {
-      if (c.prof_compute_only && ph != 1) continue;  // only the compute launch was bracketed
-      float ms = 0.f;
-      HIPCHK(hipEventElapsedTime(&ms, c.prof_ev[4 * i + ph], c.prof_ev[4 * i + ph + 1]));
-      ms3[ph] += ms;
-    }
-  }
-  *n_ops = (int)c.prof_n;
-  c.prof_n = 0;
-  return RBG_OK;
-}
-int rbg_ctx_sync(rbg_ctx* ctx) {
-  CHK(enter(&ctx->c));
-  HIPCHK(hipStreamSynchronize(ctx->c.stream));
-  return RBG_OK;
-}
-int rbg_ctx_load_separate(rbg_ctx* ctx, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* ids) {
-  if (!ctx || !ids) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_load_separate(&ctx->c, bufs, lens, n, ids);
-}
-int rbg_ctx_load(rbg_ctx* ctx, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* batch) {
-  CHK(enter(&ctx->c));
-  return ctx_load(&ctx->c, bufs, lens, n, batch);
-}
-int rbg_ctx_load_packed(rbg_ctx* ctx, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* batch) {
-  if (!ctx || !batch) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_load(&ctx->c, bufs, lens, n, batch, true);
-}
-int rbg_ctx_release(rbg_ctx* ctx, int32_t batch) {
-  Ctx& c = ctx->c;
-  Batch* b;
-  CHK(find_batch(&c, batch, &b));  // no statistics read-back for a batch that goes
-  CHK(enter(&c));
-  // A materialised result references pass-through containers inside its operand
-  // batches (ORec::src) until it is serialized: serialize it before an operand goes.
-  if (c.last == 1 && !c.serialized &&
-      std::find(c.pending_src.begin(), c.pending_src.end(), batch) != c.pending_src.end())
-    CHK(ctx_serialize(&c));
-  // No host sync: the buffers go to this context's pool, and whatever reuses them is enqueued on
-  // the same stream after every launch that reads them (a pipelined op's second stream is joined
-  // back into it at the op's end); a pooled buffer that is freed goes through hipFree, which waits
-  // for the device.
-  for (DevBuf* d : {&b->keys, &b->desc, &b->bm, &b->key_off, &b->bm_off, &b->payload, &b->ro_stats,
-                    &b->bsi_tasks, &b->bsi_nt, &b->bsi_table, &b->rd_cum, &b->rd_off, &b->rd_aux})
-    pool_put(&c, *d);
-  c.batches[batch].reset();
-  return RBG_OK;
-}
-int rbg_ctx_batch_stats(rbg_ctx* ctx, int32_t batch, int64_t* st) {
-  Batch* b;
-  CHK(get_batch(&ctx->c, batch, &b));
-  st[0] = (int64_t)b->n_bm;
-  st[1] = (int64_t)b->n_ctr;
-  st[2] = b->n_kind[0];
-  st[3] = b->n_kind[1];
-  st[4] = b->n_kind[2];
-  st[5] = 0;  // payload bytes (serialized form)
-  st[6] = b->long_card;
-  st[7] = b->ser_bytes;
-  if (b->n_ctr) {
-    CHK(enter(&ctx->c));
-    hipStream_t s = ctx->c.stream;
-    HIPCHK(hipMemsetAsync(ctx->c.scalar.p, 0, 8, s));
-    launch_batch_bytes(s, b->desc.as<CDesc>(), b->n_ctr, b->payload.as<uint8_t>(),
-                       ctx->c.scalar.as<unsigned long long>());
-    unsigned long long pay = 0;
-    HIPCHK(hipMemcpyAsync(&pay, ctx->c.scalar.p, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    st[5] = (int64_t)pay;
-  }
-  return RBG_OK;
-}
-static int ctx_batch_fetch(Ctx* c, int32_t batch, size_t i, rbg_buffer* out);
-static int ctx_batch_fetch_range(Ctx* c, int32_t batch, size_t i0, size_t i1, rbg_buffer* outs);
-int rbg_ctx_batch_fetch(rbg_ctx* ctx, int32_t batch, size_t i, rbg_buffer* out) {
-  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_batch_fetch(&ctx->c, batch, i, out);
-}
-int rbg_ctx_batch_fetch_range(rbg_ctx* ctx, int32_t batch, size_t first, size_t count, rbg_buffer* outs) {
-  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_batch_fetch_range(&ctx->c, batch, first, first + count, outs);
-}
-}  // extern "C"
-
-namespace rbg {
-// Host index of a batch's containers, built once per batch: the container table and,
-// per input bitmap, its container positions (in key order).
-static int batch_host_index(Ctx* c, Batch* b) {
-  if (b->h_index) return RBG_OK;
-  HIPCHK(hipStreamSynchronize(c->stream));
-  b->h_desc.resize(b->n_ctr);
-  if (b->n_ctr) HIPCHK(hipMemcpy(b->h_desc.data(), b->desc.p, sizeof(CDesc) * b->n_ctr, hipMemcpyDeviceToHost));
-  b->h_pos_off.assign(b->n_bm + 1, 0);
-  b->h_pos.resize(b->n_ctr);
-  if ((b->n_bm == 1 || !b->key_major) && b->h_bm_off.size() == b->n_bm + 1) {
-    for (size_t i = 0; i <= b->n_bm; i++) b->h_pos_off[i] = b->h_bm_off[i];
-    for (size_t p = 0; p < b->n_ctr; p++) b->h_pos[p] = (uint32_t)p;
-  } else {  // key-major: counting sort of the positions by input bitmap (stable, so key order)
-    std::vector<uint32_t> bm(b->n_ctr);
-    if (b->n_ctr) HIPCHK(hipMemcpy(bm.data(), b->bm.p, 4 * b->n_ctr, hipMemcpyDeviceToHost));
-    for (uint32_t x : bm) b->h_pos_off[x + 1]++;
-    for (size_t i = 0; i < b->n_bm; i++) b->h_pos_off[i + 1] += b->h_pos_off[i];
-    std::vector<uint32_t> fill(b->h_pos_off.begin(), b->h_pos_off.end() - 1);
-    for (size_t p = 0; p < b->n_ctr; p++) b->h_pos[fill[bm[p]]++] = (uint32_t)p;
-  }
-  b->h_index = true;
-  return RBG_OK;
-}
-
-}  // namespace rbg
+static int emit_host(const std::vector<uint8_t>& v, rbg_buffer* out) { return emit_bytes(v.data(), v.size(), out); }
+// the serialized empty bitmap (no run cookie, 0 containers)
+static const uint8_t kEmpty[8] = {0x3A, 0x30, 0, 0, 0, 0, 0, 0};
+static int emit_empty(rbg_buffer* out) { return emit_bytes(kEmpty, sizeof(kEmpty), out); }
 
 // Download bitmaps [i0, i1) of a batch as portable serialized bytes: their slots are
 // gathered on the device into one buffer (one D2H copy), the headers built here.
@@ -3369,236 +2527,49 @@ static int ctx_batch_fetch(Ctx* c, int32_t batch, size_t i, rbg_buffer* out) {
   return ctx_batch_fetch_range(c, batch, i, i + 1, out);
 }
 
-extern "C" {
-int rbg_ctx_pairwise(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib) {
-  CHK(enter(&ctx->c));
-  return ctx_pairwise(&ctx->c, op, a, ia, b, ib, false);
-}
-int rbg_ctx_pairwise_serialized(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib) {
-  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  if (op < 0 || op > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(ctx_pairwise(&ctx->c, op, a, ia, b, ib, false, 0, kMaxKeys, pipe_ranges()));
-  return ctx_serialize(&ctx->c);  // no-op after the pipelined form
-}
-int rbg_ctx_pairwise_range(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib, int key_lo, int key_hi) {
-  if (!ctx || key_lo > key_hi) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_pairwise(&ctx->c, op, a, ia, b, ib, false, key_lo, key_hi);
-}
-int rbg_ctx_pairwise_card(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib) {
-  CHK(enter(&ctx->c));
-  if (op != RBG_CARD_AND) {
-    set_err("the session API computes andCardinality; derive the others from the input cardinalities");
+static bool point_op_ok(int op) { return op >= RBG_PQ_RANK && op <= RBG_PQ_PREV; }
+
+static int ctx_batch_card(Ctx* c, int32_t id) {
+  Batch* B;
+  CHK(get_batch(c, id, &B));
+  if (B->packed) {
+    set_err("batched andCardinality needs slot-aligned payloads");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  return ctx_pairwise(&ctx->c, OP_AND, a, ia, b, ib, true);
-}
-int rbg_ctx_wide(rbg_ctx* ctx, int op, int32_t batch, int key_lo, int key_hi, const int32_t* ids) {
-  CHK(enter(&ctx->c));
-  int hc;
-  bool hv;
-  return ctx_wide(&ctx->c, op, batch, key_lo, key_hi, ids, false, &hc, &hv);
-}
-int rbg_ctx_wide_start(rbg_ctx* ctx, int op, int32_t batch, int key_lo, int key_hi, const int32_t* ids,
-                       int32_t start_bm) {
-  CHK(enter(&ctx->c));
-  int hc;
-  bool hv;
-  return ctx_wide(&ctx->c, op, batch, key_lo, key_hi, ids, false, &hc, &hv, start_bm);
-}
-int rbg_ctx_batch_counts(rbg_ctx* ctx, int32_t batch, uint32_t* out, size_t n) {
-  Batch* b;
-  CHK(get_batch(&ctx->c, batch, &b));
-  if (!out || n != b->n_bm) return RBG_ERR_ILLEGAL_ARGUMENT;
-  for (size_t i = 0; i < n; i++) out[i] = b->h_bm_nctr[i];
-  return RBG_OK;
-}
-int rbg_synth_key_bytes(int kind, uint64_t seed, size_t n, uint64_t* out) {
-  if (!out || (kind != 1 && kind != 2)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  for (int k = 0; k < kMaxKeys; k++) out[k] = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (kind == 1) {
-      for (int k = 0; k < kMaxKeys; k++) out[k] += 4 + 2 * (uint64_t)c3u_card(seed, (uint32_t)i, (uint32_t)k);
-    } else {
-      const uint32_t b0 = c3c_base(seed, (uint32_t)i);
-      for (uint32_t k = b0; k < b0 + 16; k++) out[k] += 4 + 8192;
-    }
+  if (B->n_bm % 2 != 0) {
+    set_err("batched andCardinality needs an even number of bitmaps");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  return RBG_OK;
-}
-int rbg_ctx_bsi(rbg_ctx* ctx, int32_t batch, int op, int nbits, int has_found, int32_t start, int32_t end,
-                int32_t min_value, int32_t max_value, int want_sum) {
-  CHK(enter(&ctx->c));
-  return ctx_bsi(&ctx->c, batch, op, nbits, has_found, start, end, min_value, max_value, want_sum);
-}
-int rbg_ctx_bsi_sums(rbg_ctx* ctx, int64_t* out2) {
-  if (!out2) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_bsi_sums(&ctx->c, out2);
-}
-int rbg_ctx_bsi_sums_target(rbg_ctx* ctx, void* dst2) {
-  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
-  ctx->c.bsi_sums_dst = dst2;
-  return RBG_OK;
-}
-int rbg_ctx_bsi_sums_device(rbg_ctx* ctx, void* dst2) {
-  if (!ctx || !dst2 || !ctx->c.bsi_sums.p) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  launch_bsi_sums_out(ctx->c.stream, ctx->c.bsi_sums.as<unsigned long long>(), dst2);
+  const size_t np = B->n_bm / 2;
+  CHK(c->cards.ensure(4 * std::max<size_t>(np, 1)));
+  if (B->key_major && B->n_bm > 1) {
+    // pairs need bitmap-major ranges: permuted view of a key-major batch is not supported
+    set_err("batched andCardinality needs a bitmap-major batch");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  c->mark(0);
+  c->mark(1);
+  if (!B->pair_cap_known) {
+    B->pair_items_cap = batch_pair_items_cap(B->h_bm_nctr.data(), np);
+    B->pair_cap_known = true;
+  }
+  CHK(c->pc_cnt.ensure(8 * ((np + 255) / 256) + std::max<size_t>(np, 1) + 16));  // workgroup totals + a count byte per pair
+  CHK(c->pc_part.ensure(8 * (scan_parts(std::max<size_t>(np, 1)) + 1)));
+  CHK(c->pc_items.ensure(sizeof(PairItem) * std::max<uint64_t>(B->pair_items_cap, 1)));
+  CHK(c->pc_large.ensure(4 * std::max<size_t>(np, 1)));
+  CHK(c->scalar.ensure(64));
+  launch_batch_and_card(c->stream, np, B->bm_off.as<uint32_t>(), B->keys.as<uint16_t>(), B->desc.as<CDesc>(),
+                        B->payload.as<uint8_t>(), c->cards.as<int32_t>(), c->pc_cnt.as<uint64_t>(),
+                        c->pc_part.as<uint64_t>(), c->scalar.as<uint64_t>() + 7, c->pc_items.as<PairItem>(),
+                        c->pc_large.as<uint32_t>());
+  c->mark(2);
+  c->mark(3);
   HIPCHK(hipGetLastError());
+  c->n_cards = np;
+  c->last = 3;
   return RBG_OK;
 }
-static int bsi_load(Ctx* c, const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* lens,
-                    size_t nbits, const uint8_t* found, size_t found_len, int32_t* id) {
-  if (!ebm || (nbits && (!slices || !lens)) || nbits + 2 > (size_t)kBsiMaxInputs) return RBG_ERR_ILLEGAL_ARGUMENT;
-  std::vector<const uint8_t*> bufs{ebm};
-  std::vector<size_t> ls{ebm_len};
-  for (size_t i = 0; i < nbits; i++) {
-    bufs.push_back(slices[i]);
-    ls.push_back(lens[i]);
-  }
-  if (found) {
-    bufs.push_back(found);
-    ls.push_back(found_len);
-  }
-  return ctx_load(c, bufs.data(), ls.data(), bufs.size(), id);
-}
-int rbg_bsi_compare(int op, int32_t start, int32_t end, const uint8_t* ebm, size_t ebm_len,
-                    const uint8_t* const* slices, const size_t* slice_lens, size_t nbits, int32_t min_value,
-                    int32_t max_value, const uint8_t* found, size_t found_len, rbg_buffer* out) {
-  if (!out || op < 0 || op > BSI_RANGE) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(bsi_load(c, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
-  g.ids.push_back(id);
-  CHK(ctx_bsi(c, id, op, (int)nbits, found ? 1 : 0, start, end, min_value, max_value, 0));
-  return ctx_fetch(c, out);
-}
-int rbg_bsi_compare_buffer(int op, int32_t start, int32_t end, const uint8_t* ebm, size_t ebm_len,
-                           const uint8_t* const* slices, const size_t* slice_lens, size_t nbits, int32_t min_value,
-                           int32_t max_value, const uint8_t* found, size_t found_len, rbg_buffer* out) {
-  if (!out || op < 0 || op > RBG_BSI_RANGE_NEQ_DIRECT) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(bsi_load(c, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
-  g.ids.push_back(id);
-  CHK(ctx_bsi_buffer(c, id, op, (int)nbits, found ? 1 : 0, start, end, min_value, max_value));
-  return ctx_fetch(c, out);
-}
-int rbg_ctx_bsi_buffer(rbg_ctx* ctx, int32_t batch, int op, int nbits, int has_found, int32_t start, int32_t end,
-                       int32_t min_value, int32_t max_value) {
-  CHK(enter(&ctx->c));
-  return ctx_bsi_buffer(&ctx->c, batch, op, nbits, has_found, start, end, min_value, max_value);
-}
-int rbg_bsi_sum(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
-                size_t nbits, const uint8_t* found, size_t found_len, int64_t* out2) {
-  if (!out2) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (!found) {  // BSI/:582: null foundSet -> (0, 0)
-    out2[0] = out2[1] = 0;
-    return RBG_OK;
-  }
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
-  int32_t id;
-  CHK(bsi_load(c, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
-  g.ids.push_back(id);
-  CHK(ctx_bsi(c, id, BSI_SUM_ONLY, (int)nbits, 1, 0, 0, 0, 0, 1));
-  return ctx_bsi_sums(c, out2);
-}
-int rbg_debug_stamps(uint64_t* out20, int reset) {
-  if (!out20) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (getenv("RBG_DEBUG_BSI")) debug_bsi_stamps(out20, reset != 0);
-  else debug_stamps(out20, reset != 0);
-  return RBG_OK;
-}
-int rbg_ctx_pair_bytes(rbg_ctx* ctx, int32_t batch, int64_t* out2) {
-  Batch* b;
-  CHK(get_batch(&ctx->c, batch, &b));
-  if (!out2 || b->key_major || b->n_bm % 2) {
-    set_err("needs a bitmap-major batch of pairs");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  CHK(enter(&ctx->c));
-  HIPCHK(hipStreamSynchronize(ctx->c.stream));
-  std::vector<CDesc> d(b->n_ctr);
-  if (b->n_ctr) HIPCHK(hipMemcpy(d.data(), b->desc.p, sizeof(CDesc) * b->n_ctr, hipMemcpyDeviceToHost));
-  auto pay = [](const CDesc& x) -> int64_t { return x.kind == KA ? 2 * (int64_t)x.card : x.kind == KB ? 8192 : 0; };
-  int64_t matched = 0, all = 0;
-  for (size_t p = 0; p < b->n_bm / 2; p++) {
-    uint32_t i = b->h_bm_off[2 * p], ie = b->h_bm_off[2 * p + 1], j = ie, je = b->h_bm_off[2 * p + 2];
-    all += 4 * (int64_t)(je - i);
-    while (i < ie && j < je) {
-      if (d[i].key == d[j].key) {
-        matched += pay(d[i++]) + pay(d[j++]);
-      } else if (d[i].key < d[j].key) {
-        i++;
-      } else {
-        j++;
-      }
-    }
-  }
-  out2[0] = matched + all;  // SURVEY §8(d): matched payload + descriptors
-  int64_t tot = 0;
-  for (const CDesc& x : d) tot += pay(x) + 4;
-  out2[1] = tot;  // every payload + descriptors
-  return RBG_OK;
-}
-int rbg_ctx_wide_card(rbg_ctx* ctx, int op, int32_t batch, int key_lo, int key_hi) {
-  CHK(enter(&ctx->c));
-  int hc;
-  bool hv;
-  CHK(ctx_wide(&ctx->c, op, batch, key_lo, key_hi, nullptr, true, &hc, &hv));
-  if (hv) {
-    ResultInfo ri = {};
-    ri.card32 = (uint32_t)hc;
-    ri.long_card = hc;
-    HIPCHK(hipMemcpyAsync(ctx->c.info.p, &ri, sizeof(ri), hipMemcpyHostToDevice, ctx->c.stream));
-    HIPCHK(hipStreamSynchronize(ctx->c.stream));
-  }
-  return RBG_OK;
-}
-int rbg_ctx_batch_and_card(rbg_ctx* ctx, int32_t batch) {
-  CHK(enter(&ctx->c));
-  return ctx_batch_card(&ctx->c, batch);
-}
-int rbg_ctx_card(rbg_ctx* ctx, int32_t* out) {
-  CHK(enter(&ctx->c));
-  ResultInfo ri;
-  CHK(ctx_info(&ctx->c, &ri));
-  *out = (int32_t)ri.card32;
-  return RBG_OK;
-}
-int rbg_ctx_cards(rbg_ctx* ctx, int32_t* out, size_t n) {
-  CHK(enter(&ctx->c));
-  if (n > ctx->c.n_cards) return RBG_ERR_ILLEGAL_ARGUMENT;
-  HIPCHK(hipMemcpyAsync(out, ctx->c.cards.p, 4 * n, hipMemcpyDeviceToHost, ctx->c.stream));
-  HIPCHK(hipStreamSynchronize(ctx->c.stream));
-  return RBG_OK;
-}
-int rbg_ctx_result_stats(rbg_ctx* ctx, int64_t* st) {
-  CHK(enter(&ctx->c));
-  ResultInfo ri;
-  CHK(ctx_info(&ctx->c, &ri));
-  st[0] = ri.n_out;
-  st[1] = (int64_t)ri.payload;
-  st[2] = ri.has_run;
-  st[3] = ri.long_card;
-  return RBG_OK;
-}
-int rbg_ctx_serialize(rbg_ctx* ctx) {
-  CHK(enter(&ctx->c));
-  return ctx_serialize(&ctx->c);
-}
-int rbg_ctx_fetch(rbg_ctx* ctx, rbg_buffer* out) {
-  CHK(enter(&ctx->c));
-  return ctx_fetch(&ctx->c, out);
-}
+
 // Key-shard placement of the pending result inside a global portable bitmap of
 // total_containers containers, enqueued on the context stream.
 static int ctx_fetch_shard_device(Ctx* c, int64_t total_containers, int has_run, int64_t payload_base, void* desc_dst,
@@ -3645,79 +2616,6 @@ static int ctx_fetch_shard_device(Ctx* c, int64_t total_containers, int has_run,
                          has_run ? (uint8_t*)runflag_dst : nullptr);
   HIPCHK(hipGetLastError());
   return RBG_OK;
-}
-
-int rbg_ctx_result_layout_device(rbg_ctx* ctx, void* dst3) {
-  if (!ctx || !dst3) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c = &ctx->c;
-  CHK(enter(c));
-  if (c->last != 1) {
-    set_err("no materialised result pending");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  if (c->place_pending) {  // the placement writes the layout too (one launch fewer per sharded step)
-    OutCtx o = c->pending;
-    o.layout_out = reinterpret_cast<int64_t*>(dst3);
-    launch_place(c->stream, c->ntasks.as<uint32_t>(), o, c->info.as<ResultInfo>());
-    c->place_pending = false;
-  } else {
-    launch_layout_out(c->stream, c->info.as<ResultInfo>(), reinterpret_cast<int64_t*>(dst3));
-  }
-  HIPCHK(hipGetLastError());
-  return RBG_OK;
-}
-int rbg_ctx_fetch_shard_device_dyn(rbg_ctx* ctx, const void* layout, int rank, int world, void* out, void* runb) {
-  if (!ctx || !layout || !out || world < 1 || world > 1024 || rank < 0 || rank >= world)
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c = &ctx->c;
-  CHK(enter(c));
-  if (c->last != 1) {
-    set_err("no materialised result pending");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  CHK(ensure_placed(c));
-  // an already serialized result's pass-through records may point into released operands: copy its
-  // payload region instead (like rbg_ctx_fetch_shard_device); not expected on the sharded path
-  if (c->serialized) {
-    set_err("fetch_shard_device_dyn: the result was already serialized; fetch it before releasing operands "
-            "or use rbg_ctx_fetch_shard_device");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  launch_serialize_shard_dyn(c->stream, grid_for((c->pending_ub + 255) / 256, 256), c->ntasks.as<uint32_t>(), c->pending,
-                             reinterpret_cast<const int64_t*>(layout), rank, world, (uint8_t*)out, (uint8_t*)runb, true);
-  HIPCHK(hipGetLastError());
-  return RBG_OK;
-}
-int rbg_ctx_fetch_shard_device(rbg_ctx* ctx, int64_t total_containers, int has_run, int64_t payload_base,
-                               void* desc_dst, void* offsets_dst, void* runflag_dst, void* payload_dst) {
-  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_fetch_shard_device(&ctx->c, total_containers, has_run, payload_base, desc_dst, offsets_dst, runflag_dst,
-                                payload_dst);
-}
-
-int rbg_ctx_fetch_shard(rbg_ctx* ctx, int64_t total_containers, int has_run, int64_t first_container,
-                        int64_t payload_base, rbg_buffer* out_desc, rbg_buffer* out_offsets, rbg_buffer* out_payload) {
-  if (!ctx || !out_desc || !out_offsets || !out_payload) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx& c = ctx->c;
-  CHK(enter(&c));
-  (void)first_container;  // the shard's own buffers start at its first container
-  ResultInfo ri;
-  CHK(ctx_info(&c, &ri));
-  const size_t n = ri.n_out;
-  const bool offsets = !has_run || total_containers >= 4;
-  DevBuf d;
-  CHK(d.ensure(9 * n + ri.payload + 64));
-  uint8_t* base = d.as<uint8_t>();
-  CHK(ctx_fetch_shard_device(&c, total_containers, has_run, payload_base, base, base + 4 * n, base + 8 * n,
-                             base + 9 * n));
-  std::vector<uint8_t> h(9 * n + ri.payload);
-  if (!h.empty()) HIPCHK(hipMemcpyAsync(h.data(), base, h.size(), hipMemcpyDeviceToHost, c.stream));
-  HIPCHK(hipStreamSynchronize(c.stream));
-  CHK(emit_host(std::vector<uint8_t>(h.begin(), h.begin() + 4 * n), out_desc));
-  CHK(emit_host(offsets ? std::vector<uint8_t>(h.begin() + 4 * n, h.begin() + 8 * n) : std::vector<uint8_t>(),
-                out_offsets));
-  return emit_host(std::vector<uint8_t>(h.begin() + 9 * n, h.end()), out_payload);
 }
 
 // C3 synthetic key slice [key_lo, key_hi) of n bitmaps (kind 1 uniform, 2 clustered)
@@ -4008,7 +2906,7 @@ static int ctx_run_optimize(Ctx* c, int32_t id, int32_t* out_id, uint8_t* answer
   b.bsi_max = a->bsi_max;
   b.payload_bytes = a->payload_bytes;  // the input's layout (holes after shrunk containers)
   b.gapped = a->gapped || a->n_kind[DK_R] > 0;  // only R -> A can leave an all-array batch with holes
-  b.max_ser = 0;  // runOptimize leaves no container above 8194 serialized bytes
+  b.max_ser = 0;  // runOptimize leaves no container above kStagedMax serialized bytes
   b.ser_bytes = a->ser_bytes ? 1 : 0;  // nonzero: computed by ensure_stats
   b.stats_pending = true;
   b.live = true;
@@ -4030,7 +2928,7 @@ static int ctx_run_optimize(Ctx* c, int32_t id, int32_t* out_id, uint8_t* answer
 // :436-438,481-483), so selectRange(x, Long.MAX_VALUE) keeps [start, 0xFFFFFFFF).  Divergences, raised as
 // IllegalArgumentException: a negative bound (the reference's assert) and casts that put the last key below the
 // first (the reference would append keys out of order).
-static int ctx_select_range(Ctx* c, int32_t id, int64_t start, int64_t end, int32_t* out_id, bool buf) {
+static int ctx_select_range(Ctx* c, int32_t id, int64_t start, int64_t end, int32_t* out_id, bool buf = false) {
   if (start < 0 || end < 0) {
     set_err("selectRange: rangeStart and rangeEnd must not be negative");
     return RBG_ERR_ILLEGAL_ARGUMENT;
@@ -4115,17 +3013,1049 @@ static int ctx_select_range(Ctx* c, int32_t id, int64_t start, int64_t end, int3
   return RBG_OK;
 }
 
+// HIP-event phase timing of the next max_ops ops (Ctx::mark); max_ops <= 0 turns it off
+static int ctx_profile(Ctx* c, int max_ops, bool compute_only) {
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->prof_free();
+  c->prof_compute_only = compute_only;
+  if (max_ops <= 0) return RBG_OK;
+  c->prof_ev.resize(4 * (size_t)max_ops);
+  for (hipEvent_t& e : c->prof_ev) HIPCHK(hipEventCreate(&e));
+  c->prof_cap = (size_t)max_ops;
+  c->prof_n = 0;
+  CHK(c->rd_ctr.ensure(8));
+  HIPCHK(hipMemsetAsync(c->rd_ctr.p, 0, 8, c->stream));
+  return RBG_OK;
+}
+
+// ---------------------------------------------------------------------------
+// thread-local one-shot contexts
+// ---------------------------------------------------------------------------
+static std::mutex g_dev_mu;
+static uint64_t g_dev_mask = 1;
+
+struct TLCtx {
+  std::unique_ptr<Ctx> ctx;
+  int device = -1;
+};
+static thread_local TLCtx tl;
+
+static int tl_ctx(Ctx** out) {
+  int dev;
+  {
+    std::lock_guard<std::mutex> g(g_dev_mu);
+    uint64_t m = g_dev_mask;
+    dev = m ? __builtin_ctzll(m) : 0;
+  }
+  if (!tl.ctx || tl.device != dev) {
+    std::unique_ptr<Ctx> c(new Ctx());
+    CHK(ctx_init(c.get(), dev));
+    tl.ctx = std::move(c);
+    tl.device = dev;
+  }
+  CHK(enter(tl.ctx.get()));
+  *out = tl.ctx.get();
+  return RBG_OK;
+}
+
+// Scope of a one-shot call: the calling thread's context and the batches the call made, dropped on
+// exit.  load / load_separate register their batches before they return, adopt those an op made.
+struct OneShot {
+  Ctx* c = nullptr;
+  BatchGuard g{nullptr, {}};
+  int open() {
+    CHK(tl_ctx(&c));
+    g.c = c;
+    return RBG_OK;
+  }
+  void adopt(int32_t id) { g.ids.push_back(id); }
+  int load(const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* id, bool pack_arrays = false,
+           bool key_major = true) {
+    CHK(ctx_load_impl(c, bufs, lens, n, key_major, id, pack_arrays));
+    adopt(*id);
+    return RBG_OK;
+  }
+  int load_separate(const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* ids) {
+    CHK(ctx_load_separate(c, bufs, lens, n, ids));
+    g.ids.insert(g.ids.end(), ids, ids + n);
+    return RBG_OK;
+  }
+};
+
+// the batch [ebM, slices, foundSet?] of a one-shot BSI call
+static int bsi_load(OneShot& os, const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* lens,
+                    size_t nbits, const uint8_t* found, size_t found_len, int32_t* id) {
+  if (!ebm || (nbits && (!slices || !lens)) || nbits + 2 > (size_t)kBsiMaxInputs) return RBG_ERR_ILLEGAL_ARGUMENT;
+  std::vector<const uint8_t*> bufs{ebm};
+  std::vector<size_t> ls{ebm_len};
+  for (size_t i = 0; i < nbits; i++) {
+    bufs.push_back(slices[i]);
+    ls.push_back(lens[i]);
+  }
+  if (found) {
+    bufs.push_back(found);
+    ls.push_back(found_len);
+  }
+  return os.load(bufs.data(), ls.data(), bufs.size(), id);
+}
+
+}  // namespace rbg
+
+using namespace rbg;
+
+struct rbg_ctx {
+  Ctx c;
+};
+
+// entry of a session call: a null handle is an illegal argument; else the context, entered
+static int session(rbg_ctx* ctx, Ctx** c) {
+  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
+  *c = &ctx->c;
+  return enter(*c);
+}
+
+extern "C" {
+
+int rbg_version(void) { return 1; }
+
+void rbg_trim(void) {
+  std::lock_guard<std::mutex> g(g_out_mu);
+  for (const auto& e : g_out_cache) std::free(e.first);
+  g_out_cache.clear();
+}
+
+uint64_t rbg_pool_evictions(void) { return g_pool_evictions.load(); }
+const char* rbg_last_error(void) { return g_err.c_str(); }
+
+void rbg_free(rbg_buffer* buf) {
+  if (!buf) return;
+  if (buf->data) {
+    std::lock_guard<std::mutex> g(g_out_mu);
+    const auto it = g_out_live.find(buf->data);
+    if (it != g_out_live.end()) {  // a large result buffer: kept for reuse (the oldest kept one freed)
+      g_out_cache.emplace_back(it->first, it->second);
+      g_out_live.erase(it);
+      while (g_out_cache.size() > kOutCacheMax || (!g_out_cache.empty() && out_cache_bytes() > kOutCacheBytes)) {
+        std::free(g_out_cache.front().first);
+        g_out_cache.erase(g_out_cache.begin());
+      }
+      buf->data = nullptr;
+      buf->len = 0;
+      return;
+    }
+  }
+  std::free(buf->data);
+  buf->data = nullptr;
+  buf->len = 0;
+}
+
+int rbg_set_devices(uint64_t mask) {
+  int n = 0;
+  if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
+    set_err("no HIP device");
+    return RBG_ERR_DEVICE;
+  }
+  uint64_t usable = mask & ((n >= 64) ? ~0ULL : ((1ULL << n) - 1));
+  if (!usable) {
+    set_err("device mask selects no present device");
+    return RBG_ERR_DEVICE;
+  }
+  std::lock_guard<std::mutex> g(g_dev_mu);
+  g_dev_mask = usable;
+  return __builtin_popcountll(usable);
+}
+
+int rbg_pairwise(int op, const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, rbg_buffer* out) {
+  if (!out || op < 0 || op > RBG_ANDNOT_BUFFER) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  const uint8_t* bufs[2] = {a, b};
+  const size_t lens[2] = {a_len, b_len};
+  int32_t ids[2];
+  CHK(os.load_separate(bufs, lens, 2, ids));  // one upload for both operands
+  CHK(ctx_pairwise(c, op, ids[0], 0, ids[1], 0, false, 0, kMaxKeys, op <= RBG_ANDNOT ? pipe_ranges() : 0));
+  return ctx_fetch(c, out);
+}
+
+int rbg_pairwise_inplace(int op, const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int same_object,
+                         rbg_buffer* out) {
+  if (!out || op < 0 || op > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (same_object) {
+    // x1.and(x1) / x1.or(x1) return at once (x1 unchanged); x1.xor(x1) / x1.andNot(x1) clear it
+    // (RB/RoaringBitmap.java:1271, 2482, 3297-3300, 1347-1350)
+    if (op == RBG_XOR || op == RBG_ANDNOT) return emit_empty(out);
+    // x1 unchanged: validated on the host like any input, then its own bytes back (no device call)
+    HostBitmap hb;
+    std::string err;
+    const int st = parse(a, a_len, &hb, &err);
+    if (st) {
+      set_err(err);
+      return st;
+    }
+    uint8_t* p = out_alloc(hb.consumed);
+    if (!p) return RBG_ERR_OUT_OF_MEMORY;
+    std::memcpy(p, a, hb.consumed);
+    out->data = p;
+    out->len = hb.consumed;
+    return RBG_OK;
+  }
+  // x1.and / xor / andNot(x2) in place type like the static ops (Container.iand / ixor / iandNot
+  // end in the same container types, DESIGN.md §4); x1.or(x2) is Container.ior's
+  return rbg_pairwise(op == RBG_OR ? RBG_OR_INPLACE : op, a, a_len, b, b_len, out);
+}
+
+int rbg_ornot(const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int64_t range_end, int flags,
+              rbg_buffer* out) {
+  if (!out || flags < 0 || flags > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  const uint8_t* bufs[2] = {a, b};
+  const size_t lens[2] = {a_len, b_len};
+  int32_t ids[2];
+  CHK(os.load_separate(bufs, lens, 2, ids));
+  CHK(ctx_ornot(c, ids[0], 0, ids[1], 0, range_end, flags));
+  return ctx_fetch(c, out);
+}
+
+int rbg_ctx_ornot(rbg_ctx* ctx, int32_t a, size_t ia, int32_t b, size_t ib, int64_t range_end, int flags) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (flags < 0 || flags > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_ornot(c, a, ia, b, ib, range_end, flags);
+}
+
+int rbg_range_mut(int op, const uint8_t* a, size_t a_len, int64_t range_start, int64_t range_end, rbg_buffer* out) {
+  if (!out || op < 0 || op > (RBG_RMUT_ADD_INPLACE | RBG_RMUT_BUFFER))
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load_separate(&a, &a_len, 1, &id));
+  CHK(ctx_range_mut(c, op & 3, id, 0, range_start, range_end, (op & RBG_RMUT_BUFFER) != 0));
+  return ctx_fetch(c, out);
+}
+
+int rbg_ctx_range_mut(rbg_ctx* ctx, int op, int32_t batch, size_t i, int64_t range_start, int64_t range_end) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (op < 0 || op > (RBG_RMUT_ADD_INPLACE | RBG_RMUT_BUFFER)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_range_mut(c, op & 3, batch, i, range_start, range_end, (op & RBG_RMUT_BUFFER) != 0);
+}
+
+int rbg_add_offset(const uint8_t* a, size_t a_len, int64_t offset, rbg_buffer* out) {
+  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load_separate(&a, &a_len, 1, &id));
+  CHK(ctx_add_offset(c, id, 0, offset));
+  return ctx_fetch(c, out);
+}
+
+/* ---- point queries (rankdir.hip) ---- */
+
+int rbg_ctx_point_query(rbg_ctx* ctx, int op, int32_t batch, size_t i, const uint32_t* q, size_t n, int64_t* out) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!point_op_ok(op)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n == 0) return RBG_OK;
+  if (!q || !out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_point_host(c, op, batch, i, q, n, out);
+}
+
+int rbg_ctx_point_query_device(rbg_ctx* ctx, int op, int32_t batch, size_t i, const void* q_dev, size_t n,
+                               void* out_dev) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!point_op_ok(op)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n == 0) return RBG_OK;
+  if (!q_dev || !out_dev) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_point(c, op, batch, i, reinterpret_cast<const uint32_t*>(q_dev), n,
+                   reinterpret_cast<long long*>(out_dev));
+}
+
+int rbg_point_query(int op, const uint8_t* buf, size_t len, const uint32_t* q, size_t n, int64_t* out) {
+  if (!point_op_ok(op)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n == 0) return RBG_OK;
+  if (!buf || !q || !out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load_separate(&buf, &len, 1, &id));
+  return ctx_point_host(c, op, id, 0, q, n, out);
+}
+
+int rbg_ctx_from_values(rbg_ctx* ctx, const uint32_t* values, size_t n, int run_optimize, int32_t* batch) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!batch || (n && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_from_values_host(c, values, n, run_optimize != 0, batch);
+}
+
+int rbg_ctx_from_values_device(rbg_ctx* ctx, const void* values_dev, size_t n, int run_optimize, int32_t* batch) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!batch || (n && !values_dev)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_from_values(c, reinterpret_cast<const uint32_t*>(values_dev), n, run_optimize != 0, batch);
+}
+
+int rbg_ctx_to_values(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t count, uint32_t* out,
+                      uint64_t* n_out) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_to_values_host(c, batch, i, first, count, out, n_out);
+}
+
+int rbg_ctx_to_values_device(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t count, int out64,
+                             void* out_dev, uint64_t* n_out) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_to_values(c, batch, i, first, count, out64 != 0, out_dev, n_out);
+}
+
+int rbg_build_values(const uint32_t* values, size_t n, int run_optimize, rbg_buffer* out) {
+  if (!out || (n && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(ctx_from_values_host(c, values, n, run_optimize != 0, &id));
+  os.adopt(id);
+  return ctx_batch_fetch(c, id, 0, out);
+}
+
+int rbg_expand_values(const uint8_t* buf, size_t len, rbg_buffer* out) {
+  if (!out || (!buf && len)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load_separate(&buf, &len, 1, &id));
+  const uint64_t card = (uint64_t)c->batches[id]->long_card;
+  uint8_t* p = (uint8_t*)std::malloc(card * 4 + 4);
+  if (!p) return RBG_ERR_OUT_OF_MEMORY;
+  uint64_t got = 0;
+  const int st = ctx_to_values_host(c, id, 0, 0, card, reinterpret_cast<uint32_t*>(p), &got);
+  if (st != RBG_OK) {
+    std::free(p);
+    return st;
+  }
+  out->data = p;
+  out->len = (size_t)got * 4;
+  return RBG_OK;
+}
+
+// x.limit(maxcardinality) (RB/RoaringBitmap.java:2457-2476).  The cut is planned from the serialized
+// header's cardinalities on the host (the reference's own loop walks getCardinality per container);
+// ctx_limit cuts on the device.
+int rbg_limit(const uint8_t* a, size_t a_len, int32_t maxcard, rbg_buffer* out) {
+  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  HostBitmap hb;
+  std::string err;
+  const int pst = parse(a, a_len, &hb, &err);
+  if (pst) {
+    set_err(err);
+    return pst;
+  }
+  int cut_key = 65536, leftover = 0;
+  int64_t cur = 0;
+  for (size_t i = 0; cur < maxcard && i < hb.ctrs.size(); i++) {
+    const int64_t cc = hb.ctrs[i].card;
+    if (cc + cur <= maxcard) {
+      cur += cc;
+    } else {
+      cut_key = hb.ctrs[i].key;
+      leftover = (int)(maxcard - cur);
+      break;
+    }
+  }
+  if (leftover == 0) {  // the containers that fit whole: those before the first that does not
+    cut_key = 0;
+    for (size_t i = 0, acc = 0; i < hb.ctrs.size() && (int64_t)(acc + hb.ctrs[i].card) <= (int64_t)maxcard; i++) {
+      acc += hb.ctrs[i].card;
+      cut_key = hb.ctrs[i].key + 1;
+    }
+  }
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load_separate(&a, &a_len, 1, &id));
+  CHK(ctx_limit(c, id, 0, cut_key, leftover));
+  return ctx_fetch(c, out);
+}
+
+// RoaringBitmap.bitmapOfRange(min, max) (RB/RoaringBitmap.java:588-615): k_rmut<RMUT_RANGE> over an empty
+// bitmap (every container written as a run container)
+int rbg_bitmap_of_range(int64_t min, int64_t max, rbg_buffer* out) {
+  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  const uint8_t* a = kEmpty;
+  size_t a_len = sizeof(kEmpty);
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load_separate(&a, &a_len, 1, &id));
+  CHK(ctx_range_mut(c, RMUT_RANGE, id, 0, min, max, false));
+  return ctx_fetch(c, out);
+}
+
+int rbg_remove_run_compression(const uint8_t* a, size_t a_len, rbg_buffer* out) {
+  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load_separate(&a, &a_len, 1, &id));
+  CHK(ctx_remove_run_compression(c, id, 0));
+  return ctx_fetch(c, out);
+}
+
+int rbg_ctx_add_offset(rbg_ctx* ctx, int32_t batch, size_t i, int64_t offset) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_add_offset(c, batch, i, offset);
+}
+
+int rbg_pairwise_card(int op, const uint8_t* a, size_t a_len, const uint8_t* b, size_t b_len, int32_t* out) {
+  if (!out || op < 0 || op > RBG_CONTAINS) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t ia, ib;
+  CHK(os.load(&a, &a_len, 1, &ia));
+  CHK(os.load(&b, &b_len, 1, &ib));
+  CHK(ctx_pairwise(c, OP_AND, ia, 0, ib, 0, true));
+  ResultInfo ri;
+  CHK(ctx_info(c, &ri));
+  const uint32_t ac = ri.card32;
+  const uint32_t ca = (uint32_t)(uint64_t)c->batches[ia]->long_card;  // RoaringBitmap.getCardinality (int)
+  const uint32_t cb = (uint32_t)(uint64_t)c->batches[ib]->long_card;
+  switch (op) {
+    case RBG_CARD_AND: *out = (int32_t)ac; break;
+    case RBG_CARD_OR: *out = (int32_t)(ca + cb - ac); break;         // RB/RoaringBitmap.java:916-920
+    case RBG_CARD_XOR: *out = (int32_t)(ca + cb - 2u * ac); break;   // :931-933
+    case RBG_CARD_ANDNOT: *out = (int32_t)(ca - ac); break;          // :944-985 (both branches, mod 2^32)
+    case RBG_CONTAINS:  // b is a subset of a (:2781-2802): every value of b in a AND b, counted in 64 bits
+      *out = ri.long_card == c->batches[ib]->long_card ? 1 : 0;
+      break;
+    default: *out = ri.any ? 1 : 0; break;                           // intersects :698-720
+  }
+  return RBG_OK;
+}
+
+int rbg_wide(int op, const uint8_t* const* bufs, const size_t* lens, const int32_t* ids, size_t n, rbg_buffer* out) {
+  if (!out || op < 0 || op > RBG_WIDE_BUFFER_AND_ITER) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load(bufs, lens, n, &id, wide_reads_packed(op, n)));
+  int hc;
+  bool hv;
+  CHK(ctx_wide(c, op, id, 0, 65536, ids, false, &hc, &hv));
+  return ctx_fetch(c, out);
+}
+
+int rbg_range_op(int op, const uint8_t* const* bufs, const size_t* lens, size_t n, int64_t range_start,
+                 int64_t range_end, rbg_buffer* out) {
+  if (!out || op < RBG_RANGE_AND || op > RBG_RANGE_BUFFER_ANDNOT ||
+      ((op == RBG_RANGE_ANDNOT || op == RBG_RANGE_BUFFER_ANDNOT) && n != 2))
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  const bool buf = op >= RBG_RANGE_BUFFER_AND;
+  const int base = buf ? op - RBG_RANGE_BUFFER_AND : op;
+  if (buf && base == RBG_RANGE_AND && n == 0) {
+    // BufferFastAggregation.and(long[], Iterator) with no input: an empty bitmap (:81-88)
+    CHK(check_range(range_start, range_end));
+    return emit_empty(out);
+  }
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  CHK(check_range(range_start, range_end));  // rangeSanityCheck before the selections (RB/RoaringBitmap.java:204-213)
+  if (base == RBG_RANGE_ANDNOT) {  // andNot(x1, x2, start, end): both operands selected, then andNot
+    int32_t ids[2], sel[2];
+    CHK(os.load_separate(bufs, lens, 2, ids));
+    for (int i = 0; i < 2; i++) {
+      CHK(ctx_select_range(c, ids[i], range_start, range_end, &sel[i], buf));
+      os.adopt(sel[i]);
+    }
+    // the buffer package's andNot keeps R \ R's merged run container (ImmutableRoaringBitmap.andNot)
+    CHK(ctx_pairwise(c, buf ? RBG_ANDNOT_BUFFER : OP_ANDNOT, sel[0], 0, sel[1], 0, false));
+    return ctx_fetch(c, out);
+  }
+  int32_t id, sel;
+  CHK(os.load(bufs, lens, n, &id));
+  CHK(ctx_select_range(c, id, range_start, range_end, &sel, buf));
+  os.adopt(sel);
+  // heap: and -> FastAggregation.and(Iterator) = naive_and(Iterator); or / xor -> naive_or / naive_xor.
+  // buffer: and -> BufferFastAggregation.and(Iterator) = workShyAnd for any count (no input: empty);
+  // or / xor -> naive_or / naive_xor, typed like the heap's
+  const int wop = base == RBG_RANGE_AND ? (buf ? RBG_WIDE_WORKSHY_AND : RBG_WIDE_AND_ITER)
+                  : base == RBG_RANGE_OR ? RBG_WIDE_OR
+                                         : RBG_WIDE_XOR;
+  int hc;
+  bool hv;
+  CHK(ctx_wide(c, wop, sel, 0, 65536, nullptr, false, &hc, &hv));
+  return ctx_fetch(c, out);
+}
+
+int rbg_select_range(const uint8_t* a, size_t a_len, int64_t range_start, int64_t range_end, int buffer,
+                     rbg_buffer* out) {
+  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id, sel;
+  CHK(os.load_separate(&a, &a_len, 1, &id));
+  CHK(ctx_select_range(c, id, range_start, range_end, &sel, buffer != 0));
+  os.adopt(sel);
+  return ctx_batch_fetch(c, sel, 0, out);
+}
+
+int rbg_ctx_select_range(rbg_ctx* ctx, int32_t batch, int64_t range_start, int64_t range_end, int32_t* out_batch) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!out_batch) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_select_range(c, batch, range_start, range_end, out_batch);
+}
+
+int rbg_wide_card(int op, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* out) {
+  if (!out || op < 0 || op > 1) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load(bufs, lens, n, &id));
+  int hc = 0;
+  bool hv = false;
+  CHK(ctx_wide(c, op, id, 0, 65536, nullptr, true, &hc, &hv));
+  if (hv) {
+    *out = hc;
+    return RBG_OK;
+  }
+  ResultInfo ri;
+  CHK(ctx_info(c, &ri));
+  *out = (int32_t)ri.card32;
+  return RBG_OK;
+}
+
+int rbg_batch_and_card(size_t n_pairs, const uint8_t* const* a_bufs, const size_t* a_lens,
+                       const uint8_t* const* b_bufs, const size_t* b_lens, int32_t* out) {
+  if (n_pairs && (!a_bufs || !a_lens || !b_bufs || !b_lens || !out)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n_pairs == 0) return RBG_OK;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  std::vector<const uint8_t*> bufs(2 * n_pairs);
+  std::vector<size_t> lens(2 * n_pairs);
+  for (size_t i = 0; i < n_pairs; i++) {
+    bufs[2 * i] = a_bufs[i];
+    lens[2 * i] = a_lens[i];
+    bufs[2 * i + 1] = b_bufs[i];
+    lens[2 * i + 1] = b_lens[i];
+  }
+  int32_t id;  // bitmap-major: the pairs stay adjacent
+  CHK(os.load(bufs.data(), lens.data(), 2 * n_pairs, &id, false, false));
+  CHK(ctx_batch_card(c, id));
+  HIPCHK(hipMemcpyAsync(out, c->cards.p, 4 * n_pairs, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return RBG_OK;
+}
+
+// ---- host-side format utilities ----
+
+int rbg_from_values(const uint32_t* values, size_t n, int run_optimize, rbg_buffer* out) {
+  if (!out || (n && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return emit_host(build_from_values(values, n, run_optimize != 0), out);
+}
+
+// RoaringBitmap.runOptimize() (RB/RoaringBitmap.java:2764-2774): the device pass
+// (runopt.hip) over a one-bitmap batch, like rbg_run_optimize_many.
+int rbg_run_optimize(const uint8_t* buf, size_t len, rbg_buffer* out) {
+  if (!out || (!buf && len)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  uint8_t answer = 0;
+  return rbg_run_optimize_many(&buf, &len, 1, out, &answer);
+}
+
+int rbg_to_values(const uint8_t* buf, size_t len, rbg_buffer* out) {
+  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  std::vector<uint32_t> v;
+  std::string err;
+  int st = values_of_serialized(buf, len, &v, &err);
+  if (st) {
+    set_err(err);
+    return st;
+  }
+  return emit_bytes(reinterpret_cast<const uint8_t*>(v.data()), v.size() * 4, out);
+}
+
+int rbg_inspect(const uint8_t* buf, size_t len, size_t* consumed, int64_t* cardinality, int64_t* stats3) {
+  HostBitmap hb;
+  std::string err;
+  int st = parse(buf, len, &hb, &err);
+  if (st) {
+    set_err(err);
+    return st;
+  }
+  if (consumed) *consumed = hb.consumed;
+  if (cardinality) *cardinality = hb.card;
+  if (stats3) {
+    stats3[0] = stats3[1] = stats3[2] = 0;
+    for (const HostCtr& c : hb.ctrs) stats3[c.kind]++;
+  }
+  return RBG_OK;
+}
+
+// ---- session API ----
+int rbg_ctx_create(int device, rbg_ctx** out) {
+  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  std::unique_ptr<rbg_ctx> c(new rbg_ctx());
+  CHK(ctx_init(&c->c, device));
+  *out = c.release();
+  return RBG_OK;
+}
+void rbg_ctx_destroy(rbg_ctx* ctx) {
+  if (!ctx) return;
+  (void)hipSetDevice(ctx->c.device);
+  delete ctx;
+}
+void* rbg_ctx_stream(rbg_ctx* ctx) { return ctx ? (void*)ctx->c.stream : nullptr; }
+int rbg_ctx_profile(rbg_ctx* ctx, int max_ops) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_profile(c, max_ops, false);
+}
+int rbg_ctx_profile_compute(rbg_ctx* ctx, int max_ops) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_profile(c, max_ops, true);
+}
+int rbg_ctx_profile_bytes(rbg_ctx* ctx, int64_t* bytes) {
+  if (!ctx || !bytes) {
+    set_err("profile_bytes: null argument");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  Ctx* c;
+  CHK(session(ctx, &c));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  unsigned long long v = 0;
+  if (c->rd_ctr.p) HIPCHK(hipMemcpy(&v, c->rd_ctr.p, 8, hipMemcpyDeviceToHost));
+  *bytes = (int64_t)v;
+  return RBG_OK;
+}
+int rbg_ctx_profile_read(rbg_ctx* ctx, double* ms3, int* n_ops) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  ms3[0] = ms3[1] = ms3[2] = 0.0;
+  for (size_t i = 0; i < c->prof_n; i++) {
+    for (int ph = 0; ph < 3; ph++) {
+      if (c->prof_compute_only && ph != 1) continue;  // only the compute launch was bracketed
+      float ms = 0.f;
+      HIPCHK(hipEventElapsedTime(&ms, c->prof_ev[4 * i + ph], c->prof_ev[4 * i + ph + 1]));
+      ms3[ph] += ms;
+    }
+  }
+  *n_ops = (int)c->prof_n;
+  c->prof_n = 0;
+  return RBG_OK;
+}
+int rbg_ctx_sync(rbg_ctx* ctx) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return RBG_OK;
+}
+int rbg_ctx_load_separate(rbg_ctx* ctx, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* ids) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!ids) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_load_separate(c, bufs, lens, n, ids);
+}
+int rbg_ctx_load(rbg_ctx* ctx, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* batch) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_load(c, bufs, lens, n, batch);
+}
+int rbg_ctx_load_packed(rbg_ctx* ctx, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* batch) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!batch) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_load(c, bufs, lens, n, batch, true);
+}
+int rbg_ctx_release(rbg_ctx* ctx, int32_t batch) {
+  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
+  Ctx& c = ctx->c;
+  Batch* b;
+  CHK(find_batch(&c, batch, &b));  // no statistics read-back for a batch that goes
+  CHK(enter(&c));
+  // A materialised result references pass-through containers inside its operand
+  // batches (ORec::src) until it is serialized: serialize it before an operand goes.
+  if (c.last == 1 && !c.serialized &&
+      std::find(c.pending_src.begin(), c.pending_src.end(), batch) != c.pending_src.end())
+    CHK(ctx_serialize(&c));
+  // No host sync: the buffers go to this context's pool, and whatever reuses them is enqueued on
+  // the same stream after every launch that reads them (a pipelined op's second stream is joined
+  // back into it at the op's end); a pooled buffer that is freed goes through hipFree, which waits
+  // for the device.
+  for (DevBuf* d : {&b->keys, &b->desc, &b->bm, &b->key_off, &b->bm_off, &b->payload, &b->ro_stats,
+                    &b->bsi_tasks, &b->bsi_nt, &b->bsi_table, &b->rd_cum, &b->rd_off, &b->rd_aux})
+    pool_put(&c, *d);
+  c.batches[batch].reset();
+  return RBG_OK;
+}
+int rbg_ctx_batch_stats(rbg_ctx* ctx, int32_t batch, int64_t* st) {
+  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
+  Batch* b;
+  CHK(get_batch(&ctx->c, batch, &b));
+  st[0] = (int64_t)b->n_bm;
+  st[1] = (int64_t)b->n_ctr;
+  st[2] = b->n_kind[0];
+  st[3] = b->n_kind[1];
+  st[4] = b->n_kind[2];
+  st[5] = 0;  // payload bytes (serialized form)
+  st[6] = b->long_card;
+  st[7] = b->ser_bytes;
+  if (b->n_ctr) {
+    CHK(enter(&ctx->c));
+    hipStream_t s = ctx->c.stream;
+    HIPCHK(hipMemsetAsync(ctx->c.scalar.p, 0, 8, s));
+    launch_batch_bytes(s, b->desc.as<CDesc>(), b->n_ctr, b->payload.as<uint8_t>(),
+                       ctx->c.scalar.as<unsigned long long>());
+    unsigned long long pay = 0;
+    HIPCHK(hipMemcpyAsync(&pay, ctx->c.scalar.p, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    st[5] = (int64_t)pay;
+  }
+  return RBG_OK;
+}
+int rbg_ctx_batch_fetch(rbg_ctx* ctx, int32_t batch, size_t i, rbg_buffer* out) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_batch_fetch(c, batch, i, out);
+}
+int rbg_ctx_batch_fetch_range(rbg_ctx* ctx, int32_t batch, size_t first, size_t count, rbg_buffer* outs) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_batch_fetch_range(c, batch, first, first + count, outs);
+}
+int rbg_ctx_pairwise(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_pairwise(c, op, a, ia, b, ib, false);
+}
+int rbg_ctx_pairwise_serialized(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (op < 0 || op > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
+  CHK(ctx_pairwise(c, op, a, ia, b, ib, false, 0, kMaxKeys, pipe_ranges()));
+  return ctx_serialize(c);  // no-op after the pipelined form
+}
+int rbg_ctx_pairwise_range(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib, int key_lo, int key_hi) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (key_lo > key_hi) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_pairwise(c, op, a, ia, b, ib, false, key_lo, key_hi);
+}
+int rbg_ctx_pairwise_card(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (op != RBG_CARD_AND) {
+    set_err("the session API computes andCardinality; derive the others from the input cardinalities");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  return ctx_pairwise(c, OP_AND, a, ia, b, ib, true);
+}
+int rbg_ctx_wide(rbg_ctx* ctx, int op, int32_t batch, int key_lo, int key_hi, const int32_t* ids) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  int hc;
+  bool hv;
+  return ctx_wide(c, op, batch, key_lo, key_hi, ids, false, &hc, &hv);
+}
+int rbg_ctx_wide_start(rbg_ctx* ctx, int op, int32_t batch, int key_lo, int key_hi, const int32_t* ids,
+                       int32_t start_bm) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  int hc;
+  bool hv;
+  return ctx_wide(c, op, batch, key_lo, key_hi, ids, false, &hc, &hv, start_bm);
+}
+int rbg_ctx_batch_counts(rbg_ctx* ctx, int32_t batch, uint32_t* out, size_t n) {
+  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
+  Batch* b;
+  CHK(get_batch(&ctx->c, batch, &b));
+  if (!out || n != b->n_bm) return RBG_ERR_ILLEGAL_ARGUMENT;
+  for (size_t i = 0; i < n; i++) out[i] = b->h_bm_nctr[i];
+  return RBG_OK;
+}
+int rbg_synth_key_bytes(int kind, uint64_t seed, size_t n, uint64_t* out) {
+  if (!out || (kind != 1 && kind != 2)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  for (int k = 0; k < kMaxKeys; k++) out[k] = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (kind == 1) {
+      for (int k = 0; k < kMaxKeys; k++) out[k] += 4 + 2 * (uint64_t)c3u_card(seed, (uint32_t)i, (uint32_t)k);
+    } else {
+      const uint32_t b0 = c3c_base(seed, (uint32_t)i);
+      for (uint32_t k = b0; k < b0 + 16; k++) out[k] += 4 + 8192;
+    }
+  }
+  return RBG_OK;
+}
+int rbg_ctx_bsi(rbg_ctx* ctx, int32_t batch, int op, int nbits, int has_found, int32_t start, int32_t end,
+                int32_t min_value, int32_t max_value, int want_sum) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_bsi(c, batch, op, nbits, has_found, start, end, min_value, max_value, want_sum);
+}
+int rbg_ctx_bsi_sums(rbg_ctx* ctx, int64_t* out2) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!out2) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_sums(c, out2);
+}
+int rbg_ctx_bsi_sums_target(rbg_ctx* ctx, void* dst2) {
+  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
+  ctx->c.bsi_sums_dst = dst2;
+  return RBG_OK;
+}
+int rbg_ctx_bsi_sums_device(rbg_ctx* ctx, void* dst2) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!dst2 || !c->bsi_sums.p) return RBG_ERR_ILLEGAL_ARGUMENT;
+  launch_bsi_sums_out(c->stream, c->bsi_sums.as<unsigned long long>(), dst2);
+  HIPCHK(hipGetLastError());
+  return RBG_OK;
+}
+int rbg_bsi_compare(int op, int32_t start, int32_t end, const uint8_t* ebm, size_t ebm_len,
+                    const uint8_t* const* slices, const size_t* slice_lens, size_t nbits, int32_t min_value,
+                    int32_t max_value, const uint8_t* found, size_t found_len, rbg_buffer* out) {
+  if (!out || op < 0 || op > BSI_RANGE) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
+  CHK(ctx_bsi(c, id, op, (int)nbits, found ? 1 : 0, start, end, min_value, max_value, 0));
+  return ctx_fetch(c, out);
+}
+int rbg_bsi_compare_buffer(int op, int32_t start, int32_t end, const uint8_t* ebm, size_t ebm_len,
+                           const uint8_t* const* slices, const size_t* slice_lens, size_t nbits, int32_t min_value,
+                           int32_t max_value, const uint8_t* found, size_t found_len, rbg_buffer* out) {
+  if (!out || op < 0 || op > RBG_BSI_RANGE_NEQ_DIRECT) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
+  CHK(ctx_bsi_buffer(c, id, op, (int)nbits, found ? 1 : 0, start, end, min_value, max_value));
+  return ctx_fetch(c, out);
+}
+int rbg_ctx_bsi_buffer(rbg_ctx* ctx, int32_t batch, int op, int nbits, int has_found, int32_t start, int32_t end,
+                       int32_t min_value, int32_t max_value) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_bsi_buffer(c, batch, op, nbits, has_found, start, end, min_value, max_value);
+}
+int rbg_bsi_sum(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
+                size_t nbits, const uint8_t* found, size_t found_len, int64_t* out2) {
+  if (!out2) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (!found) {  // BSI/:582: null foundSet -> (0, 0)
+    out2[0] = out2[1] = 0;
+    return RBG_OK;
+  }
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
+  CHK(ctx_bsi(c, id, BSI_SUM_ONLY, (int)nbits, 1, 0, 0, 0, 0, 1));
+  return ctx_bsi_sums(c, out2);
+}
+int rbg_debug_stamps(uint64_t* out20, int reset) {
+  if (!out20) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (getenv("RBG_DEBUG_BSI")) debug_bsi_stamps(out20, reset != 0);
+  else debug_stamps(out20, reset != 0);
+  return RBG_OK;
+}
+int rbg_ctx_pair_bytes(rbg_ctx* ctx, int32_t batch, int64_t* out2) {
+  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
+  Batch* b;
+  CHK(get_batch(&ctx->c, batch, &b));
+  if (!out2 || b->key_major || b->n_bm % 2) {
+    set_err("needs a bitmap-major batch of pairs");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  CHK(enter(&ctx->c));
+  HIPCHK(hipStreamSynchronize(ctx->c.stream));
+  std::vector<CDesc> d(b->n_ctr);
+  if (b->n_ctr) HIPCHK(hipMemcpy(d.data(), b->desc.p, sizeof(CDesc) * b->n_ctr, hipMemcpyDeviceToHost));
+  auto pay = [](const CDesc& x) -> int64_t { return x.kind == KA ? 2 * (int64_t)x.card : x.kind == KB ? 8192 : 0; };
+  int64_t matched = 0, all = 0;
+  for (size_t p = 0; p < b->n_bm / 2; p++) {
+    uint32_t i = b->h_bm_off[2 * p], ie = b->h_bm_off[2 * p + 1], j = ie, je = b->h_bm_off[2 * p + 2];
+    all += 4 * (int64_t)(je - i);
+    while (i < ie && j < je) {
+      if (d[i].key == d[j].key) {
+        matched += pay(d[i++]) + pay(d[j++]);
+      } else if (d[i].key < d[j].key) {
+        i++;
+      } else {
+        j++;
+      }
+    }
+  }
+  out2[0] = matched + all;  // SURVEY §8(d): matched payload + descriptors
+  int64_t tot = 0;
+  for (const CDesc& x : d) tot += pay(x) + 4;
+  out2[1] = tot;  // every payload + descriptors
+  return RBG_OK;
+}
+int rbg_ctx_wide_card(rbg_ctx* ctx, int op, int32_t batch, int key_lo, int key_hi) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  int hc;
+  bool hv;
+  CHK(ctx_wide(c, op, batch, key_lo, key_hi, nullptr, true, &hc, &hv));
+  if (hv) {
+    ResultInfo ri = {};
+    ri.card32 = (uint32_t)hc;
+    ri.long_card = hc;
+    HIPCHK(hipMemcpyAsync(c->info.p, &ri, sizeof(ri), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return RBG_OK;
+}
+int rbg_ctx_batch_and_card(rbg_ctx* ctx, int32_t batch) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_batch_card(c, batch);
+}
+int rbg_ctx_card(rbg_ctx* ctx, int32_t* out) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  ResultInfo ri;
+  CHK(ctx_info(c, &ri));
+  *out = (int32_t)ri.card32;
+  return RBG_OK;
+}
+int rbg_ctx_cards(rbg_ctx* ctx, int32_t* out, size_t n) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (n > c->n_cards) return RBG_ERR_ILLEGAL_ARGUMENT;
+  HIPCHK(hipMemcpyAsync(out, c->cards.p, 4 * n, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return RBG_OK;
+}
+int rbg_ctx_result_stats(rbg_ctx* ctx, int64_t* st) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  ResultInfo ri;
+  CHK(ctx_info(c, &ri));
+  st[0] = ri.n_out;
+  st[1] = (int64_t)ri.payload;
+  st[2] = ri.has_run;
+  st[3] = ri.long_card;
+  return RBG_OK;
+}
+int rbg_ctx_serialize(rbg_ctx* ctx) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_serialize(c);
+}
+int rbg_ctx_fetch(rbg_ctx* ctx, rbg_buffer* out) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_fetch(c, out);
+}
+int rbg_ctx_result_layout_device(rbg_ctx* ctx, void* dst3) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!dst3) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (c->last != 1) {
+    set_err("no materialised result pending");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (c->place_pending) {  // the placement writes the layout too (one launch fewer per sharded step)
+    OutCtx o = c->pending;
+    o.layout_out = reinterpret_cast<int64_t*>(dst3);
+    launch_place(c->stream, c->ntasks.as<uint32_t>(), o, c->info.as<ResultInfo>());
+    c->place_pending = false;
+  } else {
+    launch_layout_out(c->stream, c->info.as<ResultInfo>(), reinterpret_cast<int64_t*>(dst3));
+  }
+  HIPCHK(hipGetLastError());
+  return RBG_OK;
+}
+int rbg_ctx_fetch_shard_device_dyn(rbg_ctx* ctx, const void* layout, int rank, int world, void* out, void* runb) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!layout || !out || world < 1 || world > 1024 || rank < 0 || rank >= world)
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (c->last != 1) {
+    set_err("no materialised result pending");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  CHK(ensure_placed(c));
+  // an already serialized result's pass-through records may point into released operands: copy its
+  // payload region instead (like rbg_ctx_fetch_shard_device); not expected on the sharded path
+  if (c->serialized) {
+    set_err("fetch_shard_device_dyn: the result was already serialized; fetch it before releasing operands "
+            "or use rbg_ctx_fetch_shard_device");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  launch_serialize_shard_dyn(c->stream, grid_for((c->pending_ub + 255) / 256, 256), c->ntasks.as<uint32_t>(), c->pending,
+                             reinterpret_cast<const int64_t*>(layout), rank, world, (uint8_t*)out, (uint8_t*)runb, true);
+  HIPCHK(hipGetLastError());
+  return RBG_OK;
+}
+int rbg_ctx_fetch_shard_device(rbg_ctx* ctx, int64_t total_containers, int has_run, int64_t payload_base,
+                               void* desc_dst, void* offsets_dst, void* runflag_dst, void* payload_dst) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_fetch_shard_device(c, total_containers, has_run, payload_base, desc_dst, offsets_dst, runflag_dst,
+                                payload_dst);
+}
+
+int rbg_ctx_fetch_shard(rbg_ctx* ctx, int64_t total_containers, int has_run, int64_t first_container,
+                        int64_t payload_base, rbg_buffer* out_desc, rbg_buffer* out_offsets, rbg_buffer* out_payload) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!out_desc || !out_offsets || !out_payload) return RBG_ERR_ILLEGAL_ARGUMENT;
+  (void)first_container;  // the shard's own buffers start at its first container
+  ResultInfo ri;
+  CHK(ctx_info(c, &ri));
+  const size_t n = ri.n_out;
+  const bool offsets = !has_run || total_containers >= 4;
+  DevBuf d;
+  CHK(d.ensure(9 * n + ri.payload + 64));
+  uint8_t* base = d.as<uint8_t>();
+  CHK(ctx_fetch_shard_device(c, total_containers, has_run, payload_base, base, base + 4 * n, base + 8 * n,
+                             base + 9 * n));
+  std::vector<uint8_t> h(9 * n + ri.payload);
+  if (!h.empty()) HIPCHK(hipMemcpyAsync(h.data(), base, h.size(), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  CHK(emit_bytes(h.data(), 4 * n, out_desc));
+  CHK(emit_bytes(h.data() + 4 * n, offsets ? 4 * n : 0, out_offsets));
+  return emit_bytes(h.data() + 9 * n, ri.payload, out_payload);
+}
+
 int rbg_run_optimize_many(const uint8_t* const* bufs, const size_t* lens, size_t n, rbg_buffer* outs,
                           uint8_t* answers) {
   if (n && !outs) return RBG_ERR_ILLEGAL_ARGUMENT;
-  Ctx* c;
-  CHK(tl_ctx(&c));
-  BatchGuard g{c, {}};
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
   int32_t in = -1, opt = -1;
-  CHK(ctx_load(c, bufs, lens, n, &in));
-  g.ids.push_back(in);
+  CHK(os.load(bufs, lens, n, &in));
   CHK(ctx_run_optimize(c, in, &opt, answers));
-  g.ids.push_back(opt);
+  os.adopt(opt);
   for (size_t i = 0; i < n; i++) {
     outs[i] = rbg_buffer{};
     const int st = ctx_batch_fetch(c, opt, i, &outs[i]);
@@ -4138,12 +4068,14 @@ int rbg_run_optimize_many(const uint8_t* const* bufs, const size_t* lens, size_t
 }
 
 int rbg_ctx_run_optimize(rbg_ctx* ctx, int32_t batch, int32_t* out_batch, uint8_t* answers) {
-  if (!ctx || !out_batch) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(enter(&ctx->c));
-  return ctx_run_optimize(&ctx->c, batch, out_batch, answers);
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!out_batch) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_run_optimize(c, batch, out_batch, answers);
 }
 
 int rbg_ctx_batch_minmax(rbg_ctx* ctx, int32_t batch, int32_t* out2) {
+  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
   Batch* b;
   CHK(get_batch(&ctx->c, batch, &b));
   if (!out2) return RBG_ERR_ILLEGAL_ARGUMENT;
@@ -4153,8 +4085,8 @@ int rbg_ctx_batch_minmax(rbg_ctx* ctx, int32_t batch, int32_t* out2) {
 }
 
 int rbg_ctx_synth(rbg_ctx* ctx, int kind, uint64_t seed, size_t n, int key_lo, int key_hi, int32_t* batch) {
-  Ctx* c = &ctx->c;
-  CHK(enter(c));
+  Ctx* c;
+  CHK(session(ctx, &c));
   if (kind == 4) return synth_c5(c, seed, n, key_lo, key_hi, batch);
   if (kind == 1 || kind == 2) return synth_c3(c, kind, seed, n, key_lo, key_hi, batch);
   if (kind == 3) return synth_c4(c, seed, n, batch);

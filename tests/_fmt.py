@@ -163,3 +163,17 @@ def sub_bitmap(buf, keep_keys):
     for i in sel:
         out += buf[int(offs[i]):int(offs[i] + lens[i])]
     return bytes(out)
+
+
+def repeat_run_container(vals, n_keys):
+    """The serialized bitmap whose keys 0 .. n_keys - 1 (n_keys >= 4) each hold the run container of
+    `vals`: the payload is encoded once and repeated (encode() of many long run containers is slow)."""
+    assert 4 <= n_keys <= 65536
+    payload = encode([(0, R, vals)])[4 + 1 + 4:]  # cookie, one flag byte, one descriptor; no offset table
+    header = 4 + (n_keys + 7) // 8 + 8 * n_keys
+    keys = np.arange(n_keys, dtype="<u2")
+    desc = np.stack([keys, np.full(n_keys, len(vals) - 1, dtype="<u2")], axis=1)
+    offs = (header + len(payload) * np.arange(n_keys)).astype("<u4")
+    flags = np.packbits(np.ones(n_keys, dtype=np.uint8), bitorder="little")
+    return (struct.pack("<I", 12347 | ((n_keys - 1) << 16)) + flags.tobytes() + desc.tobytes() + offs.tobytes() +
+            payload * n_keys)

@@ -190,3 +190,27 @@ def test_priorityqueue_many_bitmaps_wide_keys(gpu, n):
         bufs.append(O.from_values(v.ravel(), i % 7 == 0))
     for op in ("priorityqueue_or", "priorityqueue_xor"):
         assert _wide(op, bufs) == O.wide(op, bufs), op
+
+
+def test_buffer_naive_and_overflows_the_arena_once(gpu):
+    """BufferFastAggregation.naive_and of two bitmaps whose 300 keys each AND into a run container of 16,384
+    one-value runs (65,538 B each, 19.7 MB in all), on a fresh session, whose big-run arena starts at
+    16 MiB: the first pass overflows, the arena grows to what that pass counted and the op runs once
+    more.  Then a 1-key batch on the same session: the runner's state after a grow."""
+    from roaringbitmap_amd import Engine
+    from _fmt import container_table, repeat_run_container
+    ev = lambda ph: np.sort(np.concatenate([np.arange(ph, 65536, 4), np.arange(1 + ph, 65536, 4)]))
+    bufs = [repeat_run_container(ev(0), 300), repeat_run_container(ev(1), 300)]
+    e = Engine(0)
+    batch = e.load(bufs)
+    e.wide("buffer_naive_and", batch, ids=[0, 1])
+    got = e.fetch().serialize()
+    assert got == O.wide("buffer_naive_and", bufs, [0, 1])
+    _, kinds, cards, _, lens = container_table(got)
+    assert len(kinds) == 300 and (kinds == R).all() and (lens == 65538).all()
+    assert len(got) > 16 << 20  # more than the arena a fresh session starts with: the first pass overflowed
+    one = [encode([(7, R, ev(0))]), encode([(7, R, ev(1))])]
+    b1 = e.load(one)
+    e.wide("buffer_naive_and", b1, ids=[0, 1])
+    assert e.fetch().serialize() == O.wide("buffer_naive_and", one, [0, 1])
+    e.close()

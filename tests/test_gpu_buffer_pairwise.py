@@ -87,3 +87,27 @@ def test_mutable_in_place(gpu):
     # the static forms on the Mutable class are the Immutable ones
     assert getattr(rb.MutableRoaringBitmap, "and")(rb.RoaringBitmap(a), rb.RoaringBitmap(b)).serialize() == \
         O.pairwise("and_buf", a, b)
+
+
+def test_run_results_overflow_the_arena_once(gpu):
+    """300 keys of R AND R into 16,384 one-value runs (65,538 B each, 19.7 MB in all) on a fresh session,
+    whose big-run arena starts at 16 MiB (257 such containers already pass it): the first pass overflows,
+    the arena grows to what that pass counted and the op runs once more.  Then a 1-key pair on the same
+    session: the runner's state after a grow."""
+    from roaringbitmap_amd import Engine
+    from _fmt import container_table, repeat_run_container
+    ev = lambda ph: np.sort(np.concatenate([np.arange(ph, 65536, 4), np.arange(1 + ph, 65536, 4)]))
+    a, b = repeat_run_container(ev(0), 300), repeat_run_container(ev(1), 300)
+    e = Engine(0)
+    ia, ib = e.load_pair(a, b)
+    e.pairwise("and_buffer", ia, ib)
+    got = e.fetch().serialize()
+    assert got == O.pairwise("and_buf", a, b)
+    _, kinds, cards, _, lens = container_table(got)
+    assert len(kinds) == 300 and (kinds == R).all() and (lens == 65538).all()
+    assert len(got) > 16 << 20  # more than the arena a fresh session starts with: the first pass overflowed
+    a1, b1 = encode([(7, R, ev(0))]), encode([(7, R, ev(1))])
+    ja, jb = e.load_pair(a1, b1)
+    e.pairwise("and_buffer", ja, jb)
+    assert e.fetch().serialize() == O.pairwise("and_buf", a1, b1)
+    e.close()

@@ -289,3 +289,23 @@ def test_in_place_range_forms_dispatch():
 def test_contains_subset_op_code():
     import roaringbitmap_amd._lib as L
     assert L.CARD_OP["contains"] == 5
+
+
+def _null_handle_calls():
+    return sorted(n for n in L.EXPORTED if n.startswith("rbg_ctx_") and n != "rbg_ctx_create")
+
+
+@pytest.mark.parametrize("name", _null_handle_calls())
+def test_session_entry_points_refuse_a_null_handle(name):
+    """Every session entry point answers a null rbg_ctx* with RBG_ERR_ILLEGAL_ARGUMENT before it touches
+    anything (no device call, so this runs without a GPU); rbg_ctx_stream gives null, rbg_ctx_destroy
+    does nothing."""
+    fn = getattr(L.lib(), name)
+    assert fn.argtypes[0] is ctypes.c_void_p, name  # the handle comes first
+    zeros = [None if t in (ctypes.c_void_p, ctypes.c_char_p) or issubclass(t, ctypes._Pointer) else 0
+             for t in fn.argtypes[1:]]
+    got = fn(None, *zeros)
+    if name in ("rbg_ctx_stream", "rbg_ctx_destroy"):
+        assert got is None
+    else:
+        assert got == L.RBG_ERR_ILLEGAL_ARGUMENT, (name, got)
