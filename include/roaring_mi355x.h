@@ -274,6 +274,20 @@ int rbg_bsi_compare_buffer(int op, int32_t start, int32_t end, const uint8_t* eb
 /* sum(foundSet) -> Pair<Long, Long> (RoaringBitmapSliceIndex.java:581-592): out2 = {sum, count}. */
 int rbg_bsi_sum(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
                 size_t nbits, const uint8_t* found, size_t found_len, int64_t* out2);
+/* setValue(columnId, value) for each of n pairs (RoaringBitmapSliceIndex.java:299-347) [+ runOptimize(),
+ * :141-150], built on the device: outs[0] = ebM, outs[1 + i] = bA[i] as portable bytes (outs must have
+ * room for 33 buffers; 1 + nbits are written, each released with rbg_free), out3 = {nbits, minValue,
+ * maxValue}.  The pairs may come in any order.  A negative value or a column given more than once (setValue
+ * would overwrite: the last pair wins, which needs the order) is RBG_ERR_ILLEGAL_ARGUMENT.  n == 0 gives
+ * the empty ebM alone and out3 = {0, 0, 0}. */
+int rbg_bsi_from_columns(const uint32_t* columns, const int32_t* values, size_t n, int run_optimize, rbg_buffer* outs,
+                         int32_t* out3);
+/* getValue(columnId) (RoaringBitmapSliceIndex.java:181-196) for n columns at once, the loop of the
+ * buffer package's batchIn / transposeWithCount (BitSliceIndexBase.java:551-639): out[i] = the value of
+ * columns[i], -1 where ebM lacks it (valueExist, BitSliceIndexBase.java:82).  The columns need not be
+ * sorted or distinct. */
+int rbg_bsi_get_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
+                       int nbits, const uint32_t* columns, size_t n, int64_t* out);
 
 /* Releases an output.  Large results (>= 8 MiB, 2 MiB-aligned huge-page buffers) are kept for
  * reuse by the next large result, at most two of them, so a caller's steady stream of big results
@@ -475,6 +489,43 @@ int rbg_ctx_to_values(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uin
  * on return (from the batch's cardinality). */
 int rbg_ctx_to_values_device(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t count, int out64,
                              void* out_dev, uint64_t* n_out);
+/* RoaringBitmapSliceIndex.setValue for each of n pairs (bsi/.../RoaringBitmapSliceIndex.java:299-347:
+ * ensureCapacityInternal's min / max and bit count, ebM.add, one add per set bit of the value) [+
+ * runOptimize(), :141-150], on the device: a new key-major batch [ebM, bA[0], ..., bA[nbits - 1]], the
+ * batch rbg_ctx_load of those bitmaps gives, ready for rbg_ctx_bsi / rbg_ctx_bsi_buffer.  out3 = {nbits,
+ * minValue, maxValue}.  columns (uint32) and values (int32) are host arrays, in any order.  A negative
+ * value or a column given more than once: RBG_ERR_ILLEGAL_ARGUMENT, no batch is made.  n == 0: a batch of
+ * the empty ebM alone, out3 = {0, 0, 0}.  The workspace (one 8 KiB bitmap per present key and input) is
+ * walked in passes under a byte budget (1 GiB; RBG_BSI_BUILD_WS=<bytes>, read at every call, overrides it).
+ * Synchronous. */
+int rbg_ctx_bsi_from_columns(rbg_ctx* ctx, const uint32_t* columns, const int32_t* values, size_t n, int run_optimize,
+                             int32_t* batch, int32_t* out3);
+/* The same from device memory; whatever produced the pairs must be ordered before the context stream, and
+ * they must not change until the call returns (every pass reads them). */
+int rbg_ctx_bsi_from_columns_device(rbg_ctx* ctx, const void* columns_dev, const void* values_dev, size_t n,
+                                    int run_optimize, int32_t* batch, int32_t* out3);
+/* RoaringBitmapSliceIndex.getValue (RoaringBitmapSliceIndex.java:181-196) for n columns against a batch
+ * [ebM, bA[0..nbits-1], foundSet?] (has_found: the batch ends with a foundSet, which is ignored), the
+ * loop of the buffer package's batchIn / transposeWithCount (buffer/BitSliceIndexBase.java:551-639):
+ * out[i] = the value of columns[i], -1 where ebM lacks it (valueExist, :82).  Any order, repeats allowed.
+ * Returns after the values are in out. */
+int rbg_ctx_bsi_get_values(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const uint32_t* columns, size_t n,
+                           int64_t* out);
+/* The same with columns (uint32) and out (int64) in device memory, enqueued on the context stream with no
+ * host synchronisation. */
+int rbg_ctx_bsi_get_values_device(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const void* columns_dev,
+                                  size_t n, void* out_dev);
+/* BitSliceIndexBase.toPairList() (buffer/BitSliceIndexBase.java:534-549): every column of ebM, ascending
+ * and unsigned, into columns_out (uint32, or int64 zero-extended with columns64) and its value into
+ * values_out (int32, or int64 with values64), host memory with room for cardinality(ebM) entries each;
+ * *n_out (nullable) = the pairs.  Both outputs null with n_out given: only *n_out is computed (no device
+ * work).  Returns after the pairs are written. */
+int rbg_ctx_bsi_to_pairs(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int columns64, int values64,
+                         void* columns_out, void* values_out, uint64_t* n_out);
+/* The same into device memory, enqueued on the context stream with no host synchronisation; *n_out is
+ * known on return (from the batch's cardinalities). */
+int rbg_ctx_bsi_to_pairs_device(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int columns64, int values64,
+                                void* columns_dev, void* values_dev, uint64_t* n_out);
 /* Retired diagnostic (the per-phase clock builds of rounds 2-5 are gone; their results are in
  * profiles/): writes 20 zeros.  Kept so bindings of earlier rounds still link. */
 int rbg_debug_stamps(uint64_t* out20, int reset);

@@ -54,6 +54,8 @@ EXPORTED = [
     "rbg_point_query", "rbg_ctx_point_query", "rbg_ctx_point_query_device",
     "rbg_build_values", "rbg_expand_values", "rbg_ctx_from_values", "rbg_ctx_from_values_device",
     "rbg_ctx_to_values", "rbg_ctx_to_values_device",
+    "rbg_bsi_from_columns", "rbg_bsi_get_values", "rbg_ctx_bsi_from_columns", "rbg_ctx_bsi_from_columns_device",
+    "rbg_ctx_bsi_get_values", "rbg_ctx_bsi_get_values_device", "rbg_ctx_bsi_to_pairs", "rbg_ctx_bsi_to_pairs_device",
 ]
 
 _lib = None
@@ -94,6 +96,15 @@ def _declare(L):
     L.rbg_ctx_from_values_device.argtypes = [vp, vp, sz, ctypes.c_int, P(i32)]
     L.rbg_ctx_to_values.argtypes = [vp, i32, sz, u64, u64, P(ctypes.c_uint32), P(u64)]
     L.rbg_ctx_to_values_device.argtypes = [vp, i32, sz, u64, u64, ctypes.c_int, vp, P(u64)]
+    u32p, i32p, i64p, ci = P(ctypes.c_uint32), P(i32), P(ctypes.c_int64), ctypes.c_int
+    L.rbg_bsi_from_columns.argtypes = [u32p, i32p, sz, ci, vp, i32p]
+    L.rbg_bsi_get_values.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, u32p, sz, i64p]
+    L.rbg_ctx_bsi_from_columns.argtypes = [vp, u32p, i32p, sz, ci, i32p, i32p]
+    L.rbg_ctx_bsi_from_columns_device.argtypes = [vp, vp, vp, sz, ci, i32p, i32p]
+    L.rbg_ctx_bsi_get_values.argtypes = [vp, i32, ci, ci, u32p, sz, i64p]
+    L.rbg_ctx_bsi_get_values_device.argtypes = [vp, i32, ci, ci, vp, sz, vp]
+    L.rbg_ctx_bsi_to_pairs.argtypes = [vp, i32, ci, ci, ci, ci, vp, vp, P(u64)]
+    L.rbg_ctx_bsi_to_pairs_device.argtypes = [vp, i32, ci, ci, ci, ci, vp, vp, P(u64)]
     L.rbg_select_range.argtypes = [u8p, sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, buf]
     L.rbg_ctx_add_offset.argtypes = [vp, i32, sz, ctypes.c_int64]
     L.rbg_ctx_select_range.argtypes = [vp, i32, ctypes.c_int64, ctypes.c_int64, P(i32)]

@@ -7,7 +7,9 @@ MutableBitSliceIndex (bsi/src/main/java/org/roaringbitmap/bsi/buffer/BitSliceInd
 BBSI/): compare (BBSI/:422-453), rangeEQ / rangeNEQ / rangeLT / rangeLE / rangeGT / rangeGE /
 range (BBSI/:351-408) and sum (BBSI/:521-532).  Every query runs on the MI355X
 (csrc/bsi.hip) and the results are the reference's bytes, container types included.
-Construction (setValue) is host-side.
+Construction (setValue) is host-side by default; from_columns(..., gpu=True) builds the slices on the
+device (csrc/bsibuild.hip), and getValues / toPairList read values back in bulk (csrc/bsival.hip with
+gpu=True).
 """
 import ctypes
 
@@ -31,14 +33,30 @@ class RoaringBitmapSliceIndex:
         self.runOptimized = False
 
     @classmethod
-    def from_columns(cls, columns, values, run_optimize=False):
-        """setValue(c, v) for each pair, in order (BSI/:320-347); runOptimize() if asked (BSI/:141-150)."""
+    def from_columns(cls, columns, values, run_optimize=False, gpu=False):
+        """setValue(c, v) for each pair, in order (BSI/:320-347); runOptimize() if asked (BSI/:141-150).
+        gpu=True: the same object from the one-shot device build (rbg_bsi_from_columns, csrc/bsibuild.hip),
+        which takes the pairs in any order but refuses a repeated column (setValue would overwrite)."""
         columns = np.asarray(columns, dtype=np.int64)
         values = np.asarray(values, dtype=np.int64)
         if columns.shape != values.shape:
             raise IllegalArgumentException("columns and values differ in length")
         if (values < 0).any():
             raise IllegalArgumentException("Values should be non-negative")
+        if gpu:
+            if values.size and int(values.max()) >= 1 << 31:
+                raise IllegalArgumentException("Values should be below 2^31")
+            c = np.ascontiguousarray(columns.reshape(-1).astype(np.uint32))
+            v = np.ascontiguousarray(values.reshape(-1).astype(np.int32))
+            outs = (_lib.rbg_buffer * 33)()
+            out3 = (ctypes.c_int32 * 3)()
+            check(lib().rbg_bsi_from_columns(c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                             v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size,
+                                             int(bool(run_optimize)), outs, out3))
+            bms = [RoaringBitmap(take(outs[k])) for k in range(1 + int(out3[0]))]
+            obj = cls(bms[0], bms[1:], int(out3[1]), int(out3[2]))
+            obj.runOptimized = bool(run_optimize)
+            return obj
         mn = mx = 0
         if values.size:  # ensureCapacityInternal: first value sets both, then min or else max
             mn = mx = int(values[0])
@@ -89,6 +107,44 @@ class RoaringBitmapSliceIndex:
             if b.contains(columnId):
                 v |= 1 << i
         return v, True
+
+    def valueExist(self, columnId):
+        """BBSI/:82 valueExist(columnId): ebM.contains(columnId)"""
+        return self.ebM.contains(columnId)
+
+    def getValues(self, columns, gpu=False):
+        """getValue for many columns at once, the loop body of the buffer package's batchIn /
+        transposeWithCount (BBSI/:551-639): an int64 array in query order, -1 where ebM lacks the column
+        (getValue's exists == false).  The columns need not be sorted or distinct.  Host default: numpy
+        membership tests against toArray() of ebM and of every slice; gpu=True: one batched lookup on the
+        device (rbg_bsi_get_values, csrc/bsival.hip)."""
+        q = np.ascontiguousarray(np.asarray(columns, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        if gpu:
+            out = np.empty(q.size, dtype=np.int64)
+            if q.size:
+                arr, lens = self._slices()
+                e = self.ebM.serialize()
+                check(lib().rbg_bsi_get_values(e, len(e), arr, lens, len(self.bA),
+                                               q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), q.size,
+                                               out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+            return out
+        v = np.zeros(q.size, dtype=np.int64)
+        for i, b in enumerate(self.bA):
+            v |= np.isin(q, b.toArray()).astype(np.int64) << i
+        return np.where(np.isin(q, self.ebM.toArray()), v, -1)
+
+    def toPairList(self, foundSet=None, gpu=False):
+        """BBSI/:534-549 toPairList() / toPairList(foundSet) -> (columns, values): the columns of ebM, or of
+        and(ebM, foundSet), ascending and unsigned (uint32), and their values (int64) from the batched
+        lookup.  Host default: numpy over toArray() and getValues; gpu=True: the intersection, the expansion
+        and the lookup run on the device."""
+        if foundSet is None:
+            cols = self.ebM.toArray(gpu=gpu)
+        elif gpu:
+            cols = RoaringBitmap.and_(self.ebM, foundSet).toArray(gpu=True)
+        else:
+            cols = np.intersect1d(self.ebM.toArray(), foundSet.toArray())
+        return cols, self.getValues(cols, gpu=gpu)
 
     def runOptimize(self):
         """BSI/:141-150: runOptimize of ebM and of every slice (one device pass over all of them)."""

@@ -182,6 +182,10 @@ struct Ctx {
   DevBuf pt_q, pt_out;    // point queries from host memory: the queries and results on the device
   DevBuf bld_info, bld_size, bld_part;  // construction from values (build.hip): the plan's table, slot sizes, scan
   DevBuf tv_out;                        // expansion to host memory: one window of values on the device
+  // a BSI batch from (column, value) pairs (bsibuild.hip): the present keys and their CSR, the plan's cell
+  // table, the cells' size words (scanned in place) and scan scratch, the per-input totals
+  DevBuf bsib_pkeys, bsib_pkoff, bsib_info, bsib_size, bsib_part, bsib_per;
+  DevBuf bsiv_cards, bsiv_part;  // toPairList (bsival.hip): ebM's cardinality per key (scanned in place)
   DevBuf gather_items, gather_out;  // batch fetch: slot gather list and download buffer
   DevBuf order;                     // horizontal_*: chain order of every key segment
   DevBuf ro_info, ro_size, ro_part;  // range selection scratch (kept: no allocation per call)
@@ -1135,6 +1139,267 @@ static int ctx_from_values_host(Ctx* c, const uint32_t* v, size_t n, bool run_op
   const int st = ctx_from_values(c, in.as<uint32_t>(), n, run_opt, out_id);
   pool_put(c, in);
   return st;
+}
+
+// n 32-bit words from host memory into dst (device), through the context's pinned buffer, a chunk at a time
+static int upload_words(Ctx* c, void* dst, const void* src, size_t n) {
+  constexpr size_t kChunk = 16u << 20;  // words per staged copy (64 MiB)
+  if (!n) return RBG_OK;
+  CHK(pinned_ensure(c, 4 * std::min(n, kChunk)));
+  HIPCHK(hipStreamSynchronize(c->stream));  // nothing enqueued earlier still reads the staging buffer
+  for (size_t off = 0; off < n; off += kChunk) {
+    const size_t m = std::min(kChunk, n - off);
+    std::memcpy(c->pinned, reinterpret_cast<const uint32_t*>(src) + off, 4 * m);
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<uint32_t*>(dst) + off, c->pinned, 4 * m, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return RBG_OK;
+}
+
+// Workspace bytes of one pass of the BSI build (bsibuild.hip).  RBG_BSI_BUILD_WS=<bytes> overrides the
+// default, read at every call (tests force several passes at small shapes); a pass always holds at least
+// one key's m bitmaps and stays below 2^31 words.
+constexpr size_t kBsibBudget = 1ull << 30;  // a released workspace of this size still goes to the pool (kPoolMaxBuf)
+static size_t bsib_budget() {
+  const char* e = std::getenv("RBG_BSI_BUILD_WS");
+  const unsigned long long v = e ? std::strtoull(e, nullptr, 10) : 0;
+  return (size_t)std::min<unsigned long long>(v ? v : kBsibBudget, 4ull << 30);
+}
+
+// A bit-sliced index from n (column, value) pairs in device memory (u32 columns, all distinct; i32 values,
+// none negative; any order) as a new key-major batch [ebM, bA[0..nbits-1]]: setValue for every pair
+// (BSI/:299-347: ensureCapacityInternal's min / max and bit count, then ebM.add and one add per set bit),
+// with run_opt followed by runOptimize() (BSI/:141-150) -- the batch ctx_load of the host builder's
+// bitmaps gives (bsibuild.hip).  out3 = {nbits, minValue, maxValue}.  Two read-backs: the key count with
+// min / max (a negative value is refused here), then the per-input totals (a repeated column shows as
+// cardinality(ebM) != n and is refused before anything is allocated for the batch).
+// The K x (nbits + 1) bitmaps of the workspace are walked in passes of whole keys under bsib_budget().  One
+// pass: scatter, plan, scan, write from the same workspace.  Several passes: a first sweep scatters and plans
+// every pass (sizes alone), the scan places every container, and a second sweep scatters again and writes
+// -- the payload is allocated once at its exact size.  The pairs are read by every scatter:
+// they must not change until the call returns.
+static int ctx_bsi_from_columns(Ctx* c, const uint32_t* col_dev, const int32_t* val_dev, size_t n, bool run_opt,
+                                int32_t* out_id, int32_t* out3) {
+  hipStream_t s = c->stream;
+  out3[0] = out3[1] = out3[2] = 0;
+  if (n == 0) return ctx_from_values(c, nullptr, 0, run_opt, out_id);  // one empty bitmap: ebM, no slice
+  if (n > (1ull << 32)) {
+    set_err("bsi_from_columns: more pairs than columns");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
+  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
+  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] {min, max} as two i32
+  static const int kMinMaxInit[2] = {INT32_MAX, INT32_MIN};
+  HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
+  HIPCHK(hipMemsetAsync(sc, 0, 64, s));
+  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxInit, 8, hipMemcpyHostToDevice, s));
+  launch_bld_keys(s, col_dev, n, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
+  launch_bsib_minmax(s, val_dev, n, reinterpret_cast<int*>(sc + 1));
+  HIPCHK(hipGetLastError());
+  unsigned long long h[2] = {};
+  HIPCHK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const size_t K = (size_t)h[0];
+  const int32_t mn = (int32_t)(uint32_t)h[1], mx = (int32_t)(uint32_t)(h[1] >> 32);
+  if (mn < 0) {
+    set_err("Values should be non-negative");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  const int nbits = mx ? 32 - __builtin_clz((uint32_t)mx) : 1;  // Integer.toBinaryString(max).length()
+  const int m = nbits + 1;
+  const size_t cells = K * (size_t)m;
+  dbg(s, "bsi_from_columns: keys + min / max");
+  CHK(c->bsib_info.ensure(kBsibInfoBytes * cells));
+  CHK(c->bsib_size.ensure(8 * (cells + 1)));
+  CHK(c->bsib_part.ensure(8 * (scan_parts(cells) + 1)));
+  CHK(c->bsib_per.ensure(8 * (4 * (size_t)m + 4)));
+  uint64_t* size = c->bsib_size.as<uint64_t>();
+  unsigned long long* per = c->bsib_per.as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
+  const size_t P = std::min(K, std::max<size_t>(1, bsib_budget() / (8192 * (size_t)m)));  // keys per pass
+  DevBuf ws;  // back to the pool at the end (freed on an error)
+  CHK(pool_take(c, ws, 8192 * (size_t)m * P));
+  bool precheck = kBldPrecheck;  // RBG_BLD_PRECHECK as in ctx_from_values
+  if (const char* e = std::getenv("RBG_BLD_PRECHECK")) precheck = e[0] == '1';
+  auto scatter = [&](size_t k_lo, size_t k_hi) -> int {
+    HIPCHK(hipMemsetAsync(ws.p, 0, 8192 * (size_t)m * (k_hi - k_lo), s));
+    launch_bsib_scatter(s, col_dev, val_dev, n, c->bsib_pkoff.as<uint32_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m,
+                        ws.as<uint32_t>(), precheck);
+    return RBG_OK;
+  };
+  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+    const size_t k_hi = std::min(K, k_lo + P);
+    CHK(scatter(k_lo, k_hi));
+    launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, run_opt ? 1 : 0, c->bsib_info.p, size, per,
+                     per + 4 * m);
+  }
+  launch_exclusive_scan(s, size, size, cells, c->bsib_part.as<uint64_t>(), size + cells);
+  HIPCHK(hipGetLastError());
+  std::vector<unsigned long long> hp(4 * (size_t)m + 4);
+  uint64_t total = 0;
+  HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&total, size + cells, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  dbg(s, "bsi_from_columns: scatter + plan");
+  if (hp[1] != n) {  // setValue overwrites: a column given twice would need the pairs' order
+    set_err("bsi_from_columns: a column is given more than once");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  const size_t C = (size_t)(total >> kBsibCountShift);
+  const int32_t id = new_batch(c);
+  Batch& b = *c->batches[id];
+  BatchGuard guard{c, {id}};  // dropped unless the build completes
+  b.payload_bytes = (size_t)(total & ((1ull << kBsibCountShift) - 1));
+  CHK(pool_take(c, b.keys, 2 * C + 16));
+  CHK(pool_take(c, b.desc, sizeof(CDesc) * C + 16));
+  CHK(pool_take(c, b.bm, 4 * C + 16));
+  CHK(pool_take(c, b.key_off, 4 * (kMaxKeys + 1)));
+  CHK(pool_take(c, b.bm_off, 4 * ((size_t)m + 1)));
+  CHK(pool_take(c, b.payload, b.payload_bytes + 64));
+  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+    const size_t k_hi = std::min(K, k_lo + P);
+    if (P < K) CHK(scatter(k_lo, k_hi));  // several passes: the workspace held another pass since the plan
+    launch_bsib_write(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, c->bsib_info.p, size,
+                      c->bsib_pkeys.as<uint16_t>(), b.desc.as<CDesc>(), b.keys.as<uint16_t>(), b.bm.as<uint32_t>(),
+                      b.payload.as<uint8_t>());
+  }
+  launch_bsib_key_off(s, c->bsib_pkoff.as<uint32_t>(), size, m, b.key_off.as<uint32_t>());
+  HIPCHK(hipGetLastError());
+  pool_put(c, ws);  // whatever takes it next is enqueued on this stream, after the write kernels
+  b.n_bm = (size_t)m;
+  b.n_ctr = C;
+  b.key_major = true;
+  for (int k = 0; k < 3; k++) b.n_kind[k] = (int64_t)hp[4 * m + k];
+  b.max_ser = 0;  // no container above kStagedMax serialized bytes
+  b.h_bm_off.assign(m + 1, 0);
+  b.h_bm_nctr.resize(m);
+  b.h_bm_card.resize(m);
+  b.h_has_run.resize(m);
+  for (int i = 0; i < m; i++) {
+    b.h_bm_nctr[i] = (uint32_t)hp[4 * i];
+    b.h_bm_off[i + 1] = b.h_bm_off[i] + b.h_bm_nctr[i];
+    b.h_bm_card[i] = (int64_t)hp[4 * i + 1];
+    b.h_has_run[i] = hp[4 * i + 3] != 0;
+    b.long_card += b.h_bm_card[i];
+    b.ser_bytes += (int64_t)(header_size(b.h_bm_nctr[i], b.h_has_run[i] != 0) + hp[4 * i + 2]);
+  }
+  HIPCHK(hipMemcpyAsync(b.bm_off.p, b.h_bm_off.data(), 4 * ((size_t)m + 1), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  dbg(s, "bsi_from_columns: write");
+  guard.ids.clear();
+  b.live = true;
+  *out_id = id;
+  out3[0] = nbits;
+  out3[1] = mn;
+  out3[2] = mx;
+  return RBG_OK;
+}
+
+// the same from host memory: the pairs go to the device through the context's pinned buffer
+static int ctx_bsi_from_columns_host(Ctx* c, const uint32_t* col, const int32_t* val, size_t n, bool run_opt,
+                                     int32_t* out_id, int32_t* out3) {
+  DevBuf dc, dv;
+  CHK(pool_take(c, dc, 4 * n + 16));
+  CHK(pool_take(c, dv, 4 * n + 16));
+  CHK(upload_words(c, dc.p, col, n));
+  CHK(upload_words(c, dv.p, val, n));
+  const int st = ctx_bsi_from_columns(c, dc.as<uint32_t>(), dv.as<int32_t>(), n, run_opt, out_id, out3);
+  pool_put(c, dc);
+  pool_put(c, dv);
+  return st;
+}
+
+// A batch as the operand of the BSI read-outs (bsival.hip): key-major [ebM, nbits slices, foundSet?]
+static int bsi_val_operand(Ctx* c, int32_t id, int nbits, int has_found, Batch** B, BsiValArgs* a) {
+  CHK(get_batch(c, id, B));
+  const Batch* b = *B;
+  if (!b->key_major || b->packed || nbits < 0 || nbits + 2 > kBsiMaxInputs ||
+      b->n_bm != (size_t)(1 + nbits + (has_found ? 1 : 0))) {
+    set_err("bsi values: batch must hold ebM, nbits slices and the optional foundSet");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  *a = BsiValArgs{b->key_off.as<uint32_t>(), b->desc.as<CDesc>(), b->bm.as<uint32_t>(), b->payload.as<uint8_t>(), nbits};
+  return RBG_OK;
+}
+
+// getValue (BSI/:181-196) of n columns (device memory, u32, any order, repeats allowed) into out (device
+// memory, i64; -1: ebM lacks the column), in query order, enqueued on the context stream
+static int ctx_bsi_get_values(Ctx* c, int32_t batch, int nbits, int has_found, const uint32_t* q_dev, size_t n,
+                              long long* out_dev) {
+  Batch* B;
+  BsiValArgs a;
+  CHK(bsi_val_operand(c, batch, nbits, has_found, &B, &a));
+  launch_bsi_get_values(c->stream, a, q_dev, n, out_dev);
+  HIPCHK(hipGetLastError());
+  return RBG_OK;
+}
+
+// the same from host memory: staged through the context's pinned buffer, results in out on return
+static int ctx_bsi_get_values_host(Ctx* c, int32_t batch, int nbits, int has_found, const uint32_t* q, size_t n,
+                                   int64_t* out) {
+  CHK(pinned_ensure(c, 12 * n + 64));
+  CHK(c->pt_q.ensure(4 * n));
+  CHK(c->pt_out.ensure(8 * n));
+  uint8_t* pin = reinterpret_cast<uint8_t*>(c->pinned);
+  hipStream_t s = c->stream;
+  HIPCHK(hipStreamSynchronize(s));  // nothing enqueued earlier still reads the staging buffer
+  std::memcpy(pin + 8 * n, q, 4 * n);
+  HIPCHK(hipMemcpyAsync(c->pt_q.p, pin + 8 * n, 4 * n, hipMemcpyHostToDevice, s));
+  CHK(ctx_bsi_get_values(c, batch, nbits, has_found, c->pt_q.as<uint32_t>(), n, c->pt_out.as<long long>()));
+  HIPCHK(hipMemcpyAsync(pin, c->pt_out.p, 8 * n, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  std::memcpy(out, pin, 8 * n);
+  return RBG_OK;
+}
+
+// toPairList() (BBSI/:534-549): every column of ebM, ascending and unsigned, into cols_dev (u32, or i64
+// with cols64) with its value in vals_dev (i32, or i64 with vals64), enqueued on the context stream.
+// *n_out: the pairs, known here from ebM's cardinality; no buffers with n_out: the size alone.
+static int ctx_bsi_to_pairs(Ctx* c, int32_t batch, int nbits, int has_found, bool cols64, bool vals64, void* cols_dev,
+                            void* vals_dev, uint64_t* n_out) {
+  Batch* B;
+  BsiValArgs a;
+  CHK(bsi_val_operand(c, batch, nbits, has_found, &B, &a));
+  const uint64_t total = B->h_bm_card.empty() ? 0 : (uint64_t)B->h_bm_card[0];
+  if (n_out) *n_out = total;
+  if (!total || (!cols_dev && !vals_dev && n_out)) return RBG_OK;
+  if (!cols_dev || !vals_dev) {
+    set_err("bsi_to_pairs: no output buffer");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  CHK(c->bsiv_cards.ensure(8 * (kMaxKeys + 1)));
+  CHK(c->bsiv_part.ensure(8 * (scan_parts(kMaxKeys) + 1)));
+  uint64_t* cards = c->bsiv_cards.as<uint64_t>();
+  launch_bsi_pair_cards(c->stream, a, cards);
+  launch_exclusive_scan(c->stream, cards, cards, kMaxKeys, c->bsiv_part.as<uint64_t>(), cards + kMaxKeys);
+  launch_bsi_pairs(c->stream, a, cards, cols64, vals64, cols_dev, vals_dev);
+  HIPCHK(hipGetLastError());
+  return RBG_OK;
+}
+
+// the same into host memory: both arrays on the device first, then one copy each
+static int ctx_bsi_to_pairs_host(Ctx* c, int32_t batch, int nbits, int has_found, bool cols64, bool vals64, void* cols,
+                                 void* vals, uint64_t* n_out) {
+  uint64_t total = 0;
+  CHK(ctx_bsi_to_pairs(c, batch, nbits, has_found, cols64, vals64, nullptr, nullptr, &total));  // operand check, size
+  if (n_out) *n_out = total;
+  if (!total || (!cols && !vals && n_out)) return RBG_OK;
+  if (!cols || !vals) {
+    set_err("bsi_to_pairs: no output buffer");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  const size_t cb = (cols64 ? 8 : 4) * (size_t)total, vb = (vals64 ? 8 : 4) * (size_t)total;
+  DevBuf dc, dv;
+  CHK(pool_take(c, dc, cb));
+  CHK(pool_take(c, dv, vb));
+  CHK(ctx_bsi_to_pairs(c, batch, nbits, has_found, cols64, vals64, dc.p, dv.p, nullptr));
+  HIPCHK(hipMemcpyAsync(cols, dc.p, cb, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(vals, dv.p, vb, hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  pool_put(c, dc);
+  pool_put(c, dv);
+  return RBG_OK;
 }
 
 // op RBG_OR_INPLACE: x1.or(x2) in place (RB/RoaringBitmap.java:2481-2523), the OR with Container.ior's
@@ -3877,6 +4142,86 @@ int rbg_bsi_sum(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices
   CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
   CHK(ctx_bsi(c, id, BSI_SUM_ONLY, (int)nbits, 1, 0, 0, 0, 0, 1));
   return ctx_bsi_sums(c, out2);
+}
+
+/* ---- a BSI from (column, value) pairs (bsibuild.hip) and its values back (bsival.hip) ---- */
+
+int rbg_ctx_bsi_from_columns(rbg_ctx* ctx, const uint32_t* columns, const int32_t* values, size_t n, int run_optimize,
+                             int32_t* batch, int32_t* out3) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!batch || !out3 || (n && (!columns || !values))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_from_columns_host(c, columns, values, n, run_optimize != 0, batch, out3);
+}
+
+int rbg_ctx_bsi_from_columns_device(rbg_ctx* ctx, const void* columns_dev, const void* values_dev, size_t n,
+                                    int run_optimize, int32_t* batch, int32_t* out3) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!batch || !out3 || (n && (!columns_dev || !values_dev))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_from_columns(c, reinterpret_cast<const uint32_t*>(columns_dev),
+                              reinterpret_cast<const int32_t*>(values_dev), n, run_optimize != 0, batch, out3);
+}
+
+int rbg_ctx_bsi_get_values(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const uint32_t* columns, size_t n,
+                           int64_t* out) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (nbits < 0 || (n && (!columns || !out))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n == 0) return RBG_OK;
+  return ctx_bsi_get_values_host(c, batch, nbits, has_found, columns, n, out);
+}
+
+int rbg_ctx_bsi_get_values_device(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const void* columns_dev,
+                                  size_t n, void* out_dev) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (nbits < 0 || (n && (!columns_dev || !out_dev))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n == 0) return RBG_OK;
+  return ctx_bsi_get_values(c, batch, nbits, has_found, reinterpret_cast<const uint32_t*>(columns_dev), n,
+                            reinterpret_cast<long long*>(out_dev));
+}
+
+int rbg_ctx_bsi_to_pairs(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int columns64, int values64,
+                         void* columns_out, void* values_out, uint64_t* n_out) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (nbits < 0) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_to_pairs_host(c, batch, nbits, has_found, columns64 != 0, values64 != 0, columns_out, values_out,
+                               n_out);
+}
+
+int rbg_ctx_bsi_to_pairs_device(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int columns64, int values64,
+                                void* columns_dev, void* values_dev, uint64_t* n_out) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (nbits < 0) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_to_pairs(c, batch, nbits, has_found, columns64 != 0, values64 != 0, columns_dev, values_dev, n_out);
+}
+
+int rbg_bsi_from_columns(const uint32_t* columns, const int32_t* values, size_t n, int run_optimize, rbg_buffer* outs,
+                         int32_t* out3) {
+  if (!outs || !out3 || (n && (!columns || !values))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(ctx_bsi_from_columns_host(c, columns, values, n, run_optimize != 0, &id, out3));
+  os.adopt(id);
+  return ctx_batch_fetch_range(c, id, 0, 1 + (size_t)out3[0], outs);
+}
+
+int rbg_bsi_get_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
+                       int nbits, const uint32_t* columns, size_t n, int64_t* out) {
+  if (nbits < 0 || (n && (!columns || !out))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (!ebm || (nbits && (!slices || !slice_lens)) || nbits + 2 > kBsiMaxInputs) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (n == 0) return RBG_OK;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, (size_t)nbits, nullptr, 0, &id));
+  return ctx_bsi_get_values_host(c, id, nbits, 0, columns, n, out);
 }
 int rbg_debug_stamps(uint64_t* out20, int reset) {
   if (!out20) return RBG_ERR_ILLEGAL_ARGUMENT;

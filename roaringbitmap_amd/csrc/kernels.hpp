@@ -531,6 +531,46 @@ void launch_bld_plan(hipStream_t s, const uint8_t* ws, uint64_t n_ctr, int run_o
 void launch_bld_write(hipStream_t s, const uint8_t* ws, uint64_t n_ctr, const void* info, const uint64_t* off,
                       const uint16_t* keys, CDesc* desc, uint32_t* bm, uint32_t* bm_off, uint8_t* payload);
 
+// bsibuild.hip: the key-major batch [ebM, bA[0..nbits-1]] of a bit-sliced index from n (column, value)
+// pairs in device memory (RoaringBitmapSliceIndex.setValue, BSI/:299-347) [+ runOptimize].
+// mm: {min, max} of the values, set to {INT_MAX, INT_MIN} by the caller
+void launch_bsib_minmax(hipStream_t s, const int32_t* v, uint64_t n, int* mm);
+// One pass over the key indices [k_lo, k_hi) of the K present keys (pkey_off: launch_bld_keys' CSR over
+// the columns), m = nbits + 1 inputs.  ws: (k_hi - k_lo) x m bitmaps of 8 KiB, zeroed by the caller, below
+// 2^31 words.
+void launch_bsib_scatter(hipStream_t s, const uint32_t* col, const int32_t* val, uint64_t n, const uint32_t* pkey_off,
+                         uint32_t k_lo, uint32_t k_hi, int m, uint32_t* ws, bool precheck);
+constexpr size_t kBsibInfoBytes = 8;  // per (key index, input) cell: the plan's (card, nruns, kind)
+// a cell's size word: container count (0 / 1) << kBsibCountShift | slot bytes; one scan places both
+constexpr int kBsibCountShift = 40;
+// info / size: K x m cells (the pass fills its own); per (4 u64 per input: containers, cardinality,
+// serialized payload bytes, run containers) and kinds (3 u64) are added to: zeroed by the caller
+void launch_bsib_plan(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t k_hi, int m, int run_optimize,
+                      void* info, uint64_t* size, unsigned long long* per, unsigned long long* kinds);
+// scan: the exclusive scan of size[] over all K x m cells; pkeys: the K present keys
+void launch_bsib_write(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t k_hi, int m, const void* info,
+                       const uint64_t* scan, const uint16_t* pkeys, CDesc* desc, uint16_t* keys, uint32_t* bm,
+                       uint8_t* payload);
+// the batch's key CSR (65,537 entries); scan[K m] = the scan's total
+void launch_bsib_key_off(hipStream_t s, const uint32_t* pkey_off, const uint64_t* scan, int m, uint32_t* key_off);
+
+// bsival.hip: values out of a key-major batch [ebM, bA[0..nbits-1], foundSet?]
+struct BsiValArgs {
+  const uint32_t* key_off;  // the batch's key CSR (65,537 entries)
+  const CDesc* desc;
+  const uint32_t* bm;  // input index per container
+  const uint8_t* payload;
+  int nbits;
+};
+// out[i] = getValue(q[i]) (BSI/:181-196), -1 where ebM lacks the column; in query order
+void launch_bsi_get_values(hipStream_t s, BsiValArgs a, const uint32_t* q, uint64_t n, long long* out);
+// cards[k] = cardinality of ebM's container of key k (65,536 u64), to be scanned (launch_exclusive_scan)
+void launch_bsi_pair_cards(hipStream_t s, BsiValArgs a, uint64_t* cards);
+// toPairList() (BBSI/:534-549): every column of ebM ascending (u32, or i64 zero-extended) with its value
+// (i32 or i64); base: the exclusive scan of cards
+void launch_bsi_pairs(hipStream_t s, BsiValArgs a, const uint64_t* base, bool cols64, bool vals64, void* cols,
+                      void* vals);
+
 // decode.hip: portable-format decode on the device
 enum DecErr : uint32_t {
   DEC_OK = 0,

@@ -376,6 +376,128 @@ class Engine:
                                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(n_out)))
         return out
 
+    def _words(self, what, t):
+        """A torch tensor on this engine's GPU as contiguous 32-bit words: int64 (the low 32 bits of every
+        element, little-endian words), uint32 or int32, as from_values and point_query take them."""
+        import torch
+        self._check_tensor(what, t)
+        if t.dtype == torch.int64:
+            w = t.contiguous().reshape(-1).view(torch.int32)[::2].contiguous()
+        elif t.dtype in (torch.uint32, torch.int32):
+            w = t.contiguous()
+        else:
+            raise ValueError(f"{what}: an int64, uint32 or int32 tensor is required")
+        return w.reshape(-1)
+
+    def bsi_from_columns(self, columns, values, run_optimize=False):
+        """A resident bit-sliced index from (column, value) pairs, built on the device
+        (rbg_ctx_bsi_from_columns): setValue(column, value) for every pair, with run_optimize followed by
+        runOptimize() -> (batch, nbits, minValue, maxValue), the batch being the key-major [ebM, bA[0..nbits-1]]
+        that load([ebM] + slices) of RoaringBitmapSliceIndex.from_columns gives, as bsi / bsi_buffer take it.
+        The pairs may come in any order; a negative value or a repeated column raises
+        IllegalArgumentException, as do columns and values of different lengths.  numpy arrays or sequences
+        (columns below 2^32, values below 2^31) are uploaded; torch tensors on this engine's GPU are read
+        in place (rbg_ctx_bsi_from_columns_device), int64 (the low 32 bits of every element are read) or
+        uint32 / int32, with point_query's stream handshake.  Synchronous either way."""
+        out = ctypes.c_int32()
+        out3 = (ctypes.c_int32 * 3)()
+        if type(columns).__module__.split(".")[0] == "torch":
+            import torch
+            if type(values).__module__.split(".")[0] != "torch":
+                raise ValueError("bsi_from_columns: columns and values must both be tensors or both arrays")
+            if columns.numel() != values.numel():
+                raise _lib.IllegalArgumentException("columns and values differ in length")
+            if values.dtype == torch.int64 and values.numel() and bool(((values < 0) | (values >= 1 << 31)).any()):
+                raise _lib.IllegalArgumentException("Values should be non-negative and below 2^31")
+            c = self._words("bsi_from_columns", columns)
+            v = self._words("bsi_from_columns", values)
+            done = self._handshake(columns.device)
+            n = c.numel()
+            check(lib().rbg_ctx_bsi_from_columns_device(
+                self._ctx, ctypes.c_void_p(c.data_ptr()) if n else None, ctypes.c_void_p(v.data_ptr()) if n else None,
+                n, int(bool(run_optimize)), ctypes.byref(out), out3))
+            done()
+            return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+        c = np.asarray(columns, dtype=np.int64).reshape(-1)
+        v = np.asarray(values, dtype=np.int64).reshape(-1)
+        if c.size != v.size:
+            raise _lib.IllegalArgumentException("columns and values differ in length")
+        if v.size and (v.min() < 0 or v.max() >= 1 << 31):
+            raise _lib.IllegalArgumentException("Values should be non-negative and below 2^31")
+        c = np.ascontiguousarray(c.astype(np.uint32))
+        v = np.ascontiguousarray(v.astype(np.int32))
+        check(lib().rbg_ctx_bsi_from_columns(self._ctx, c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                             v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size,
+                                             int(bool(run_optimize)), ctypes.byref(out), out3))
+        return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+
+    def bsi_get_values(self, batch, nbits, columns, has_found=False):
+        """getValue for many columns at once against a resident index [ebM, bA[0..nbits-1], foundSet?]
+        (rbg_ctx_bsi_get_values): one int64 per column, in query order, -1 where ebM lacks the column.  The
+        columns need not be sorted or distinct.  numpy in -> numpy out, synchronous; a torch tensor on this
+        engine's GPU (int64 low words, or uint32) -> torch int64 tensor through the device entry point with no
+        host synchronisation, under point_query's stream handshake."""
+        if type(columns).__module__.split(".")[0] == "torch":
+            import torch
+            q = self._words("bsi_get_values", columns)
+            out = torch.empty(q.numel(), dtype=torch.int64, device=columns.device)
+            if q.numel() == 0:
+                return out
+            done = self._handshake(columns.device)
+            check(lib().rbg_ctx_bsi_get_values_device(self._ctx, int(batch), int(nbits), int(bool(has_found)),
+                                                      ctypes.c_void_p(q.data_ptr()), q.numel(),
+                                                      ctypes.c_void_p(out.data_ptr())))
+            done()
+            return out
+        q = np.ascontiguousarray(np.asarray(columns, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        out = np.empty(q.size, dtype=np.int64)
+        check(lib().rbg_ctx_bsi_get_values(self._ctx, int(batch), int(nbits), int(bool(has_found)),
+                                           q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), q.size,
+                                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
+        return out
+
+    def bsi_pairs_count(self, batch, nbits, has_found=False) -> int:
+        """The pairs bsi_to_pairs would write (cardinality of ebM): a null-output call, no device work."""
+        n_out = ctypes.c_uint64()
+        check(lib().rbg_ctx_bsi_to_pairs_device(self._ctx, int(batch), int(nbits), int(bool(has_found)), 0, 0, None,
+                                                None, ctypes.byref(n_out)))
+        return int(n_out.value)
+
+    def bsi_to_pairs(self, batch, nbits, dtype=None, has_found=False):
+        """toPairList() of a resident index (rbg_ctx_bsi_to_pairs): every column of ebM, ascending and
+        unsigned, with its value -> (columns, values).  dtype None: numpy uint32 columns and int32 values,
+        synchronous.  dtype torch.uint32 or torch.int64: torch tensors on this engine's GPU (columns of
+        that dtype; values int32 with uint32 columns, int64 with int64 columns), written through the device
+        entry point on the engine stream with no host synchronisation; torch's current stream waits for
+        them, as with point_query's result."""
+        n = self.bsi_pairs_count(batch, nbits, has_found)
+        n_out = ctypes.c_uint64()
+        if dtype is not None and type(dtype).__module__.split(".")[0] == "torch":
+            import torch
+            if dtype not in (torch.uint32, torch.int64):
+                raise ValueError("bsi_to_pairs: dtype torch.uint32 or torch.int64")
+            wide = int(dtype == torch.int64)
+            dev = torch.device("cuda", self.device)
+            cols = torch.empty(n, dtype=dtype, device=dev)
+            vals = torch.empty(n, dtype=torch.int64 if wide else torch.int32, device=dev)
+            if n == 0:
+                return cols, vals
+            done = self._handshake(dev)
+            check(lib().rbg_ctx_bsi_to_pairs_device(self._ctx, int(batch), int(nbits), int(bool(has_found)), wide, wide,
+                                                    ctypes.c_void_p(cols.data_ptr()), ctypes.c_void_p(vals.data_ptr()),
+                                                    ctypes.byref(n_out)))
+            done()
+            return cols, vals
+        if dtype is not None and np.dtype(dtype) != np.uint32:
+            raise ValueError("bsi_to_pairs: numpy columns are uint32")
+        cols = np.empty(n, dtype=np.uint32)
+        vals = np.empty(n, dtype=np.int32)
+        if n:
+            check(lib().rbg_ctx_bsi_to_pairs(self._ctx, int(batch), int(nbits), int(bool(has_found)), 0, 0,
+                                             cols.ctypes.data_as(ctypes.c_void_p), vals.ctypes.data_as(ctypes.c_void_p),
+                                             ctypes.byref(n_out)))
+        return cols, vals
+
     def batch_counts(self, batch) -> np.ndarray:
         """containers per input bitmap of a batch"""
         n = self.batch_stats(batch)["bitmaps"]
