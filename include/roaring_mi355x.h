@@ -288,6 +288,19 @@ int rbg_bsi_from_columns(const uint32_t* columns, const int32_t* values, size_t 
  * sorted or distinct. */
 int rbg_bsi_get_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
                        int nbits, const uint32_t* columns, size_t n, int64_t* out);
+/* RoaringBitmapSliceIndex.add(otherBsi) (RoaringBitmapSliceIndex.java:66-95: ebM.or(other.ebM) in place,
+ * grow, addDigit per slice of the other index with its carry chain, then minValue() / maxValue(), :97-138;
+ * the buffer package's MutableBitSliceIndex.add, buffer/MutableBitSliceIndex.java:121-130, 201-262, gives
+ * the same bytes) of index a = (ebm_a, slices_a[0..na-1]) and b, fused on the device: outs[0] = ebM,
+ * outs[1 + i] = bA[i] of the sum as portable bytes (outs must have room for 34 buffers; 1 + out3[0] are
+ * written, each released with rbg_free), out3 = {bit count, minValue, maxValue} (Java ints: with a 32nd
+ * slice they wrap negative, as valueAt's 1 << 31 does).  An empty ebM of b returns a unchanged with
+ * {na, min_a, max_a} (:67-69).  Neither index may hold a run container (RBG_ERR_ILLEGAL_ARGUMENT: compose
+ * the sum from rbg_pairwise and / xor per slice instead); na, nb <= 32, and a sum that needs a 33rd slice
+ * is RBG_ERR_ILLEGAL_ARGUMENT. */
+int rbg_bsi_add(const uint8_t* ebm_a, size_t ebm_a_len, const uint8_t* const* slices_a, const size_t* lens_a, int na,
+                int32_t min_a, int32_t max_a, const uint8_t* ebm_b, size_t ebm_b_len, const uint8_t* const* slices_b,
+                const size_t* lens_b, int nb, rbg_buffer* outs, int32_t* out3);
 
 /* Releases an output.  Large results (>= 8 MiB, 2 MiB-aligned huge-page buffers) are kept for
  * reuse by the next large result, at most two of them, so a caller's steady stream of big results
@@ -504,6 +517,18 @@ int rbg_ctx_bsi_from_columns(rbg_ctx* ctx, const uint32_t* columns, const int32_
  * they must not change until the call returns (every pass reads them). */
 int rbg_ctx_bsi_from_columns_device(rbg_ctx* ctx, const void* columns_dev, const void* values_dev, size_t n,
                                     int run_optimize, int32_t* batch, int32_t* out3);
+/* RoaringBitmapSliceIndex.add (RoaringBitmapSliceIndex.java:66-95, min / max :97-138) of two resident
+ * indexes, the key-major unpacked batches [ebM, bA[0..nbits_a-1]] and [ebM, bA[0..nbits_b-1]] (no trailing
+ * foundSet), as a new batch [ebM', bA'[0..n'-1]]: field for field what rbg_ctx_load of the reference's
+ * result bitmaps gives, usable wherever a built or loaded index is.  out3 = {n', minValue, maxValue}.  Both
+ * operands stay as they are; batch_a == batch_b doubles every value.  An empty ebM of b: a copy of a with
+ * {nbits_a, min_a, max_a} (the reference returns early, :67-69; min_a / max_a are used in that case
+ * alone).  RBG_ERR_ILLEGAL_ARGUMENT, with no batch made: a batch of another shape, nbits above 32, a run
+ * container in either batch (compose the sum from and / xor per slice), a sum that needs more than 32
+ * slices.  The workspace (2 + max(nbits_a, nbits_b) bitmaps of 8 KiB per present key) is walked in passes
+ * under rbg_ctx_bsi_from_columns' byte budget (RBG_BSI_BUILD_WS).  Synchronous. */
+int rbg_ctx_bsi_add(rbg_ctx* ctx, int32_t batch_a, int nbits_a, int32_t batch_b, int nbits_b, int32_t min_a,
+                    int32_t max_a, int32_t* out_batch, int32_t* out3);
 /* RoaringBitmapSliceIndex.getValue (RoaringBitmapSliceIndex.java:181-196) for n columns against a batch
  * [ebM, bA[0..nbits-1], foundSet?] (has_found: the batch ends with a foundSet, which is ignored), the
  * loop of the buffer package's batchIn / transposeWithCount (buffer/BitSliceIndexBase.java:551-639):

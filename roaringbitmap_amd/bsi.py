@@ -9,9 +9,12 @@ range (BBSI/:351-408) and sum (BBSI/:521-532).  Every query runs on the MI355X
 (csrc/bsi.hip) and the results are the reference's bytes, container types included.
 Construction (setValue) is host-side by default; from_columns(..., gpu=True) builds the slices on the
 device (csrc/bsibuild.hip), and getValues / toPairList read values back in bulk (csrc/bsival.hip with
-gpu=True).
+gpu=True).  add(otherBsi) (BSI/:66-95) sums two indexes in one fused device pass (csrc/bsiadd.hip) when
+neither holds a run container, and replays the reference's and / xor chain with the pairwise device ops
+otherwise.
 """
 import ctypes
+import os
 
 import numpy as np
 
@@ -96,6 +99,76 @@ class RoaringBitmapSliceIndex:
         self.runOptimized = self.runOptimized or otherBsi.runOptimized
         self.maxValue = max(self.maxValue, otherBsi.maxValue)
         self.minValue = min(self.minValue, otherBsi.minValue)
+
+    def _has_run(self):
+        """a run container anywhere in the index, from the serialized headers"""
+        return any(b.container_stats()[2] > 0 for b in [self.ebM] + self.bA)
+
+    def add(self, otherBsi):
+        """BSI/:66-95, in place: ebM.or(other.ebM), grow, addDigit(other.bA[i], i) for every slice of the other
+        index (carry = and(bA[i], x); bA[i].xor(x); the carry goes on to slice i + 1, growing the index by a
+        slice when it leaves the top), then minValue() / maxValue() (:97-138).  None or an empty other index
+        returns at once.  When neither index holds a run container the whole sum is one fused device pass
+        (rbg_bsi_add, csrc/bsiadd.hip), the reference's bytes; otherwise, or with RBG_BSI_ADD_COMPOSED=1 in
+        the environment (read at every call), the reference's sequence is replayed with the pairwise device
+        ops (_add_composed).  runOptimized stays as it was.  A sum that needs a 33rd slice raises
+        IllegalArgumentException on the fused path."""
+        if otherBsi is None or otherBsi.ebM.isEmpty():
+            return
+        if os.environ.get("RBG_BSI_ADD_COMPOSED") == "1" or self._has_run() or otherBsi._has_run():
+            self._add_composed(otherBsi)
+            return
+        if len(self.bA) > 32 or len(otherBsi.bA) > 32:
+            raise IllegalArgumentException("add: an index holds at most 32 slices")
+        arr_a, lens_a = self._slices()
+        arr_b, lens_b = otherBsi._slices()
+        ea, eb = self.ebM.serialize(), otherBsi.ebM.serialize()
+        outs = (_lib.rbg_buffer * 34)()
+        out3 = (ctypes.c_int32 * 3)()
+        check(lib().rbg_bsi_add(ea, len(ea), arr_a, lens_a, len(self.bA), self.minValue, self.maxValue,
+                                eb, len(eb), arr_b, lens_b, len(otherBsi.bA), outs, out3))
+        cls = type(self.ebM)
+        self.ebM = cls(take(outs[0]))
+        self.bA = [RoaringBitmap(take(outs[1 + k])) for k in range(int(out3[0]))]
+        self.minValue, self.maxValue = int(out3[1]), int(out3[2])
+
+    def _add_composed(self, otherBsi):
+        """The reference's literal sequence (BSI/:71-95) over the device's pairwise ops: the in-place or of the
+        existence bitmaps, and per addDigit one static and, one in-place xor and the isEmpty() of the carry.
+        (other is self: the reference would read slices it has already changed; a snapshot is added instead,
+        which doubles the values as the fused path does.)"""
+        other_ba = [b.clone() for b in otherBsi.bA]
+        self.ebM.or_(otherBsi.ebM)
+        while len(self.bA) < len(other_ba):  # grow(otherBsi.bitCount())
+            self.bA.append(RoaringBitmap())
+        for i, x in enumerate(other_ba):
+            carry, k = x, i
+            while True:  # addDigit(carry, k)
+                nxt = RoaringBitmap.and_(self.bA[k], carry)
+                self.bA[k].xor(carry)
+                if nxt.isEmpty():
+                    break
+                if k + 1 >= len(self.bA):
+                    self.bA.append(RoaringBitmap())  # grow(bitCount() + 1)
+                carry, k = nxt, k + 1
+        self.minValue, self.maxValue = self._extreme(False), self._extreme(True)
+
+    def _extreme(self, largest):
+        """minValue() / maxValue() (BSI/:97-138): the descent over the slices, then valueAt(first()) as a
+        Java int"""
+        if self.ebM.isEmpty():
+            return 0
+        ids = self.ebM
+        for b in reversed(self.bA):
+            tmp = RoaringBitmap.and_(ids, b) if largest else RoaringBitmap.andNot(ids, b)
+            if not tmp.isEmpty():
+                ids = tmp
+        col = ids.first()
+        v = 0
+        for i, b in enumerate(self.bA):
+            if b.contains(col):
+                v |= 1 << i
+        return int(np.int64(v).astype(np.int32))
 
     def getValue(self, columnId):
         """BSI/:181-196 getValue(columnId) -> (value, exists): ebM.contains, then one contains per slice
@@ -191,6 +264,19 @@ class BitSliceIndexBase(RoaringBitmapSliceIndex):
     against ebM) and ImmutableRoaringBitmap's result types (csrc/bsi.hip, k_bsi_buf)."""
 
     RANGE_NEQ_DIRECT = 7  # RBG_BSI_RANGE_NEQ_DIRECT
+
+    def add(self, otherBsi):
+        """MutableBitSliceIndex.add (bsi/.../buffer/MutableBitSliceIndex.java:121-130, 201-262): for indexes
+        without a run container the heap index's bytes (the mappeable containers' or / and / xor type rules
+        are the heap's there), through the same fused pass.  With a run container it is refused:
+        MappeableRunContainer's and keeps merged runs, and the buffer package's in-place xor over run
+        containers is not established here."""
+        if otherBsi is None or otherBsi.ebM.isEmpty():
+            return
+        if self._has_run() or otherBsi._has_run():
+            raise IllegalArgumentException("add: a buffer index with a run container is not supported "
+                                           "(the buffer package's in-place xor over run containers)")
+        RoaringBitmapSliceIndex.add(self, otherBsi)
 
     def _compare(self, op, start, end, foundSet):
         arr, lens = self._slices()

@@ -18,6 +18,9 @@
 //   k_bsib_write    one wave per non-empty cell: the slot, the CDesc, keys[], bm[] = input
 //   k_bsib_key_off  the batch's key CSR over its containers
 //
+// (bsiadd.hip fills the same workspace with the sum of two indexes and shares the plan, scan, write and key
+// CSR stages; its only extension is the plan's ebm_run flag.)
+//
 // Types as in build.hip: card <= 4096 -> A, else B; with run_optimize A -> R iff 2 card > 2 + 4 nruns,
 // B -> R iff 2 + 4 nruns < 8192.
 //
@@ -126,7 +129,8 @@ static_assert(sizeof(BsibInfo) == kBsibInfoBytes, "the engine sizes the plan's t
 __global__ __launch_bounds__(256) void k_bsib_plan(const uint8_t* __restrict__ ws, uint32_t k_lo, uint32_t k_hi, int m,
                                                    uint32_t R, int run_optimize, BsibInfo* __restrict__ info,
                                                    uint64_t* __restrict__ size, unsigned long long* __restrict__ per,
-                                                   unsigned long long* __restrict__ kinds) {
+                                                   unsigned long long* __restrict__ kinds,
+                                                   const uint8_t* __restrict__ ebm_run) {
   const int lane = lane_id();
   const uint32_t wave = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (wave >= R * (uint32_t)m) return;
@@ -148,6 +152,10 @@ __global__ __launch_bounds__(256) void k_bsib_plan(const uint8_t* __restrict__ w
     if (run_optimize) {
       nruns = w_runs(x);
       if (kind == DK_A ? 2 * card > 2 + 4 * nruns : 2 + 4 * nruns < 8192) kind = DK_R;
+    }
+    if (ebm_run && j == 0 && ebm_run[ki]) {  // the full ebM' of bsiadd.hip (wave-uniform)
+      kind = DK_R;
+      nruns = 1;
     }
     const uint32_t len = kind == DK_A ? 2u * card : kind == DK_B ? 8192u : 2u + 4u * nruns;
     if (lane == 0) {
@@ -246,11 +254,12 @@ void launch_bsib_scatter(hipStream_t s, const uint32_t* col, const int32_t* val,
 }
 
 void launch_bsib_plan(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t k_hi, int m, int run_optimize,
-                      void* info, uint64_t* size, unsigned long long* per, unsigned long long* kinds) {
+                      void* info, uint64_t* size, unsigned long long* per, unsigned long long* kinds,
+                      const uint8_t* ebm_run) {
   if (k_hi <= k_lo) return;
   const uint32_t R = std::max<uint32_t>(1, std::min<uint32_t>(k_hi - k_lo, 16384u / (uint32_t)m));
   hipLaunchKernelGGL(k_bsib_plan, dim3((R * (uint32_t)m + 3) / 4), dim3(256), 0, s, ws, k_lo, k_hi, m, R, run_optimize,
-                     reinterpret_cast<BsibInfo*>(info), size, per, kinds);
+                     reinterpret_cast<BsibInfo*>(info), size, per, kinds, ebm_run);
 }
 
 void launch_bsib_write(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t k_hi, int m, const void* info,

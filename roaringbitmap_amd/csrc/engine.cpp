@@ -185,6 +185,7 @@ struct Ctx {
   // a BSI batch from (column, value) pairs (bsibuild.hip): the present keys and their CSR, the plan's cell
   // table, the cells' size words (scanned in place) and scan scratch, the per-input totals
   DevBuf bsib_pkeys, bsib_pkoff, bsib_info, bsib_size, bsib_part, bsib_per;
+  DevBuf bsia_run;  // the sum of two indexes (bsiadd.hip): per present key, ebM' is a full run container
   DevBuf bsiv_cards, bsiv_part;  // toPairList (bsival.hip): ebM's cardinality per key (scanned in place)
   DevBuf gather_items, gather_out;  // batch fetch: slot gather list and download buffer
   DevBuf order;                     // horizontal_*: chain order of every key segment
@@ -1166,6 +1167,63 @@ static size_t bsib_budget() {
   return (size_t)std::min<unsigned long long>(v ? v : kBsibBudget, 4ull << 30);
 }
 
+// The batch of a planned workspace (bsibuild.hip's cells; filled by the build's scatter or by bsiadd.hip):
+// K present keys x m cells, walked P keys per pass; hp: the plan's per-input totals (4 per cell column,
+// then the three kind counts), total: the scan's total.  The first n_bm cell columns are the batch's
+// bitmaps (any further column holds no container).  refill(k_lo, k_hi) fills the workspace with a pass
+// again when there are several.  The workspace goes back to the pool.
+template <class Refill>
+static int bsib_emit(Ctx* c, size_t K, int m, int n_bm, size_t P, DevBuf& ws, const std::vector<unsigned long long>& hp,
+                     uint64_t total, Refill&& refill, const char* what, int32_t* out_id) {
+  hipStream_t s = c->stream;
+  uint64_t* size = c->bsib_size.as<uint64_t>();
+  const size_t C = (size_t)(total >> kBsibCountShift);
+  const int32_t id = new_batch(c);
+  Batch& b = *c->batches[id];
+  BatchGuard guard{c, {id}};  // dropped unless the build completes
+  b.payload_bytes = (size_t)(total & ((1ull << kBsibCountShift) - 1));
+  CHK(pool_take(c, b.keys, 2 * C + 16));
+  CHK(pool_take(c, b.desc, sizeof(CDesc) * C + 16));
+  CHK(pool_take(c, b.bm, 4 * C + 16));
+  CHK(pool_take(c, b.key_off, 4 * (kMaxKeys + 1)));
+  CHK(pool_take(c, b.bm_off, 4 * ((size_t)n_bm + 1)));
+  CHK(pool_take(c, b.payload, b.payload_bytes + 64));
+  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+    const size_t k_hi = std::min(K, k_lo + P);
+    if (P < K) CHK(refill(k_lo, k_hi));  // several passes: the workspace held another pass since the plan
+    launch_bsib_write(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, c->bsib_info.p, size,
+                      c->bsib_pkeys.as<uint16_t>(), b.desc.as<CDesc>(), b.keys.as<uint16_t>(), b.bm.as<uint32_t>(),
+                      b.payload.as<uint8_t>());
+  }
+  launch_bsib_key_off(s, c->bsib_pkoff.as<uint32_t>(), size, m, b.key_off.as<uint32_t>());
+  HIPCHK(hipGetLastError());
+  pool_put(c, ws);  // whatever takes it next is enqueued on this stream, after the write kernels
+  b.n_bm = (size_t)n_bm;
+  b.n_ctr = C;
+  b.key_major = true;
+  for (int k = 0; k < 3; k++) b.n_kind[k] = (int64_t)hp[4 * m + k];
+  b.max_ser = 0;  // no container above kStagedMax serialized bytes
+  b.h_bm_off.assign(n_bm + 1, 0);
+  b.h_bm_nctr.resize(n_bm);
+  b.h_bm_card.resize(n_bm);
+  b.h_has_run.resize(n_bm);
+  for (int i = 0; i < n_bm; i++) {
+    b.h_bm_nctr[i] = (uint32_t)hp[4 * i];
+    b.h_bm_off[i + 1] = b.h_bm_off[i] + b.h_bm_nctr[i];
+    b.h_bm_card[i] = (int64_t)hp[4 * i + 1];
+    b.h_has_run[i] = hp[4 * i + 3] != 0;
+    b.long_card += b.h_bm_card[i];
+    b.ser_bytes += (int64_t)(header_size(b.h_bm_nctr[i], b.h_has_run[i] != 0) + hp[4 * i + 2]);
+  }
+  HIPCHK(hipMemcpyAsync(b.bm_off.p, b.h_bm_off.data(), 4 * ((size_t)n_bm + 1), hipMemcpyHostToDevice, s));
+  HIPCHK(hipStreamSynchronize(s));
+  dbg(s, what);
+  guard.ids.clear();
+  b.live = true;
+  *out_id = id;
+  return RBG_OK;
+}
+
 // A bit-sliced index from n (column, value) pairs in device memory (u32 columns, all distinct; i32 values,
 // none negative; any order) as a new key-major batch [ebM, bA[0..nbits-1]]: setValue for every pair
 // (BSI/:299-347: ensureCapacityInternal's min / max and bit count, then ebM.add and one add per set bit),
@@ -1246,50 +1304,7 @@ static int ctx_bsi_from_columns(Ctx* c, const uint32_t* col_dev, const int32_t* 
     set_err("bsi_from_columns: a column is given more than once");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  const size_t C = (size_t)(total >> kBsibCountShift);
-  const int32_t id = new_batch(c);
-  Batch& b = *c->batches[id];
-  BatchGuard guard{c, {id}};  // dropped unless the build completes
-  b.payload_bytes = (size_t)(total & ((1ull << kBsibCountShift) - 1));
-  CHK(pool_take(c, b.keys, 2 * C + 16));
-  CHK(pool_take(c, b.desc, sizeof(CDesc) * C + 16));
-  CHK(pool_take(c, b.bm, 4 * C + 16));
-  CHK(pool_take(c, b.key_off, 4 * (kMaxKeys + 1)));
-  CHK(pool_take(c, b.bm_off, 4 * ((size_t)m + 1)));
-  CHK(pool_take(c, b.payload, b.payload_bytes + 64));
-  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
-    const size_t k_hi = std::min(K, k_lo + P);
-    if (P < K) CHK(scatter(k_lo, k_hi));  // several passes: the workspace held another pass since the plan
-    launch_bsib_write(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, c->bsib_info.p, size,
-                      c->bsib_pkeys.as<uint16_t>(), b.desc.as<CDesc>(), b.keys.as<uint16_t>(), b.bm.as<uint32_t>(),
-                      b.payload.as<uint8_t>());
-  }
-  launch_bsib_key_off(s, c->bsib_pkoff.as<uint32_t>(), size, m, b.key_off.as<uint32_t>());
-  HIPCHK(hipGetLastError());
-  pool_put(c, ws);  // whatever takes it next is enqueued on this stream, after the write kernels
-  b.n_bm = (size_t)m;
-  b.n_ctr = C;
-  b.key_major = true;
-  for (int k = 0; k < 3; k++) b.n_kind[k] = (int64_t)hp[4 * m + k];
-  b.max_ser = 0;  // no container above kStagedMax serialized bytes
-  b.h_bm_off.assign(m + 1, 0);
-  b.h_bm_nctr.resize(m);
-  b.h_bm_card.resize(m);
-  b.h_has_run.resize(m);
-  for (int i = 0; i < m; i++) {
-    b.h_bm_nctr[i] = (uint32_t)hp[4 * i];
-    b.h_bm_off[i + 1] = b.h_bm_off[i] + b.h_bm_nctr[i];
-    b.h_bm_card[i] = (int64_t)hp[4 * i + 1];
-    b.h_has_run[i] = hp[4 * i + 3] != 0;
-    b.long_card += b.h_bm_card[i];
-    b.ser_bytes += (int64_t)(header_size(b.h_bm_nctr[i], b.h_has_run[i] != 0) + hp[4 * i + 2]);
-  }
-  HIPCHK(hipMemcpyAsync(b.bm_off.p, b.h_bm_off.data(), 4 * ((size_t)m + 1), hipMemcpyHostToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));
-  dbg(s, "bsi_from_columns: write");
-  guard.ids.clear();
-  b.live = true;
-  *out_id = id;
+  CHK(bsib_emit(c, K, m, m, P, ws, hp, total, scatter, "bsi_from_columns: write", out_id));
   out3[0] = nbits;
   out3[1] = mn;
   out3[2] = mx;
@@ -1308,6 +1323,113 @@ static int ctx_bsi_from_columns_host(Ctx* c, const uint32_t* col, const int32_t*
   pool_put(c, dc);
   pool_put(c, dv);
   return st;
+}
+
+// An operand of the fused add: a key-major, unpacked, run-free batch [ebM, bA[0..nbits-1]]
+static int bsi_add_operand(Ctx* c, int32_t id, int nbits, Batch** B, BsiAddSide* side) {
+  CHK(get_batch(c, id, B));
+  const Batch* b = *B;
+  if (nbits < 0 || nbits > 32) {
+    set_err("bsi_add: an index holds at most 32 slices");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (!b->key_major || b->packed || b->n_bm != (size_t)(1 + nbits)) {
+    set_err("bsi_add: batch must be key-major, unpacked and hold ebM and nbits slices");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (b->n_kind[DK_R] != 0) {
+    set_err("bsi_add: an operand holds a run container; the composed route (and / xor per slice) handles it");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  *side = BsiAddSide{b->key_off.as<uint32_t>(), b->desc.as<CDesc>(), b->bm.as<uint32_t>(), b->payload.as<uint8_t>(), nbits};
+  return RBG_OK;
+}
+
+// RoaringBitmapSliceIndex.add (BSI/:66-95; MutableBitSliceIndex.add, buffer/MutableBitSliceIndex.java:121-130,
+// 201-262) of two resident run-free indexes as a new key-major batch [ebM', bA'[0..n'-1]]: what ctx_load of
+// the reference's result bitmaps gives (bsiadd.hip; both operands untouched, batch_a == batch_b doubles).
+// out3 = {n', minValue, maxValue}, min / max from the descent of BSI/:97-138 as Java ints.  An empty ebM of
+// b (:67-69): a copy of a with {nbits_a, min_a, max_a}.  Two read-backs: the key count, then the per-input
+// totals with min / max -- the carry out of the top input slice decides whether the result has one more
+// slice, and out of slice 31 it is refused before a batch exists.  The K x (2 + max(na, nb)) bitmaps of the
+// workspace are walked in key passes under bsib_budget() with the build's two-sweep scheme.
+static int ctx_bsi_add(Ctx* c, int32_t batch_a, int nbits_a, int32_t batch_b, int nbits_b, int32_t min_a, int32_t max_a,
+                       int32_t* out_id, int32_t* out3) {
+  hipStream_t s = c->stream;
+  Batch *A, *B;
+  BsiAddSide sa, sb;
+  CHK(bsi_add_operand(c, batch_a, nbits_a, &A, &sa));
+  CHK(bsi_add_operand(c, batch_b, nbits_b, &B, &sb));
+  const bool b_empty = B->h_bm_card.empty() || B->h_bm_card[0] == 0;
+  if (b_empty) sb = BsiAddSide{nullptr, nullptr, nullptr, nullptr, 0};
+  const int top = b_empty ? nbits_a : std::max(nbits_a, nbits_b);
+  const int m = top + 2;
+  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
+  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
+  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] {min, max} as two u32
+  static const uint32_t kMinMaxInit[2] = {0xFFFFFFFFu, 0u};
+  HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
+  HIPCHK(hipMemsetAsync(sc, 0, 64, s));
+  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxInit, 8, hipMemcpyHostToDevice, s));
+  launch_bsia_keys(s, A->keys.as<uint16_t>(), A->n_ctr, B->keys.as<uint16_t>(), b_empty ? 0 : B->n_ctr,
+                   c->flag.as<uint8_t>());
+  launch_bld_keys(s, nullptr, 0, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
+  HIPCHK(hipGetLastError());
+  unsigned long long h[2] = {};
+  HIPCHK(hipMemcpyAsync(h, sc, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const size_t K = (size_t)h[0];
+  const size_t cells = K * (size_t)m;
+  dbg(s, "bsi_add: keys");
+  CHK(c->bsib_info.ensure(kBsibInfoBytes * cells + 16));
+  CHK(c->bsib_size.ensure(8 * (cells + 1)));
+  CHK(c->bsib_part.ensure(8 * (scan_parts(cells) + 1)));
+  CHK(c->bsib_per.ensure(8 * (4 * (size_t)m + 4)));
+  CHK(c->bsia_run.ensure(K + 16));
+  uint64_t* size = c->bsib_size.as<uint64_t>();
+  unsigned long long* per = c->bsib_per.as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
+  const size_t P = std::min(K, std::max<size_t>(1, bsib_budget() / (8192 * (size_t)m)));  // keys per pass
+  DevBuf ws;  // back to the pool at the end (freed on an error)
+  if (K) CHK(pool_take(c, ws, 8192 * (size_t)m * P));
+  auto fill = [&](size_t k_lo, size_t k_hi) -> int {  // every cell of the pass is written: no memset
+    launch_bsi_add(s, sa, sb, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, ws.as<uint8_t>(),
+                   c->bsia_run.as<uint8_t>());
+    return RBG_OK;
+  };
+  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+    const size_t k_hi = std::min(K, k_lo + P);
+    CHK(fill(k_lo, k_hi));
+    if (!b_empty) launch_bsia_minmax(s, ws.as<uint8_t>(), (uint32_t)(k_hi - k_lo), m, reinterpret_cast<uint32_t*>(sc + 1));
+    launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, 0, c->bsib_info.p, size, per, per + 4 * m,
+                     c->bsia_run.as<uint8_t>());
+  }
+  launch_exclusive_scan(s, size, size, cells, c->bsib_part.as<uint64_t>(), size + cells);
+  HIPCHK(hipGetLastError());
+  std::vector<unsigned long long> hp(4 * (size_t)m + 4);
+  uint64_t total = 0;
+  uint32_t mm[2] = {0, 0};
+  HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&total, size + cells, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(mm, sc + 1, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  dbg(s, "bsi_add: add + plan");
+  const bool grown = hp[4 * (size_t)(m - 1) + 1] != 0;  // a carry left the top input slice
+  if (grown && top == 32) {
+    set_err("bsi_add: the sum needs more than 32 slices");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  const int nbits = top + (grown ? 1 : 0);
+  CHK(bsib_emit(c, K, m, 1 + nbits, P, ws, hp, total, fill, "bsi_add: write", out_id));
+  out3[0] = nbits;
+  if (b_empty) {  // the reference returns before it recomputes them
+    out3[1] = min_a;
+    out3[2] = max_a;
+  } else {  // an empty ebM' (b's ebM holds a column: cannot be) would leave {~0u, 0}; minValue() gives 0 then
+    out3[1] = mm[0] <= mm[1] ? (int32_t)mm[0] : 0;
+    out3[2] = mm[0] <= mm[1] ? (int32_t)mm[1] : 0;
+  }
+  return RBG_OK;
 }
 
 // A batch as the operand of the BSI read-outs (bsival.hip): key-major [ebM, nbits slices, foundSet?]
@@ -4207,6 +4329,30 @@ int rbg_bsi_from_columns(const uint32_t* columns, const int32_t* values, size_t 
   Ctx* c = os.c;
   int32_t id;
   CHK(ctx_bsi_from_columns_host(c, columns, values, n, run_optimize != 0, &id, out3));
+  os.adopt(id);
+  return ctx_batch_fetch_range(c, id, 0, 1 + (size_t)out3[0], outs);
+}
+
+int rbg_ctx_bsi_add(rbg_ctx* ctx, int32_t batch_a, int nbits_a, int32_t batch_b, int nbits_b, int32_t min_a,
+                    int32_t max_a, int32_t* out_batch, int32_t* out3) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!out_batch || !out3) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_add(c, batch_a, nbits_a, batch_b, nbits_b, min_a, max_a, out_batch, out3);
+}
+
+int rbg_bsi_add(const uint8_t* ebm_a, size_t ebm_a_len, const uint8_t* const* slices_a, const size_t* lens_a, int na,
+                int32_t min_a, int32_t max_a, const uint8_t* ebm_b, size_t ebm_b_len, const uint8_t* const* slices_b,
+                const size_t* lens_b, int nb, rbg_buffer* outs, int32_t* out3) {
+  if (!outs || !out3 || na < 0 || nb < 0 || na > 32 || nb > 32) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (!ebm_a || !ebm_b || (na && (!slices_a || !lens_a)) || (nb && (!slices_b || !lens_b))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t ia, ib, id;
+  CHK(bsi_load(os, ebm_a, ebm_a_len, slices_a, lens_a, (size_t)na, nullptr, 0, &ia));
+  CHK(bsi_load(os, ebm_b, ebm_b_len, slices_b, lens_b, (size_t)nb, nullptr, 0, &ib));
+  CHK(ctx_bsi_add(c, ia, na, ib, nb, min_a, max_a, &id, out3));
   os.adopt(id);
   return ctx_batch_fetch_range(c, id, 0, 1 + (size_t)out3[0], outs);
 }

@@ -545,14 +545,36 @@ constexpr size_t kBsibInfoBytes = 8;  // per (key index, input) cell: the plan's
 constexpr int kBsibCountShift = 40;
 // info / size: K x m cells (the pass fills its own); per (4 u64 per input: containers, cardinality,
 // serialized payload bytes, run containers) and kinds (3 u64) are added to: zeroed by the caller
+// ebm_run (may be null; indexed by key index): cell 0 of a flagged key is a run container of one run (the
+// full ebM' of an in-place union, bsiadd.hip)
 void launch_bsib_plan(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t k_hi, int m, int run_optimize,
-                      void* info, uint64_t* size, unsigned long long* per, unsigned long long* kinds);
+                      void* info, uint64_t* size, unsigned long long* per, unsigned long long* kinds,
+                      const uint8_t* ebm_run = nullptr);
 // scan: the exclusive scan of size[] over all K x m cells; pkeys: the K present keys
 void launch_bsib_write(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t k_hi, int m, const void* info,
                        const uint64_t* scan, const uint16_t* pkeys, CDesc* desc, uint16_t* keys, uint32_t* bm,
                        uint8_t* payload);
 // the batch's key CSR (65,537 entries); scan[K m] = the scan's total
 void launch_bsib_key_off(hipStream_t s, const uint32_t* pkey_off, const uint64_t* scan, int m, uint32_t* key_off);
+
+// bsiadd.hip: the sum of two run-free key-major batches [ebM, bA[0..n-1]] (RoaringBitmapSliceIndex.add,
+// BSI/:66-95) into the workspace layout of the build above, m = 2 + max(na, nb) cells per present key:
+// ebM', the slices, the carry out of the top input slice
+struct BsiAddSide {
+  const uint32_t* key_off;  // the batch's key CSR; null: the side takes no part (an empty operand)
+  const CDesc* desc;
+  const uint32_t* bm;  // input index per container
+  const uint8_t* payload;
+  int n;  // slices
+};
+// flag[key] = 1 for every container key of both batches (flag: 65,536 bytes, zeroed by the caller)
+void launch_bsia_keys(hipStream_t s, const uint16_t* ka, uint64_t na, const uint16_t* kb, uint64_t nb, uint8_t* flag);
+// one pass over the key indices [k_lo, k_hi); writes every cell of the pass and ebm_run[k_lo..k_hi)
+void launch_bsi_add(hipStream_t s, BsiAddSide a, BsiAddSide b, const uint16_t* pkeys, uint32_t k_lo, uint32_t k_hi,
+                    int m, uint8_t* ws, uint8_t* ebm_run);
+// minValue() / maxValue() (BSI/:97-138) over the n_keys keys of a pass's workspace; mm = {min, max} as
+// unsigned, set to {~0u, 0} by the caller
+void launch_bsia_minmax(hipStream_t s, const uint8_t* ws, uint32_t n_keys, int m, uint32_t* mm);
 
 // bsival.hip: values out of a key-major batch [ebM, bA[0..nbits-1], foundSet?]
 struct BsiValArgs {

@@ -431,6 +431,20 @@ class Engine:
                                              int(bool(run_optimize)), ctypes.byref(out), out3))
         return out.value, int(out3[0]), int(out3[1]), int(out3[2])
 
+    def bsi_add(self, a, nbits_a, b, nbits_b, min_a=0, max_a=0):
+        """RoaringBitmapSliceIndex.add (BSI/:66-95) of two resident run-free indexes, the key-major batches
+        [ebM, bA[0..nbits_a-1]] and [ebM, bA[0..nbits_b-1]], fused on the device (rbg_ctx_bsi_add)
+        -> (batch, nbits, minValue, maxValue): a new batch, the one load() of the reference's result bitmaps
+        gives, as bsi / bsi_buffer / bsi_get_values / bsi_to_pairs take it.  Both operands stay; a == b
+        doubles the values.  An empty ebM of b: a copy of a with (nbits_a, min_a, max_a).  A run container
+        in either batch, more than 32 slices on either side or in the sum: IllegalArgumentException, no
+        batch made.  Synchronous."""
+        out = ctypes.c_int32()
+        out3 = (ctypes.c_int32 * 3)()
+        check(lib().rbg_ctx_bsi_add(self._ctx, int(a), int(nbits_a), int(b), int(nbits_b), int(min_a), int(max_a),
+                                    ctypes.byref(out), out3))
+        return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+
     def bsi_get_values(self, batch, nbits, columns, has_found=False):
         """getValue for many columns at once against a resident index [ebM, bA[0..nbits-1], foundSet?]
         (rbg_ctx_bsi_get_values): one int64 per column, in query order, -1 where ebM lacks the column.  The
