@@ -301,6 +301,20 @@ int rbg_bsi_get_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const*
 int rbg_bsi_add(const uint8_t* ebm_a, size_t ebm_a_len, const uint8_t* const* slices_a, const size_t* lens_a, int na,
                 int32_t min_a, int32_t max_a, const uint8_t* ebm_b, size_t ebm_b_len, const uint8_t* const* slices_b,
                 const size_t* lens_b, int nb, rbg_buffer* outs, int32_t* out3);
+/* BitSliceIndexBase.parallelIn(parallelism, foundSet, values, pool) of the buffer package's index
+ * (buffer/BitSliceIndexBase.java:611-639): WHERE value IN (values).  The result is
+ * {c in ebM and fixed : value(c) in values}, fixed = the foundSet, or ebM when found is NULL, as the
+ * reference's bytes: parallelExec (:99-136) cuts fixed into batches of
+ * min(max(cardinality(fixed) / parallelism, parallelism), 65536) columns, batchIn (:628-639) builds one bitmap
+ * per batch and parallelMR (:148-164) ors them lazily, so every container is typed by its cardinality (array
+ * up to 4096, bitmap above) except a full one, which is a run container of one run unless its 65,536 columns
+ * fall into a single batch.  values: n_values host ints in any order, repeats allowed; membership is
+ * equality of 32-bit patterns (with fewer than 32 slices a negative entry matches nothing).  An empty list
+ * or an empty fixed gives the empty bitmap.  RBG_ERR_ILLEGAL_ARGUMENT: parallelism < 1 (the reference
+ * divides by it), nbits > 32, more than 2^31 - 1 columns in fixed (its getCardinality() is an int). */
+int rbg_bsi_in(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens, int nbits,
+               const uint8_t* found, size_t found_len, const int32_t* values, size_t n_values, int parallelism,
+               rbg_buffer* out);
 
 /* Releases an output.  Large results (>= 8 MiB, 2 MiB-aligned huge-page buffers) are kept for
  * reuse by the next large result, at most two of them, so a caller's steady stream of big results
@@ -529,6 +543,18 @@ int rbg_ctx_bsi_from_columns_device(rbg_ctx* ctx, const void* columns_dev, const
  * under rbg_ctx_bsi_from_columns' byte budget (RBG_BSI_BUILD_WS).  Synchronous. */
 int rbg_ctx_bsi_add(rbg_ctx* ctx, int32_t batch_a, int nbits_a, int32_t batch_b, int nbits_b, int32_t min_a,
                     int32_t max_a, int32_t* out_batch, int32_t* out3);
+/* BitSliceIndexBase.parallelIn (buffer/BitSliceIndexBase.java:611-639; rbg_bsi_in above) over a resident
+ * index, the key-major unpacked batch [ebM, bA[0..nbits-1], foundSet if has_found], as a new one-bitmap
+ * batch: field for field what rbg_ctx_load of the reference's result gives, usable wherever a loaded bitmap
+ * is (pairwise, to_values, batch_fetch; fetched, it loads as the trailing foundSet of a later call).  The operand
+ * stays as it is.  values is a host array like compare's start / end; the device gets a sorted distinct copy.
+ * An empty fixed or an empty list: a live batch of one empty bitmap.  RBG_ERR_ILLEGAL_ARGUMENT, with no
+ * batch made: parallelism < 1, nbits > 32, a batch that is not key-major, is packed or does not hold
+ * 1 + nbits + has_found bitmaps, more than 2^31 - 1 columns in the foundSet (or ebM) or entries in the list.
+ * The workspace (one 8 KiB bitmap per key that ebM and the foundSet share) is walked in passes under
+ * rbg_ctx_bsi_from_columns' byte budget (RBG_BSI_BUILD_WS).  Synchronous. */
+int rbg_ctx_bsi_in(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const int32_t* values, size_t n_values,
+                   int parallelism, int32_t* out_batch);
 /* RoaringBitmapSliceIndex.getValue (RoaringBitmapSliceIndex.java:181-196) for n columns against a batch
  * [ebM, bA[0..nbits-1], foundSet?] (has_found: the batch ends with a foundSet, which is ignored), the
  * loop of the buffer package's batchIn / transposeWithCount (buffer/BitSliceIndexBase.java:551-639):

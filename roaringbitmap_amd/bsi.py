@@ -11,7 +11,8 @@ Construction (setValue) is host-side by default; from_columns(..., gpu=True) bui
 device (csrc/bsibuild.hip), and getValues / toPairList read values back in bulk (csrc/bsival.hip with
 gpu=True).  add(otherBsi) (BSI/:66-95) sums two indexes in one fused device pass (csrc/bsiadd.hip) when
 neither holds a run container, and replays the reference's and / xor chain with the pairwise device ops
-otherwise.
+otherwise.  The buffer index's parallelIn (BBSI/:611-639), WHERE value IN (...), is one fused pass too
+(csrc/bsiin.hip).
 """
 import ctypes
 import os
@@ -20,6 +21,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import IllegalArgumentException, check, lib, take
+from .engine import _in_list
 from .roaring import RoaringBitmap, run_optimize_many
 
 OPERATIONS = ("EQ", "NEQ", "LE", "LT", "GE", "GT", "RANGE")  # BitmapSliceIndex.Operation order
@@ -277,6 +279,27 @@ class BitSliceIndexBase(RoaringBitmapSliceIndex):
             raise IllegalArgumentException("add: a buffer index with a run container is not supported "
                                            "(the buffer package's in-place xor over run containers)")
         RoaringBitmapSliceIndex.add(self, otherBsi)
+
+    def parallelIn(self, parallelism, foundSet, values, pool=None):
+        """BBSI/:611-639 parallelIn(parallelism, foundSet, values, pool) -> ImmutableRoaringBitmap (as
+        RoaringBitmap bytes): the columns of ebM, within foundSet unless it is None, whose value is in
+        values (any iterable of ints), in one fused device pass (rbg_bsi_in, csrc/bsiin.hip).  pool is accepted
+        and ignored: the device pass has no use for an executor, and the result does not depend on it;
+        parallelism still decides parallelExec's batch size and with it whether a full container is a bitmap
+        or a run container."""
+        if int(parallelism) < 1:
+            raise IllegalArgumentException("parallelIn: parallelism must be positive")
+        if len(self.bA) > 32:
+            raise IllegalArgumentException("parallelIn: an index holds at most 32 slices")
+        v = _in_list(values)
+        arr, lens = self._slices()
+        e = self.ebM.serialize()
+        f = foundSet.serialize() if foundSet is not None else None
+        out = _lib.rbg_buffer()
+        check(lib().rbg_bsi_in(e, len(e), arr, lens, len(self.bA), f, len(f) if f else 0,
+                               v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), v.size, int(parallelism),
+                               ctypes.byref(out)))
+        return RoaringBitmap(take(out))
 
     def _compare(self, op, start, end, foundSet):
         arr, lens = self._slices()

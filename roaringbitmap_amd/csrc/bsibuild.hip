@@ -19,7 +19,8 @@
 //   k_bsib_key_off  the batch's key CSR over its containers
 //
 // (bsiadd.hip fills the same workspace with the sum of two indexes and shares the plan, scan, write and key
-// CSR stages; its only extension is the plan's ebm_run flag.)
+// CSR stages; its only extension is the plan's ebm_run flag.  bsiin.hip fills it with one cell per key, the
+// result of an IN-list query, and passes its full-container flag through the same argument.)
 //
 // Types as in build.hip: card <= 4096 -> A, else B; with run_optimize A -> R iff 2 card > 2 + 4 nruns,
 // B -> R iff 2 + 4 nruns < 8192.

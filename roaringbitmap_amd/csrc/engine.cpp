@@ -1524,6 +1524,124 @@ static int ctx_bsi_to_pairs_host(Ctx* c, int32_t batch, int nbits, int has_found
   return RBG_OK;
 }
 
+constexpr size_t kBsiInHostSort = 1024;  // ctx_bsi_in: longer value lists are sorted on the device
+
+// BitSliceIndexBase.parallelIn(parallelism, foundSet, values, pool) (BBSI/:611-639) over the resident index
+// [ebM, bA[0..nbits-1], foundSet?] as a new one-bitmap key-major batch: what ctx_load of the reference's
+// result gives (bsiin.hip).  The set is {c in ebM & fixed : value(c) in values}, fixed = the foundSet or ebM;
+// parallelism enters through parallelExec's batchSize (BBSI/:99-136) alone, which decides whether a full
+// container is a bitmap or RunContainer.full().  values: n_values host ints in any order,
+// repeats allowed; the device gets a sorted distinct copy.  An empty fixed, ebM or list: one empty bitmap.  Two
+// read-backs: the candidate key count, then the plan's totals.  The K x 8 KiB workspace is walked in key
+// passes under bsib_budget() with the build's two-sweep scheme.
+static int ctx_bsi_in(Ctx* c, int32_t batch, int nbits, int has_found, const int32_t* values, size_t n_values,
+                      int parallelism, int32_t* out_id) {
+  hipStream_t s = c->stream;
+  if (parallelism < 1) {
+    set_err("bsi_in: parallelism must be positive");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (nbits < 0 || nbits > 32) {
+    set_err("bsi_in: an index holds at most 32 slices");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (n_values > (size_t)INT32_MAX) {
+    set_err("bsi_in: more than 2^31 - 1 values in the list");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  Batch* B;
+  BsiValArgs a;
+  CHK(bsi_val_operand(c, batch, nbits, has_found, &B, &a));
+  const size_t fx = has_found ? (size_t)nbits + 1 : 0;
+  const int64_t card = B->h_bm_card.size() > fx ? B->h_bm_card[fx] : 0;  // fixed.getCardinality(), an int
+  if (card > INT32_MAX) {
+    set_err("bsi_in: the foundSet (or ebM) holds more than 2^31 - 1 columns");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  const bool ebm_empty = B->h_bm_card.empty() || B->h_bm_card[0] == 0;
+  if (card == 0 || ebm_empty || n_values == 0) return ctx_from_values(c, nullptr, 0, false, out_id);
+  // parallelExec: batchSize = min(max(card / parallelism, parallelism), 65536) (Java int arithmetic)
+  const int64_t batch_size = std::min<int64_t>(std::max<int64_t>(card / parallelism, parallelism), 65536);
+  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
+  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
+  CHK(c->bsiv_cards.ensure(8 * (kMaxKeys + 1)));
+  CHK(c->bsiv_part.ensure(8 * (scan_parts(kMaxKeys) + 1)));
+  uint64_t* rank = c->bsiv_cards.as<uint64_t>();
+  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] the distinct list entries
+  // the list as 32-bit patterns (membership is their equality), ascending and distinct, in device memory: a
+  // short one is sorted here, a long one on the device
+  DevBuf dl, ws;  // back to the pool at the end (freed on an error)
+  size_t n_list = 0;
+  CHK(pool_take(c, dl, 4 * n_values + 16));
+  if (n_values <= kBsiInHostSort) {
+    std::vector<uint32_t> list(n_values);
+    std::memcpy(list.data(), values, 4 * n_values);
+    std::sort(list.begin(), list.end());
+    list.erase(std::unique(list.begin(), list.end()), list.end());
+    n_list = list.size();
+    CHK(upload_words(c, dl.p, list.data(), n_list));
+    HIPCHK(hipMemsetAsync(sc, 0, 64, s));
+  } else {
+    DevBuf scratch, temp;
+    const size_t tb = bsiin_sort_temp_bytes(n_values);
+    CHK(pool_take(c, scratch, 4 * n_values + 16));
+    CHK(pool_take(c, temp, tb));
+    CHK(upload_words(c, dl.p, values, n_values));
+    HIPCHK(hipMemsetAsync(sc, 0, 64, s));
+    HIPCHK((hipError_t)launch_bsiin_sort_unique(s, temp.p, tb, dl.as<uint32_t>(), scratch.as<uint32_t>(), sc + 1,
+                                                n_values));
+    pool_put(c, scratch);  // whatever takes them next is enqueued on this stream, after the sort
+    pool_put(c, temp);
+  }
+  launch_bsiin_keys(s, a, has_found, c->flag.as<uint8_t>(), rank);
+  launch_bld_keys(s, nullptr, 0, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
+  launch_exclusive_scan(s, rank, rank, kMaxKeys, c->bsiv_part.as<uint64_t>(), rank + kMaxKeys);
+  HIPCHK(hipGetLastError());
+  unsigned long long h[2] = {};
+  HIPCHK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (n_values > kBsiInHostSort) n_list = (size_t)h[1];
+  const size_t K = (size_t)h[0];
+  dbg(s, "bsi_in: keys");
+  if (K == 0) {  // ebM and the foundSet share no key
+    pool_put(c, dl);
+    return ctx_from_values(c, nullptr, 0, false, out_id);
+  }
+  constexpr int m = 1;
+  CHK(c->bsib_info.ensure(kBsibInfoBytes * K + 16));
+  CHK(c->bsib_size.ensure(8 * (K + 1)));
+  CHK(c->bsib_part.ensure(8 * (scan_parts(K) + 1)));
+  CHK(c->bsib_per.ensure(8 * (4 * (size_t)m + 4)));
+  CHK(c->bsia_run.ensure(K + 16));
+  uint64_t* size = c->bsib_size.as<uint64_t>();
+  unsigned long long* per = c->bsib_per.as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
+  const size_t P = std::min(K, std::max<size_t>(1, bsib_budget() / 8192));  // keys per pass
+  CHK(pool_take(c, ws, 8192 * P));
+  auto fill = [&](size_t k_lo, size_t k_hi) -> int {  // every cell of the pass is written: no memset
+    launch_bsi_in(s, a, has_found, dl.as<uint32_t>(), (uint32_t)n_list, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo,
+                  (uint32_t)k_hi, rank, batch_size == 65536, ws.as<uint8_t>(), c->bsia_run.as<uint8_t>());
+    return RBG_OK;
+  };
+  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+    const size_t k_hi = std::min(K, k_lo + P);
+    CHK(fill(k_lo, k_hi));
+    launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, 0, c->bsib_info.p, size, per, per + 4 * m,
+                     c->bsia_run.as<uint8_t>());
+  }
+  launch_exclusive_scan(s, size, size, K, c->bsib_part.as<uint64_t>(), size + K);
+  HIPCHK(hipGetLastError());
+  std::vector<unsigned long long> hp(4 * (size_t)m + 4);
+  uint64_t total = 0;
+  HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&total, size + K, 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  dbg(s, "bsi_in: in + plan");
+  const int st = bsib_emit(c, K, m, 1, P, ws, hp, total, fill, "bsi_in: write", out_id);  // synchronises
+  pool_put(c, dl);
+  return st;
+}
+
 // op RBG_OR_INPLACE: x1.or(x2) in place (RB/RoaringBitmap.java:2481-2523), the OR with Container.ior's
 // types (k_ior_fix)
 // RoaringBitmap.and / or / xor / andNot + serialize of a dense key range as K key ranges in one
@@ -4355,6 +4473,31 @@ int rbg_bsi_add(const uint8_t* ebm_a, size_t ebm_a_len, const uint8_t* const* sl
   CHK(ctx_bsi_add(c, ia, na, ib, nb, min_a, max_a, &id, out3));
   os.adopt(id);
   return ctx_batch_fetch_range(c, id, 0, 1 + (size_t)out3[0], outs);
+}
+
+/* ---- BitSliceIndexBase.parallelIn (BBSI/:611-639; bsiin.hip) ---- */
+
+int rbg_ctx_bsi_in(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const int32_t* values, size_t n_values,
+                   int parallelism, int32_t* out_batch) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!out_batch || (n_values && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_in(c, batch, nbits, has_found != 0, values, n_values, parallelism, out_batch);
+}
+
+int rbg_bsi_in(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens, int nbits,
+               const uint8_t* found, size_t found_len, const int32_t* values, size_t n_values, int parallelism,
+               rbg_buffer* out) {
+  if (!out || nbits < 0 || nbits > 32 || parallelism < 1 || (n_values && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (!ebm || (nbits && (!slices || !slice_lens))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id, res;
+  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, (size_t)nbits, found, found_len, &id));
+  CHK(ctx_bsi_in(c, id, nbits, found ? 1 : 0, values, n_values, parallelism, &res));
+  os.adopt(res);
+  return ctx_batch_fetch_range(c, res, 0, 1, out);
 }
 
 int rbg_bsi_get_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,

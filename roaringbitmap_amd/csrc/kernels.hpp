@@ -593,6 +593,23 @@ void launch_bsi_pair_cards(hipStream_t s, BsiValArgs a, uint64_t* cards);
 void launch_bsi_pairs(hipStream_t s, BsiValArgs a, const uint64_t* base, bool cols64, bool vals64, void* cols,
                       void* vals);
 
+// bsiin.hip: the buffer package's parallelIn (BBSI/:611-639) over a key-major batch [ebM, bA[0..nbits-1],
+// foundSet?] into the workspace layout of the build above with m = 1 cell per candidate key
+constexpr uint32_t kBsiInLdsList = 4096;  // value lists up to this length are searched in LDS (16 KiB)
+// list[0..n) (n < 2^31) sorted ascending with repeats dropped, in place; *n_out (device) = the entries left.
+// scratch: n u32; temp: bsiin_sort_temp_bytes(n) bytes.  -> hipError_t
+size_t bsiin_sort_temp_bytes(uint64_t n);
+int launch_bsiin_sort_unique(hipStream_t s, void* temp, size_t temp_bytes, uint32_t* list, uint32_t* scratch,
+                             unsigned long long* n_out, uint64_t n);
+// flag[key] = 1 for every candidate key (65,536 bytes, all written); cards[key] = cardinality of the
+// container of the foundSet (has_found) or of ebM under the key (65,536 u64), to be scanned
+void launch_bsiin_keys(hipStream_t s, BsiValArgs a, int has_found, uint8_t* flag, uint64_t* cards);
+// one pass over the candidate key indices [k_lo, k_hi): writes every cell of the pass and run[k_lo..k_hi).
+// list: n >= 1 ascending distinct values (as unsigned bit patterns); rank: the exclusive scan of cards;
+// aligned: parallelExec's batchSize is 65,536
+void launch_bsi_in(hipStream_t s, BsiValArgs a, int has_found, const uint32_t* list, uint32_t n, const uint16_t* pkeys,
+                   uint32_t k_lo, uint32_t k_hi, const uint64_t* rank, bool aligned, uint8_t* ws, uint8_t* run);
+
 // decode.hip: portable-format decode on the device
 enum DecErr : uint32_t {
   DEC_OK = 0,

@@ -22,6 +22,16 @@ def synth_key_bytes(kind, seed, n) -> np.ndarray:
     return out
 
 
+def _in_list(values):
+    """the value list of an IN query as contiguous int32: Java ints, or their unsigned bit patterns"""
+    if isinstance(values, np.ndarray) and values.dtype in (np.int32, np.uint32):
+        return np.ascontiguousarray(values.reshape(-1)).view(np.int32)
+    v = np.asarray(values if isinstance(values, np.ndarray) else list(values), dtype=np.int64).reshape(-1)
+    if v.size and (v.min() < -(1 << 31) or v.max() >= 1 << 32):
+        raise _lib.IllegalArgumentException("the values of an IN list must fit 32 bits")
+    return np.ascontiguousarray(v.astype(np.uint32).view(np.int32))
+
+
 class Engine:
     def __init__(self, device=0):
         self._ctx = ctypes.c_void_p()
@@ -444,6 +454,22 @@ class Engine:
         check(lib().rbg_ctx_bsi_add(self._ctx, int(a), int(nbits_a), int(b), int(nbits_b), int(min_a), int(max_a),
                                     ctypes.byref(out), out3))
         return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+
+    def bsi_in(self, batch, nbits, values, parallelism=1, has_found=False) -> int:
+        """BitSliceIndexBase.parallelIn (BBSI/:611-639), WHERE value IN (values), over a resident index
+        [ebM, bA[0..nbits-1], foundSet?] in one fused device pass (rbg_ctx_bsi_in) -> batch id of a new
+        one-bitmap batch: the columns of ebM (and of the foundSet) whose value is in the list, as the batch
+        load() of the reference's result gives -- usable in pairwise, to_values and batch_fetch.  values: any
+        iterable of ints that fit 32 bits (a negative entry is its bit pattern: it matches only with 32
+        slices), in any order, repeats allowed.  parallelism only decides whether a full container is a
+        bitmap or a run container.  parallelism < 1, nbits > 32 or a batch of another shape:
+        IllegalArgumentException, no batch made.  Synchronous."""
+        v = _in_list(values)
+        out = ctypes.c_int32()
+        check(lib().rbg_ctx_bsi_in(self._ctx, int(batch), int(nbits), int(bool(has_found)),
+                                   v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), v.size, int(parallelism),
+                                   ctypes.byref(out)))
+        return out.value
 
     def bsi_get_values(self, batch, nbits, columns, has_found=False):
         """getValue for many columns at once against a resident index [ebM, bA[0..nbits-1], foundSet?]
