@@ -22,6 +22,16 @@ class BSI:
     def __init__(self, ebm, slices, min_value, max_value, run_optimized=False):
         self.ebm, self.ba, self.min, self.max = ebm, list(slices), int(min_value), int(max_value)
         self.run_optimized = bool(run_optimized)
+        # opt-in ({} instead of None): the circuits' chains, which depend on the predicate alone, are kept
+        # between queries on an index that is no longer modified (the many-key tests run hundreds)
+        self.memo = None
+
+    def _memo(self, key, make):
+        if self.memo is None:
+            return make()
+        if key not in self.memo:
+            self.memo[key] = make()
+        return self.memo[key]
 
     @classmethod
     def from_columns(cls, columns, values, run_optimize=False):
@@ -63,6 +73,7 @@ class BSI:
                 x = O.run_optimize(x)
             new.append(x)
         self.ba = new
+        self.memo = None if self.memo is None else {}
         self.ebm = O.pairwise("ior", self.ebm, other.ebm)  # this.ebM.or(otherBsi.ebM), in place
         self.run_optimized = self.run_optimized or other.run_optimized
         self.max = max(self.max, other.max)
@@ -84,14 +95,19 @@ class BSI:
     # BSI/:432-468
     def _oneil(self, op, predicate, found):
         fixed = self.ebm if found is None else found
-        gt, lt, eq = EMPTY, EMPTY, self.ebm
-        for i in range(self.bit_count() - 1, -1, -1):
-            if (predicate >> i) & 1:
-                lt = O.pairwise("or", lt, O.pairwise("andnot", eq, self.ba[i]))
-                eq = O.pairwise("and", eq, self.ba[i])
-            else:
-                gt = O.pairwise("or", gt, O.pairwise("and", eq, self.ba[i]))
-                eq = O.pairwise("andnot", eq, self.ba[i])
+
+        def chain():
+            gt, lt, eq = EMPTY, EMPTY, self.ebm
+            for i in range(self.bit_count() - 1, -1, -1):
+                if (predicate >> i) & 1:
+                    lt = O.pairwise("or", lt, O.pairwise("andnot", eq, self.ba[i]))
+                    eq = O.pairwise("and", eq, self.ba[i])
+                else:
+                    gt = O.pairwise("or", gt, O.pairwise("and", eq, self.ba[i]))
+                    eq = O.pairwise("andnot", eq, self.ba[i])
+            return gt, lt, eq
+
+        gt, lt, eq = self._memo(("oneil", predicate), chain)
         eq = O.pairwise("and", fixed, eq)
         if op == "EQ":
             return eq
@@ -197,18 +213,23 @@ class BufferBSI(BSI):
     # BBSI/:190-234
     def _oneil_buf(self, op, predicate, found):
         fixed = self.ebm if found is None else found
-        gt = EMPTY if op in ("GT", "GE") else None
-        lt = EMPTY if op in ("LT", "LE") else None
-        eq = self.ebm
-        for i in range(self.bit_count() - 1, -1, -1):
-            if (predicate >> i) & 1:
-                if lt is not None:
-                    lt = O.pairwise("or", lt, self._andnot(eq, self.ba[i]))
-                eq = self._and(eq, self.ba[i])
-            else:
-                if gt is not None:
-                    gt = O.pairwise("or", gt, self._and(eq, self.ba[i]))
-                eq = self._andnot(eq, self.ba[i])
+
+        def chain():
+            gt = EMPTY if op in ("GT", "GE") else None
+            lt = EMPTY if op in ("LT", "LE") else None
+            eq = self.ebm
+            for i in range(self.bit_count() - 1, -1, -1):
+                if (predicate >> i) & 1:
+                    if lt is not None:
+                        lt = O.pairwise("or", lt, self._andnot(eq, self.ba[i]))
+                    eq = self._and(eq, self.ba[i])
+                else:
+                    if gt is not None:
+                        gt = O.pairwise("or", gt, self._and(eq, self.ba[i]))
+                    eq = self._andnot(eq, self.ba[i])
+            return gt, lt, eq
+
+        gt, lt, eq = self._memo(("oneil_buf", predicate, op in ("GT", "GE"), op in ("LT", "LE")), chain)
         if op not in ("LT", "GT"):
             eq = self._and(fixed, eq)
         if op == "EQ":
@@ -242,13 +263,17 @@ class BufferBSI(BSI):
         b = _i32(predicate - 1)
         nb = _i32(~b)
         lsz = 64 if nb == 0 else ((nb & 0xFFFFFFFF) & -(nb & 0xFFFFFFFF)).bit_length() - 1
-        spine, inputs = None, []
-        for w in range(self.bit_count() - 1, lsz - 1, -1):
-            if (b & (1 << w)) == 0:
-                inputs.append(self.ba[w] if spine is None else self._and(spine, self.ba[w]))
-            else:
-                spine = self.ba[w] if spine is None else self._and(spine, self.ba[w])
-        res = O.wide("horizontal_or", inputs) if inputs else EMPTY
+
+        def chain():
+            spine, inputs = None, []
+            for w in range(self.bit_count() - 1, lsz - 1, -1):
+                if (b & (1 << w)) == 0:
+                    inputs.append(self.ba[w] if spine is None else self._and(spine, self.ba[w]))
+                else:
+                    spine = self.ba[w] if spine is None else self._and(spine, self.ba[w])
+            return O.wide("horizontal_or", inputs) if inputs else EMPTY
+
+        res = self._memo(("owen", predicate), chain)
         return res if found is None else self._and(res, found)
 
     # BBSI/:351-375

@@ -180,5 +180,54 @@ def sparse_bitmap(rng, keys, heavy_every=97, run_every=0):
     return encode(ctrs)
 
 
+def sparse_bsi(rng, n_keys=6000, nbits=20):
+    """(keys, cols, vals) of a many-key bit-sliced index: ascending distinct columns and their values.
+
+    Keys in the style of sparse_keys: 0..299 dense, a hole of 316 keys around one whole 256-key plan workgroup
+    (2 or 3) with a key on either side, a dense middle block of n_keys // 2 keys, blocks of 1, 2, 3 and 5
+    adjacent keys at random places up to n_keys in all, and keys 65534 and 65535.
+    Columns per key (ebM's containers): the union of two tiny_values draws (2 to 16 values, low, high or both,
+    so that a mid-range predicate usually splits a key); every third key 4 to 11 adjacent values below 2,000
+    and 1 to 6 above 63,000 (a two-run run container once run-optimized); every 97th key a random MODES
+    container (bitmaps, run containers above 2,047 runs, full containers).
+    Values: uniform in [0, 2^nbits), but under keys with key % 3 == 1 the clustered
+    (low // 3000 + 37 * (key % 7)) % 2^nbits: long runs in the low slices, no container at all in the high
+    ones, and a few values that thousands of columns share; under every other two-run key the uniform values
+    ascend with the column, so that < and > select a prefix or suffix of the runs (a run result that is no
+    clone of an input once the index is run-optimized)."""
+    g = int(rng.integers(2, 4))
+    hole_lo, hole_hi = 256 * g - 30, 256 * (g + 1) + 30  # [hole_lo, hole_hi) holds no key
+    mid = int(rng.integers(26000, 34000))
+    have = np.zeros(65536, dtype=bool)
+    have[:300] = True
+    have[mid:mid + n_keys // 2] = True
+    have[[hole_lo - 1, hole_hi, 65534, 65535]] = True
+    while int(have.sum()) < n_keys:
+        n = (1, 2, 3, 5)[int(rng.integers(4))]
+        k = int(rng.integers(0, 65536 - n))
+        if k + n <= hole_lo or k >= hole_hi:
+            have[k:k + n] = True
+    keys = np.nonzero(have)[0]
+    cols, vals = [], []
+    for i, k in enumerate(keys):
+        k = int(k)
+        if i % 97 == 96:
+            low = container(rng, MODES[int(rng.integers(len(MODES)))])[1].astype(np.int64)
+        elif i % 3 == 0:
+            s, t = int(rng.integers(0, 1989)), int(rng.integers(63000, 65530))
+            low = np.concatenate([np.arange(s, s + int(rng.integers(4, 12))), np.arange(t, t + int(rng.integers(1, 7)))])
+        else:
+            low = np.union1d(tiny_values(rng, rng.random()), tiny_values(rng, rng.random())).astype(np.int64)
+        if k % 3 == 1:
+            v = (low // 3000 + 37 * (k % 7)) % (1 << nbits)
+        else:
+            v = rng.integers(0, 1 << nbits, low.size)
+            if i % 6 == 0:  # ascending with the column: < and > select a prefix / suffix of the two runs
+                v = np.sort(v)
+        cols.append((k << 16) + low)
+        vals.append(v)
+    return keys, np.concatenate(cols).astype(np.int64), np.concatenate(vals).astype(np.int64)
+
+
 def random_values(rng, n, universe=1 << 32):
     return rng.integers(0, universe, size=n, dtype=np.int64).astype(np.uint32)
