@@ -315,6 +315,24 @@ int rbg_bsi_add(const uint8_t* ebm_a, size_t ebm_a_len, const uint8_t* const* sl
 int rbg_bsi_in(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens, int nbits,
                const uint8_t* found, size_t found_len, const int32_t* values, size_t n_values, int parallelism,
                rbg_buffer* out);
+/* BitSliceIndexBase.parallelTransposeWithCount(foundSet, parallelism, pool) of the buffer package's index
+ * (buffer/BitSliceIndexBase.java:551-597): GROUP BY value / COUNT(*).  The result is a new index whose column
+ * ids are the distinct 32-bit values of the columns in ebM and fixed (fixed = the foundSet, or ebM when found
+ * is NULL; with 32 slices bit 31 gives a column >= 2^31) and whose values are how many columns held each:
+ * outs[0] = ebM, outs[1 + i] = bA[i] as portable bytes (outs must have room for 33 buffers; 1 + out3[0] are
+ * written, each released with rbg_free), out3 = {bit count, minValue, maxValue}, the bit count being that of
+ * the largest count and min / max the smallest and largest count.  The bytes are the reference's:
+ * parallelExec (:99-136) cuts fixed into batches of min(max(cardinality(fixed) / parallelism, parallelism),
+ * 65536) columns, transposeWithCount (:551-567) builds one index per batch with setValue, and the batches
+ * are summed in order with MutableBitSliceIndex.add (buffer/MutableBitSliceIndex.java:201-219).  Every
+ * container is typed by its cardinality (array up to 4096, bitmap above) except a full container of ebM, which
+ * is a run container of one run when a batch of more than 4096 distinct values of its key completes or
+ * follows the full union and is not the first batch that contributes (Container.ior).  No column of fixed in
+ * ebM: the empty ebM alone and out3 = {0, 0, 0}.  RBG_ERR_ILLEGAL_ARGUMENT: parallelism < 1 (the reference
+ * divides by it), nbits > 32, more than 2^31 - 1 columns in fixed (its getCardinality() is an int). */
+int rbg_bsi_transpose(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
+                      int nbits, const uint8_t* found, size_t found_len, int parallelism, rbg_buffer* outs,
+                      int32_t* out3);
 
 /* Releases an output.  Large results (>= 8 MiB, 2 MiB-aligned huge-page buffers) are kept for
  * reuse by the next large result, at most two of them, so a caller's steady stream of big results
@@ -555,6 +573,22 @@ int rbg_ctx_bsi_add(rbg_ctx* ctx, int32_t batch_a, int nbits_a, int32_t batch_b,
  * rbg_ctx_bsi_from_columns' byte budget (RBG_BSI_BUILD_WS).  Synchronous. */
 int rbg_ctx_bsi_in(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const int32_t* values, size_t n_values,
                    int parallelism, int32_t* out_batch);
+/* BitSliceIndexBase.parallelTransposeWithCount (buffer/BitSliceIndexBase.java:551-597; rbg_bsi_transpose
+ * above) over a resident index, the key-major unpacked batch [ebM, bA[0..nbits-1], foundSet if has_found]
+ * with any container types, as a new batch [ebM', bA'[0..n'-1]]: field for field what rbg_ctx_load of the
+ * reference's result bitmaps gives, usable wherever a built or loaded index is (bsi, bsi_buffer,
+ * bsi_get_values, bsi_to_pairs, bsi_add, bsi_in).  out3 = {n', minValue, maxValue}.  The operand stays as it
+ * is.  No column of the foundSet (or ebM) in ebM: a live batch of one empty bitmap, out3 = {0, 0, 0}, made
+ * without a kernel.  RBG_ERR_ILLEGAL_ARGUMENT, with no batch made: parallelism < 1, nbits > 32, a batch that
+ * is not key-major, is packed or does not hold 1 + nbits + has_found bitmaps, more than 2^31 - 1 columns in
+ * the foundSet (or ebM).  The workspace (per result key, value >> 16: a count table of 256 KiB and one 8 KiB
+ * bitmap per possible count bit and for ebM') is walked in passes under rbg_ctx_bsi_from_columns' byte budget
+ * (RBG_BSI_BUILD_WS).  An index of fewer than 256 columns per result key whose result cannot hold a run
+ * container (batches of at most 4096 columns, or one batch) is sorted, run-length encoded and built from the
+ * (value, count) pairs instead: the same bytes (RBG_BSI_TR_ROUTE=count|sort, read at every call, forces a route
+ * where it is exact).  Synchronous. */
+int rbg_ctx_bsi_transpose(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int parallelism, int32_t* out_batch,
+                          int32_t* out3);
 /* RoaringBitmapSliceIndex.getValue (RoaringBitmapSliceIndex.java:181-196) for n columns against a batch
  * [ebM, bA[0..nbits-1], foundSet?] (has_found: the batch ends with a foundSet, which is ignored), the
  * loop of the buffer package's batchIn / transposeWithCount (buffer/BitSliceIndexBase.java:551-639):

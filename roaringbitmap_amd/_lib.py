@@ -56,7 +56,7 @@ EXPORTED = [
     "rbg_ctx_to_values", "rbg_ctx_to_values_device",
     "rbg_bsi_from_columns", "rbg_bsi_get_values", "rbg_ctx_bsi_from_columns", "rbg_ctx_bsi_from_columns_device",
     "rbg_ctx_bsi_get_values", "rbg_ctx_bsi_get_values_device", "rbg_ctx_bsi_to_pairs", "rbg_ctx_bsi_to_pairs_device",
-    "rbg_bsi_add", "rbg_ctx_bsi_add", "rbg_bsi_in", "rbg_ctx_bsi_in",
+    "rbg_bsi_add", "rbg_ctx_bsi_add", "rbg_bsi_in", "rbg_ctx_bsi_in", "rbg_bsi_transpose", "rbg_ctx_bsi_transpose",
 ]
 
 _lib = None
@@ -111,6 +111,8 @@ def _declare(L):
     L.rbg_ctx_bsi_add.argtypes = [vp, i32, ci, i32, ci, i32, i32, i32p, i32p]
     L.rbg_bsi_in.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, u8p, sz, i32p, sz, ci, buf]
     L.rbg_ctx_bsi_in.argtypes = [vp, i32, ci, ci, i32p, sz, ci, i32p]
+    L.rbg_bsi_transpose.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, u8p, sz, ci, vp, i32p]
+    L.rbg_ctx_bsi_transpose.argtypes = [vp, i32, ci, ci, ci, i32p, i32p]
     L.rbg_select_range.argtypes = [u8p, sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, buf]
     L.rbg_ctx_add_offset.argtypes = [vp, i32, sz, ctypes.c_int64]
     L.rbg_ctx_select_range.argtypes = [vp, i32, ctypes.c_int64, ctypes.c_int64, P(i32)]

@@ -12,7 +12,8 @@ device (csrc/bsibuild.hip), and getValues / toPairList read values back in bulk 
 gpu=True).  add(otherBsi) (BSI/:66-95) sums two indexes in one fused device pass (csrc/bsiadd.hip) when
 neither holds a run container, and replays the reference's and / xor chain with the pairwise device ops
 otherwise.  The buffer index's parallelIn (BBSI/:611-639), WHERE value IN (...), is one fused pass too
-(csrc/bsiin.hip).
+(csrc/bsiin.hip), and its parallelTransposeWithCount (BBSI/:551-597), GROUP BY value / COUNT(*), one device
+call (csrc/bsitr.hip).
 """
 import ctypes
 import os
@@ -300,6 +301,28 @@ class BitSliceIndexBase(RoaringBitmapSliceIndex):
                                v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), v.size, int(parallelism),
                                ctypes.byref(out)))
         return RoaringBitmap(take(out))
+
+    def parallelTransposeWithCount(self, foundSet, parallelism, pool=None):
+        """BBSI/:551-597 parallelTransposeWithCount(foundSet, parallelism, pool) -> a new index of the same
+        class: GROUP BY value / COUNT(*).  Its column ids are the distinct values of the columns of ebM, within
+        foundSet unless it is None, and its values are how many columns held each; bitCount() is the bit
+        length of the largest count, minValue / maxValue the smallest and largest count.  One device call
+        (rbg_bsi_transpose, csrc/bsitr.hip).  pool is accepted and ignored, as in parallelIn; parallelism
+        decides parallelExec's batch size and with it whether a full container of the result's ebM is a
+        bitmap or a run container."""
+        if int(parallelism) < 1:
+            raise IllegalArgumentException("parallelTransposeWithCount: parallelism must be positive")
+        if len(self.bA) > 32:
+            raise IllegalArgumentException("parallelTransposeWithCount: an index holds at most 32 slices")
+        arr, lens = self._slices()
+        e = self.ebM.serialize()
+        f = foundSet.serialize() if foundSet is not None else None
+        outs = (_lib.rbg_buffer * 33)()
+        out3 = (ctypes.c_int32 * 3)()
+        check(lib().rbg_bsi_transpose(e, len(e), arr, lens, len(self.bA), f, len(f) if f else 0, int(parallelism),
+                                      outs, out3))
+        bms = [RoaringBitmap(take(outs[k])) for k in range(1 + int(out3[0]))]
+        return type(self)(bms[0], bms[1:], int(out3[1]), int(out3[2]))
 
     def _compare(self, op, start, end, foundSet):
         arr, lens = self._slices()

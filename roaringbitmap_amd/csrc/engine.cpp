@@ -186,6 +186,9 @@ struct Ctx {
   // table, the cells' size words (scanned in place) and scan scratch, the per-input totals
   DevBuf bsib_pkeys, bsib_pkoff, bsib_info, bsib_size, bsib_part, bsib_per;
   DevBuf bsia_run;  // the sum of two indexes (bsiadd.hip): per present key, ebM' is a full run container
+  // parallelTransposeWithCount (bsitr.hip): the candidate input keys and their CSR, the result-key flags, per
+  // result key its distinct values and whether it is full
+  DevBuf bsit_ckeys, bsit_ckoff, bsit_rflag, bsit_kcard, bsit_full;
   DevBuf bsiv_cards, bsiv_part;  // toPairList (bsival.hip): ebM's cardinality per key (scanned in place)
   DevBuf gather_items, gather_out;  // batch fetch: slot gather list and download buffer
   DevBuf order;                     // horizontal_*: chain order of every key segment
@@ -1640,6 +1643,292 @@ static int ctx_bsi_in(Ctx* c, int32_t batch, int nbits, int has_found, const int
   const int st = bsib_emit(c, K, m, 1, P, ws, hp, total, fill, "bsi_in: write", out_id);  // synchronises
   pool_put(c, dl);
   return st;
+}
+
+// The full result keys of a transpose that are RunContainer.full(): per key, over the batches
+// of parallelExec that contribute a value to it in order, d_t distinct values in batch t and U_t in the union
+// after it; a run container iff some t >= 2 has U_t == 65536 and d_t > 4096 (Container.ior's full union with
+// a bitmap on the other side).  rank[] / val[]: (rank in fixed, value) of every column whose value lies in a
+// full key, in any order; slot[value >> 16]: the key's index, or -1.
+static void bsit_full_runs(const std::vector<uint32_t>& rank, const std::vector<uint32_t>& val, size_t n,
+                           const std::vector<int32_t>& slot, uint64_t batch_size, std::vector<uint8_t>& run) {
+  std::vector<std::vector<uint64_t>> per(run.size());  // batch << 16 | low half of the value
+  for (size_t i = 0; i < n; i++) {
+    const int32_t ki = slot[val[i] >> 16];
+    if (ki >= 0) per[(size_t)ki].push_back(((uint64_t)rank[i] / batch_size) << 16 | (val[i] & 0xFFFFu));
+  }
+  std::vector<uint8_t> seen(65536);
+  for (size_t ki = 0; ki < per.size(); ki++) {
+    std::vector<uint64_t>& v = per[ki];
+    if (v.empty()) continue;
+    std::sort(v.begin(), v.end());
+    v.erase(std::unique(v.begin(), v.end()), v.end());
+    std::fill(seen.begin(), seen.end(), 0);
+    size_t uni = 0, t = 0;
+    for (size_t i = 0; i < v.size();) {
+      size_t j = i;
+      while (j < v.size() && (v[j] >> 16) == (v[i] >> 16)) {
+        if (!seen[v[j] & 0xFFFFu]) seen[v[j] & 0xFFFFu] = 1, uni++;
+        j++;
+      }
+      t++;
+      if (t >= 2 && uni == 65536 && j - i > 4096) run[ki] = 1;
+      i = j;
+    }
+  }
+}
+
+// ctx_bsi_transpose: below this many columns per result key (an upper bound: min(card(ebM), card(fixed)) / K')
+// the sort route runs.  Measured at 32 (the count tables lose 17 x) and at 16,384 (they win); not tuned between.
+constexpr uint64_t kBsitSparse = 256;
+
+// BitSliceIndexBase.parallelTransposeWithCount(foundSet, parallelism, pool) (BBSI/:551-597) over the resident
+// index [ebM, bA[0..nbits-1], foundSet?] as a new key-major batch [ebM', bA'[0..nbits'-1]]: what ctx_load of
+// the reference's result gives (bsitr.hip).  The result's columns are the distinct 32-bit values of the
+// columns in ebM & fixed (fixed = the foundSet or ebM), its values their counts; out3 = {nbits', min, max}.
+// parallelism enters through parallelExec's batchSize (BBSI/:99-136) alone, which decides whether a full
+// result key is a bitmap or RunContainer.full().  No column of fixed in ebM: one empty bitmap,
+// {0, 0, 0}.  Read-backs: the result key count, then the plan's totals with min / max and the number of full
+// keys.  Per result key the workspace holds m = 1 + bitlen(min(card(ebM), card(fixed))) cells of 8 KiB (no
+// count exceeds that many bits) and a count table of 256 KiB, walked in key passes under bsib_budget() with
+// the build's two-sweep scheme.  Only when a key is full, batchSize > 4096 and fixed spans two batches: the
+// values of the full keys are set in one bitmap per (full key, batch), a workgroup per full key applies the
+// rule over its batches (above the byte budget: the (rank, value) pairs go to the host instead), and the plan
+// runs again.
+static int ctx_bsi_transpose(Ctx* c, int32_t batch, int nbits, int has_found, int parallelism, int32_t* out_id,
+                             int32_t* out3) {
+  hipStream_t s = c->stream;
+  out3[0] = out3[1] = out3[2] = 0;
+  if (parallelism < 1) {
+    set_err("bsi_transpose: parallelism must be positive");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (nbits < 0 || nbits > 32) {
+    set_err("bsi_transpose: an index holds at most 32 slices");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  Batch* B;
+  BsiValArgs a;
+  CHK(bsi_val_operand(c, batch, nbits, has_found, &B, &a));
+  const size_t fx = has_found ? (size_t)nbits + 1 : 0;
+  const int64_t card = B->h_bm_card.size() > fx ? B->h_bm_card[fx] : 0;  // fixed.getCardinality(), an int
+  if (card > INT32_MAX) {
+    set_err("bsi_transpose: the foundSet (or ebM) holds more than 2^31 - 1 columns");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  const int64_t ebm_card = B->h_bm_card.empty() ? 0 : B->h_bm_card[0];
+  if (card == 0 || ebm_card == 0) return ctx_from_values(c, nullptr, 0, false, out_id);
+  // parallelExec: batchSize = min(max(card / parallelism, parallelism), 65536) (Java int arithmetic)
+  const int64_t batch_size = std::min<int64_t>(std::max<int64_t>(card / parallelism, parallelism), 65536);
+  const uint32_t grid = B->h_bm_nctr[0];  // the keys of ebM: every candidate key is one of them
+  CHK(c->bsit_ckeys.ensure(2 * kMaxKeys + 16));
+  CHK(c->bsit_ckoff.ensure(4 * (kMaxKeys + 1)));
+  CHK(c->bsit_rflag.ensure(kMaxKeys));
+  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
+  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
+  CHK(c->bsiv_cards.ensure(8 * (kMaxKeys + 1)));
+  CHK(c->bsiv_part.ensure(8 * (scan_parts(kMaxKeys) + 1)));
+  uint64_t* rank = c->bsiv_cards.as<uint64_t>();
+  // [0] candidate keys, [1] K' result keys, [2] {min, max} as two u32, [3] full result keys, [4] pairs
+  unsigned long long* sc = c->scalar.as<unsigned long long>();
+  static const uint32_t kMinMaxInit[2] = {0xFFFFFFFFu, 0u};
+  HIPCHK(hipMemsetAsync(sc, 0, 64, s));
+  HIPCHK(hipMemcpyAsync(sc + 2, kMinMaxInit, 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemsetAsync(c->bsit_rflag.p, 0, kMaxKeys, s));
+  launch_bsiin_keys(s, a, has_found, c->flag.as<uint8_t>(), rank);
+  launch_bld_keys(s, nullptr, 0, c->flag.as<uint8_t>(), c->bsit_ckeys.as<uint16_t>(), c->bsit_ckoff.as<uint32_t>(), sc);
+  launch_exclusive_scan(s, rank, rank, kMaxKeys, c->bsiv_part.as<uint64_t>(), rank + kMaxKeys);
+  BsiTrSweep sw{};
+  sw.rflag = c->bsit_rflag.as<uint8_t>();
+  launch_bsitr_sweep(s, 0, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, sw);
+  launch_bld_keys(s, nullptr, 0, c->bsit_rflag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(),
+                  sc + 1);
+  HIPCHK(hipGetLastError());
+  unsigned long long h[2] = {};
+  HIPCHK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  dbg(s, "bsi_transpose: keys");
+  const size_t K = (size_t)h[1];  // result keys
+  if (K == 0) return ctx_from_values(c, nullptr, 0, false, out_id);  // no column of fixed is in ebM
+  const uint64_t most = (uint64_t)std::min<int64_t>(card, ebm_card);  // no count is larger
+  // Sparse shapes (fewer than kBsitSparse columns per result key): a count table of 256 KiB per key would be
+  // zeroed and read for a handful of counts, so the values are sorted and run-length encoded instead and the
+  // (value, count) pairs go through the build, whose containers are typed by cardinality.  That is the
+  // reference's answer whenever no run container can appear (batchSize <= 4096 or a single batch); a call
+  // that could produce one keeps the count tables.  RBG_BSI_TR_ROUTE=count|sort (read at every call) forces
+  // a route where it is exact.
+  const bool no_run = batch_size <= 4096 || card <= batch_size;
+  bool sparse = most < kBsitSparse * (uint64_t)K;
+  if (const char* e = std::getenv("RBG_BSI_TR_ROUTE")) sparse = e[0] == 's' ? true : e[0] == 'c' ? false : sparse;
+  if (sparse && no_run) {
+    DevBuf dv, ds, du, dn, temp;
+    const size_t tb = bsitr_sort_temp_bytes(most);
+    CHK(pool_take(c, dv, 4 * most + 16));
+    CHK(pool_take(c, ds, 4 * most + 16));
+    CHK(pool_take(c, du, 4 * most + 16));
+    CHK(pool_take(c, dn, 4 * most + 16));
+    CHK(pool_take(c, temp, tb));
+    BsiTrSweep p{};
+    p.n_pairs = sc + 4;
+    p.out_val = dv.as<uint32_t>();
+    p.cap = most;
+    launch_bsitr_sweep(s, 3, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, p);
+    HIPCHK(hipGetLastError());
+    unsigned long long n = 0, runs = 0;
+    HIPCHK(hipMemcpyAsync(&n, sc + 4, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    n = std::min<unsigned long long>(n, most);
+    HIPCHK((hipError_t)launch_bsitr_sort_rle(s, temp.p, tb, dv.as<uint32_t>(), ds.as<uint32_t>(), du.as<uint32_t>(),
+                                             dn.as<int32_t>(), sc + 5, n));
+    HIPCHK(hipMemcpyAsync(&runs, sc + 5, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    dbg(s, "bsi_transpose: sort + run lengths");
+    const int st = ctx_bsi_from_columns(c, du.as<uint32_t>(), dn.as<int32_t>(), (size_t)runs, false, out_id, out3);
+    pool_put(c, dv);  // whatever takes them next is enqueued on this stream, after the build
+    pool_put(c, ds);
+    pool_put(c, du);
+    pool_put(c, dn);
+    pool_put(c, temp);
+    return st;
+  }
+  const int m = 1 + (64 - __builtin_clzll(most));
+  const size_t cells = K * (size_t)m;
+  CHK(c->bsib_info.ensure(kBsibInfoBytes * cells + 16));
+  CHK(c->bsib_size.ensure(8 * (cells + 1)));
+  CHK(c->bsib_part.ensure(8 * (scan_parts(cells) + 1)));
+  CHK(c->bsib_per.ensure(8 * (4 * (size_t)m + 4)));
+  CHK(c->bsia_run.ensure(K + 16));
+  CHK(c->bsit_kcard.ensure(4 * K + 16));
+  CHK(c->bsit_full.ensure(K + 16));
+  uint64_t* size = c->bsib_size.as<uint64_t>();
+  unsigned long long* per = c->bsib_per.as<unsigned long long>();
+  HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
+  HIPCHK(hipMemsetAsync(c->bsia_run.p, 0, K, s));
+  HIPCHK(hipMemsetAsync(c->bsit_kcard.p, 0, 4 * K, s));
+  HIPCHK(hipMemsetAsync(c->bsit_full.p, 0, K, s));
+  constexpr size_t kTab = 4 * 65536;  // a result key's count table
+  const size_t per_key = kTab + 8192 * (size_t)m;
+  const size_t P = std::min(K, std::max<size_t>(1, bsib_budget() / per_key));  // result keys per pass
+  DevBuf ws;  // the cells of a pass, then its count tables; back to the pool at the end (freed on an error)
+  CHK(pool_take(c, ws, per_key * P));
+  uint32_t* tab = reinterpret_cast<uint32_t*>(ws.as<uint8_t>() + 8192 * (size_t)m * P);
+  sw.rkoff = c->bsib_pkoff.as<uint32_t>();
+  sw.tab = tab;
+  auto fill_stats = [&](size_t k_lo, size_t k_hi, bool stats) -> int {  // every cell of the pass is written
+    HIPCHK(hipMemsetAsync(tab, 0, kTab * (k_hi - k_lo), s));
+    BsiTrSweep p = sw;
+    p.k_lo = (uint32_t)k_lo;
+    p.k_hi = (uint32_t)k_hi;
+    launch_bsitr_sweep(s, 1, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, p);
+    launch_bsitr_cells(s, tab, (uint32_t)k_lo, (uint32_t)k_hi, m, ws.as<uint8_t>(), stats,
+                       reinterpret_cast<uint32_t*>(sc + 2), c->bsit_kcard.as<uint32_t>(), c->bsit_full.as<uint8_t>(),
+                       sc + 3);
+    return RBG_OK;
+  };
+  auto fill = [&](size_t k_lo, size_t k_hi) -> int { return fill_stats(k_lo, k_hi, false); };
+  std::vector<unsigned long long> hp(4 * (size_t)m + 4);
+  uint64_t total = 0;
+  unsigned long long h3[2] = {};  // {min, max}, full keys
+  auto plan_all = [&](bool first) -> int {
+    for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+      const size_t k_hi = std::min(K, k_lo + P);
+      if (first || P < K) CHK(fill_stats(k_lo, k_hi, first));
+      launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, 0, c->bsib_info.p, size, per, per + 4 * m,
+                       c->bsia_run.as<uint8_t>());
+    }
+    launch_exclusive_scan(s, size, size, cells, c->bsib_part.as<uint64_t>(), size + cells);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&total, size + cells, 8, hipMemcpyDeviceToHost, s));
+    if (first) HIPCHK(hipMemcpyAsync(h3, sc + 2, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    return RBG_OK;
+  };
+  CHK(plan_all(true));
+  dbg(s, "bsi_transpose: count + plan");
+  if (h3[1] && batch_size > 4096 && card > batch_size) {  // a full key fed by several batches of bitmap size
+    const size_t n_full = (size_t)h3[1];
+    const size_t n_batches = (size_t)((card + batch_size - 1) / batch_size);
+    std::vector<uint8_t> isfull(K);
+    HIPCHK(hipMemcpyAsync(isfull.data(), c->bsit_full.p, K, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (n_full * n_batches * 8192 <= bsib_budget()) {
+      // on the device: a bitmap per (full key, batch), then a workgroup per full key over its batches
+      std::vector<uint32_t> tbl(K + n_full, 0xFFFFFFFFu);  // fidx[K], then fki[n_full]
+      size_t f = 0;
+      for (size_t ki = 0; ki < K && f < n_full; ki++)
+        if (isfull[ki]) tbl[ki] = (uint32_t)f, tbl[K + f++] = (uint32_t)ki;
+      DevBuf dt, bits;
+      CHK(pool_take(c, dt, 4 * tbl.size() + 16));
+      CHK(pool_take(c, bits, n_full * n_batches * 8192));
+      CHK(upload_words(c, dt.p, tbl.data(), tbl.size()));
+      HIPCHK(hipMemsetAsync(bits.p, 0, n_full * n_batches * 8192, s));
+      BsiTrSweep p = sw;
+      p.rank = rank;
+      p.fidx = dt.as<uint32_t>();
+      p.bits = bits.as<uint32_t>();
+      p.n_batches = (uint32_t)n_batches;
+      p.batch_size = (uint32_t)batch_size;
+      launch_bsitr_sweep(s, 4, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, p);
+      launch_bsitr_full_runs(s, bits.as<uint32_t>(), (uint32_t)f, (uint32_t)n_batches, dt.as<uint32_t>() + K,
+                             c->bsia_run.as<uint8_t>());
+      HIPCHK(hipGetLastError());
+      pool_put(c, dt);  // whatever takes them next is enqueued on this stream, after the kernels
+      pool_put(c, bits);
+      HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
+      CHK(plan_all(false));  // a flagged key is a run container of one run: sizes and kinds again
+      dbg(s, "bsi_transpose: full keys");
+    } else {
+      // the bitmaps exceed the budget: the (rank, value) pairs of the full keys go to the host
+      const size_t cap = (size_t)most;
+      DevBuf dr, dv;
+      CHK(pool_take(c, dr, 4 * cap + 16));
+      CHK(pool_take(c, dv, 4 * cap + 16));
+      BsiTrSweep p = sw;
+      p.isfull = c->bsit_full.as<uint8_t>();
+      p.rank = rank;
+      p.n_pairs = sc + 4;
+      p.out_rank = dr.as<uint32_t>();
+      p.out_val = dv.as<uint32_t>();
+      p.cap = cap;
+      launch_bsitr_sweep(s, 2, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, p);
+      HIPCHK(hipGetLastError());
+      unsigned long long np = 0;
+      std::vector<uint16_t> rkeys(K);
+      std::vector<uint8_t> run(K, 0);
+      HIPCHK(hipMemcpyAsync(&np, sc + 4, 8, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(rkeys.data(), c->bsib_pkeys.p, 2 * K, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipStreamSynchronize(s));
+      const size_t n = (size_t)std::min<unsigned long long>(np, cap);
+      std::vector<uint32_t> hr(n), hv(n);
+      if (n) {
+        HIPCHK(hipMemcpyAsync(hr.data(), dr.p, 4 * n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipMemcpyAsync(hv.data(), dv.p, 4 * n, hipMemcpyDeviceToHost, s));
+        HIPCHK(hipStreamSynchronize(s));
+      }
+      pool_put(c, dr);
+      pool_put(c, dv);
+      std::vector<int32_t> slot(65536, -1);
+      for (size_t ki = 0; ki < K; ki++)
+        if (isfull[ki]) slot[rkeys[ki]] = (int32_t)ki;
+      bsit_full_runs(hr, hv, n, slot, (uint64_t)batch_size, run);
+      if (std::find(run.begin(), run.end(), (uint8_t)1) != run.end()) {
+        CHK(pinned_ensure(c, K));
+        std::memcpy(c->pinned, run.data(), K);
+        HIPCHK(hipMemcpyAsync(c->bsia_run.p, c->pinned, K, hipMemcpyHostToDevice, s));
+        HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
+        CHK(plan_all(false));  // the flagged keys are a run container of one run: sizes and kinds again
+        dbg(s, "bsi_transpose: full keys (host)");
+      }
+    }
+  }
+  const uint32_t mn = (uint32_t)h3[0], mx = (uint32_t)(h3[0] >> 32);
+  const int nb = mx ? 32 - __builtin_clz(mx) : 0;
+  CHK(bsib_emit(c, K, m, 1 + nb, P, ws, hp, total, fill, "bsi_transpose: write", out_id));
+  out3[0] = nb;
+  out3[1] = (int32_t)mn;
+  out3[2] = (int32_t)mx;
+  return RBG_OK;
 }
 
 // op RBG_OR_INPLACE: x1.or(x2) in place (RB/RoaringBitmap.java:2481-2523), the OR with Container.ior's
@@ -4498,6 +4787,31 @@ int rbg_bsi_in(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices,
   CHK(ctx_bsi_in(c, id, nbits, found ? 1 : 0, values, n_values, parallelism, &res));
   os.adopt(res);
   return ctx_batch_fetch_range(c, res, 0, 1, out);
+}
+
+/* ---- BitSliceIndexBase.parallelTransposeWithCount (BBSI/:551-597; bsitr.hip) ---- */
+
+int rbg_ctx_bsi_transpose(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int parallelism, int32_t* out_batch,
+                          int32_t* out3) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!out_batch || !out3) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_transpose(c, batch, nbits, has_found != 0, parallelism, out_batch, out3);
+}
+
+int rbg_bsi_transpose(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
+                      int nbits, const uint8_t* found, size_t found_len, int parallelism, rbg_buffer* outs,
+                      int32_t* out3) {
+  if (!outs || !out3 || nbits < 0 || nbits > 32 || parallelism < 1) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (!ebm || (nbits && (!slices || !slice_lens))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id, res;
+  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, (size_t)nbits, found, found_len, &id));
+  CHK(ctx_bsi_transpose(c, id, nbits, found ? 1 : 0, parallelism, &res, out3));
+  os.adopt(res);
+  return ctx_batch_fetch_range(c, res, 0, 1 + (size_t)out3[0], outs);
 }
 
 int rbg_bsi_get_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,

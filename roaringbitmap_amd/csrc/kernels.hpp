@@ -610,6 +610,46 @@ void launch_bsiin_keys(hipStream_t s, BsiValArgs a, int has_found, uint8_t* flag
 void launch_bsi_in(hipStream_t s, BsiValArgs a, int has_found, const uint32_t* list, uint32_t n, const uint16_t* pkeys,
                    uint32_t k_lo, uint32_t k_hi, const uint64_t* rank, bool aligned, uint8_t* ws, uint8_t* run);
 
+// bsitr.hip: the buffer package's parallelTransposeWithCount (BBSI/:551-597) over a key-major batch [ebM,
+// bA[0..nbits-1], foundSet?]: a count table of 65,536 u32 per result key (value >> 16), then m cells of 8 KiB
+// per result key in the workspace layout of the build above (the existence cell, then one per count bit)
+struct BsiTrSweep {
+  uint8_t* rflag;         // mode 0: rflag[value >> 16] = 1 (65,536 bytes, zeroed by the caller)
+  const uint32_t* rkoff;  // modes 1, 2: result key -> result key index (launch_bld_keys' CSR over rflag)
+  uint32_t* tab;          // mode 1: (k_hi - k_lo) x 65,536 counts, zeroed by the caller
+  uint32_t k_lo, k_hi;    // mode 1: the result key indices of the pass
+  const uint8_t* isfull;  // mode 2: per result key index, all 65,536 values present
+  const uint64_t* rank;   // mode 2: per input key, the columns of fixed below key << 16
+  unsigned long long* n_pairs;  // mode 2: pairs written (zeroed by the caller)
+  uint32_t* out_rank;           // mode 2: cap entries each, in no particular order
+  uint32_t* out_val;
+  unsigned long long cap;
+  const uint32_t* fidx;  // mode 4: per result key index, its index among the full keys, or ~0u
+  uint32_t* bits;        // mode 4: per (full key, batch) a bitmap of 2,048 words, zeroed by the caller
+  uint32_t n_batches, batch_size;  // mode 4: parallelExec's batches of fixed
+};
+// one workgroup per candidate key ckeys[0..*n_ckeys) (launch_bsiin_keys' flags through launch_bld_keys); grid:
+// an upper bound of *n_ckeys known on the host (ebM's containers).  mode 0 / 1 / 2: see BsiTrSweep
+void launch_bsitr_sweep(hipStream_t s, int mode, BsiValArgs a, int has_found, const uint16_t* ckeys,
+                        const unsigned long long* n_ckeys, uint32_t grid, BsiTrSweep p);
+// mode 4: bits[(fidx * n_batches + rank / batch_size) * 2048 ...] gets the low half of the value of every column
+// whose value lies in a full key.  launch_bsitr_full_runs then walks a full key's batches in order (a workgroup
+// per full key) and sets run[fki[f]] = 1 where the key is RunContainer.full()
+void launch_bsitr_full_runs(hipStream_t s, const uint32_t* bits, uint32_t n_full, uint32_t n_batches,
+                            const uint32_t* fki, uint8_t* run);
+// mode 3 (the sparse route): out_val = the value of every column of ebM & fixed, *n_pairs of them.  Then
+// vals[0..n) sorted into `sorted` and run-length encoded into (uniq, counts), *n_out runs; temp:
+// bsitr_sort_temp_bytes(n) bytes; n < 2^31.  -> hipError_t
+size_t bsitr_sort_temp_bytes(uint64_t n);
+int launch_bsitr_sort_rle(hipStream_t s, void* temp, size_t temp_bytes, const uint32_t* vals, uint32_t* sorted,
+                          uint32_t* uniq, int32_t* counts, unsigned long long* n_out, uint64_t n);
+// the cells of the result key indices [k_lo, k_hi) from their count tables (m - 1 <= 32 count bits); writes
+// every cell of the pass.  stats: also mm = {min, max} of the non-zero counts ({~0u, 0} set by the caller),
+// kcard[ki] += the key's distinct values, isfull[ki] = 1 and *n_full += 1 for a key that reaches 65,536
+// (kcard, isfull, n_full zeroed by the caller)
+void launch_bsitr_cells(hipStream_t s, const uint32_t* tab, uint32_t k_lo, uint32_t k_hi, int m, uint8_t* cells,
+                        bool stats, uint32_t* mm, uint32_t* kcard, uint8_t* isfull, unsigned long long* n_full);
+
 // decode.hip: portable-format decode on the device
 enum DecErr : uint32_t {
   DEC_OK = 0,

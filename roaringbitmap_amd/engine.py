@@ -471,6 +471,23 @@ class Engine:
                                    ctypes.byref(out)))
         return out.value
 
+    def bsi_transpose(self, batch, nbits, parallelism=1, has_found=False):
+        """BitSliceIndexBase.parallelTransposeWithCount (BBSI/:551-597), GROUP BY value / COUNT(*), over a
+        resident index [ebM, bA[0..nbits-1], foundSet?] on the device (rbg_ctx_bsi_transpose)
+        -> (batch, nbits, minValue, maxValue): a new key-major batch [ebM, bA[0..nbits-1]] whose columns are
+        the distinct 32-bit values of the columns of ebM (and of the foundSet) and whose values are how many
+        columns held each -- the batch load() of the reference's result bitmaps gives, as bsi / bsi_buffer /
+        bsi_get_values / bsi_to_pairs / bsi_add / bsi_in take it.  nbits is the bit count of the largest
+        count, min / max the smallest and largest count; no column: one empty bitmap and (0, 0, 0).
+        parallelism only decides whether a full container of the result's ebM is a bitmap or a run container.
+        parallelism < 1, nbits > 32 or a batch of another shape: IllegalArgumentException, no batch made.
+        Synchronous."""
+        out = ctypes.c_int32()
+        out3 = (ctypes.c_int32 * 3)()
+        check(lib().rbg_ctx_bsi_transpose(self._ctx, int(batch), int(nbits), int(bool(has_found)), int(parallelism),
+                                          ctypes.byref(out), out3))
+        return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+
     def bsi_get_values(self, batch, nbits, columns, has_found=False):
         """getValue for many columns at once against a resident index [ebM, bA[0..nbits-1], foundSet?]
         (rbg_ctx_bsi_get_values): one int64 per column, in query order, -1 where ebM lacks the column.  The
