@@ -1048,6 +1048,13 @@ static int ctx_to_values_host(Ctx* c, int32_t batch, size_t i, uint64_t first, u
 // the scatter reads a word before its atomic (18x on 2^27 values of one key, -16 % on sorted dense input:
 // DESIGN §3.9)
 constexpr bool kBldPrecheck = true;
+// RBG_BLD_PRECHECK=0 / 1 (measurement only, read at every call): the scatter without / with the read in front
+// of every atomic
+static bool bld_precheck() {
+  const char* e = std::getenv("RBG_BLD_PRECHECK");
+  return e ? e[0] == '1' : kBldPrecheck;
+}
+
 static int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32_t* out_id) {
   hipStream_t s = c->stream;
   const int32_t id = new_batch(c);
@@ -1078,11 +1085,7 @@ static int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt
   if (C) {
     CHK(pool_take(c, ws, 8192 * C));
     HIPCHK(hipMemsetAsync(ws.p, 0, 8192 * C, s));
-    // RBG_BLD_PRECHECK=0 / 1 (measurement only, read at every call): the scatter without / with the read
-    // in front of every atomic
-    bool precheck = kBldPrecheck;
-    if (const char* e = std::getenv("RBG_BLD_PRECHECK")) precheck = e[0] == '1';
-    launch_bld_scatter(s, v_dev, n, b.key_off.as<uint32_t>(), ws.as<uint32_t>(), precheck);
+    launch_bld_scatter(s, v_dev, n, b.key_off.as<uint32_t>(), ws.as<uint32_t>(), bld_precheck());
     CHK(c->bld_info.ensure(kBldInfoBytes * C));
     CHK(c->bld_size.ensure(8 * C + 16));
     CHK(c->bld_part.ensure(8 * (scan_parts(C) + 1)));
@@ -1124,26 +1127,8 @@ static int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt
   return RBG_OK;
 }
 
-// the same from host memory: the values go to the device through the context's pinned buffer, a chunk
-// at a time
-static int ctx_from_values_host(Ctx* c, const uint32_t* v, size_t n, bool run_opt, int32_t* out_id) {
-  constexpr size_t kChunk = 16u << 20;  // values per staged copy (64 MiB)
-  DevBuf in;
-  CHK(pool_take(c, in, 4 * n + 16));
-  if (n) {
-    CHK(pinned_ensure(c, 4 * std::min(n, kChunk)));
-    HIPCHK(hipStreamSynchronize(c->stream));  // nothing enqueued earlier still reads the staging buffer
-    for (size_t off = 0; off < n; off += kChunk) {
-      const size_t m = std::min(kChunk, n - off);
-      std::memcpy(c->pinned, v + off, 4 * m);
-      HIPCHK(hipMemcpyAsync(in.as<uint32_t>() + off, c->pinned, 4 * m, hipMemcpyHostToDevice, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
-  }
-  const int st = ctx_from_values(c, in.as<uint32_t>(), n, run_opt, out_id);
-  pool_put(c, in);
-  return st;
-}
+// one empty bitmap as a new batch: the result of a query that no column can satisfy
+static int ctx_empty_bitmap(Ctx* c, int32_t* out_id) { return ctx_from_values(c, nullptr, 0, false, out_id); }
 
 // n 32-bit words from host memory into dst (device), through the context's pinned buffer, a chunk at a time
 static int upload_words(Ctx* c, void* dst, const void* src, size_t n) {
@@ -1160,6 +1145,20 @@ static int upload_words(Ctx* c, void* dst, const void* src, size_t n) {
   return RBG_OK;
 }
 
+// ctx_from_values from host memory
+static int ctx_from_values_host(Ctx* c, const uint32_t* v, size_t n, bool run_opt, int32_t* out_id) {
+  DevBuf in;
+  CHK(pool_take(c, in, 4 * n + 16));
+  CHK(upload_words(c, in.p, v, n));
+  const int st = ctx_from_values(c, in.as<uint32_t>(), n, run_opt, out_id);
+  pool_put(c, in);
+  return st;
+}
+
+// the seeds of a {min, max} pair that kernels lower and raise with atomics: signed values, unsigned values
+static const int32_t kMinMaxSeedI32[2] = {INT32_MAX, INT32_MIN};
+static const uint32_t kMinMaxSeedU32[2] = {0xFFFFFFFFu, 0u};
+
 // Workspace bytes of one pass of the BSI build (bsibuild.hip).  RBG_BSI_BUILD_WS=<bytes> overrides the
 // default, read at every call (tests force several passes at small shapes); a pass always holds at least
 // one key's m bitmaps and stays below 2^31 words.
@@ -1170,62 +1169,123 @@ static size_t bsib_budget() {
   return (size_t)std::min<unsigned long long>(v ? v : kBsibBudget, 4ull << 30);
 }
 
-// The batch of a planned workspace (bsibuild.hip's cells; filled by the build's scatter or by bsiadd.hip):
-// K present keys x m cells, walked P keys per pass; hp: the plan's per-input totals (4 per cell column,
-// then the three kind counts), total: the scan's total.  The first n_bm cell columns are the batch's
-// bitmaps (any further column holds no container).  refill(k_lo, k_hi) fills the workspace with a pass
-// again when there are several.  The workspace goes back to the pool.
-template <class Refill>
-static int bsib_emit(Ctx* c, size_t K, int m, int n_bm, size_t P, DevBuf& ws, const std::vector<unsigned long long>& hp,
-                     uint64_t total, Refill&& refill, const char* what, int32_t* out_id) {
-  hipStream_t s = c->stream;
-  uint64_t* size = c->bsib_size.as<uint64_t>();
-  const size_t C = (size_t)(total >> kBsibCountShift);
-  const int32_t id = new_batch(c);
-  Batch& b = *c->batches[id];
-  BatchGuard guard{c, {id}};  // dropped unless the build completes
-  b.payload_bytes = (size_t)(total & ((1ull << kBsibCountShift) - 1));
-  CHK(pool_take(c, b.keys, 2 * C + 16));
-  CHK(pool_take(c, b.desc, sizeof(CDesc) * C + 16));
-  CHK(pool_take(c, b.bm, 4 * C + 16));
-  CHK(pool_take(c, b.key_off, 4 * (kMaxKeys + 1)));
-  CHK(pool_take(c, b.bm_off, 4 * ((size_t)n_bm + 1)));
-  CHK(pool_take(c, b.payload, b.payload_bytes + 64));
-  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
-    const size_t k_hi = std::min(K, k_lo + P);
-    if (P < K) CHK(refill(k_lo, k_hi));  // several passes: the workspace held another pass since the plan
-    launch_bsib_write(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, c->bsib_info.p, size,
-                      c->bsib_pkeys.as<uint16_t>(), b.desc.as<CDesc>(), b.keys.as<uint16_t>(), b.bm.as<uint32_t>(),
-                      b.payload.as<uint8_t>());
+// A planned workspace (bsibuild.hip's cells): K present keys x m cells of 8 KiB, walked P whole keys per pass
+// under bsib_budget().  begin sizes the scratch and takes the workspace, sweep fills and plans every pass and
+// scans the sizes, emit writes the batch.  One pass: fill, plan, scan, write from the same workspace.  Several:
+// the sweep plans every pass (sizes alone), the scan places every container, and emit fills each pass again
+// before it writes -- the payload is allocated once at its exact size.
+// fill(k_lo, k_hi, first) enqueues whatever leaves the cells of keys [k_lo, k_hi) at the front of ws; first: the
+// call comes from the first sweep (a caller's once-only statistics), not from a later sweep or from emit.
+struct BsibPlan {
+  Ctx* c;
+  size_t K = 0;
+  int m = 0;
+  size_t key_bytes = 0;  // of ws per key: the m cells, then whatever the caller keeps after a pass's cells
+  size_t P = 0;          // keys per pass
+  DevBuf ws;             // back to the pool at the end of emit (freed on an error)
+  std::vector<unsigned long long> hp;  // the plan's per-input totals: 4 per cell column, then the three kind counts
+  uint64_t total = 0;                  // the scan's total: containers << kBsibCountShift | payload bytes
+  bool run_opt = false;                // the plan types as runOptimize() does
+  bool ebm_run = false;                // the plan reads bsia_run: per key, column 0 is a full run container
+
+  size_t cells() const { return K * (size_t)m; }
+  size_t per_bytes() const { return 8 * (4 * (size_t)m + 4); }
+
+  int begin(Ctx* ctx, size_t n_keys, int n_cols, size_t extra_key_bytes, bool run_optimize, bool reads_ebm_run) {
+    c = ctx, K = n_keys, m = n_cols, run_opt = run_optimize, ebm_run = reads_ebm_run;
+    key_bytes = 8192 * (size_t)m + extra_key_bytes;
+    CHK(c->bsib_info.ensure(kBsibInfoBytes * cells() + 16));
+    CHK(c->bsib_size.ensure(8 * (cells() + 1)));
+    CHK(c->bsib_part.ensure(8 * (scan_parts(cells()) + 1)));
+    CHK(c->bsib_per.ensure(per_bytes()));
+    if (ebm_run) CHK(c->bsia_run.ensure(K + 16));
+    HIPCHK(hipMemsetAsync(c->bsib_per.p, 0, per_bytes(), c->stream));
+    hp.assign(4 * (size_t)m + 4, 0);
+    P = std::min(K, std::max<size_t>(1, bsib_budget() / key_bytes));
+    if (K) CHK(pool_take(c, ws, key_bytes * P));  // bsi_add of two empty indexes has no key
+    return RBG_OK;
   }
-  launch_bsib_key_off(s, c->bsib_pkoff.as<uint32_t>(), size, m, b.key_off.as<uint32_t>());
-  HIPCHK(hipGetLastError());
-  pool_put(c, ws);  // whatever takes it next is enqueued on this stream, after the write kernels
-  b.n_bm = (size_t)n_bm;
-  b.n_ctr = C;
-  b.key_major = true;
-  for (int k = 0; k < 3; k++) b.n_kind[k] = (int64_t)hp[4 * m + k];
-  b.max_ser = 0;  // no container above kStagedMax serialized bytes
-  b.h_bm_off.assign(n_bm + 1, 0);
-  b.h_bm_nctr.resize(n_bm);
-  b.h_bm_card.resize(n_bm);
-  b.h_has_run.resize(n_bm);
-  for (int i = 0; i < n_bm; i++) {
-    b.h_bm_nctr[i] = (uint32_t)hp[4 * i];
-    b.h_bm_off[i + 1] = b.h_bm_off[i] + b.h_bm_nctr[i];
-    b.h_bm_card[i] = (int64_t)hp[4 * i + 1];
-    b.h_has_run[i] = hp[4 * i + 3] != 0;
-    b.long_card += b.h_bm_card[i];
-    b.ser_bytes += (int64_t)(header_size(b.h_bm_nctr[i], b.h_has_run[i] != 0) + hp[4 * i + 2]);
+
+  // Every pass filled (a later sweep: only when there are several, the one pass is still in ws) and planned,
+  // the sizes scanned, hp and total read back.  more(): the caller's own device-to-host copies, enqueued in
+  // front of the one synchronise.
+  template <class Fill, class More>
+  int sweep(bool first, Fill&& fill, More&& more) {
+    hipStream_t s = c->stream;
+    uint64_t* size = c->bsib_size.as<uint64_t>();
+    unsigned long long* per = c->bsib_per.as<unsigned long long>();
+    if (!first) HIPCHK(hipMemsetAsync(per, 0, per_bytes(), s));
+    for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+      const size_t k_hi = std::min(K, k_lo + P);
+      if (first || P < K) CHK(fill(k_lo, k_hi, first));
+      launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, run_opt ? 1 : 0, c->bsib_info.p, size, per,
+                       per + 4 * m, ebm_run ? c->bsia_run.as<uint8_t>() : nullptr);
+    }
+    launch_exclusive_scan(s, size, size, cells(), c->bsib_part.as<uint64_t>(), size + cells());
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(&total, size + cells(), 8, hipMemcpyDeviceToHost, s));
+    CHK(more());
+    HIPCHK(hipStreamSynchronize(s));
+    return RBG_OK;
   }
-  HIPCHK(hipMemcpyAsync(b.bm_off.p, b.h_bm_off.data(), 4 * ((size_t)n_bm + 1), hipMemcpyHostToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));
-  dbg(s, what);
-  guard.ids.clear();
-  b.live = true;
-  *out_id = id;
-  return RBG_OK;
-}
+  template <class Fill>
+  int sweep(bool first, Fill&& fill) {
+    return sweep(first, fill, [] { return RBG_OK; });
+  }
+
+  // The batch: the first n_bm cell columns are its bitmaps (any further column holds no container).
+  template <class Fill>
+  int emit(int n_bm, Fill&& fill, const char* what, int32_t* out_id) {
+    hipStream_t s = c->stream;
+    uint64_t* size = c->bsib_size.as<uint64_t>();
+    const size_t C = (size_t)(total >> kBsibCountShift);
+    const int32_t id = new_batch(c);
+    Batch& b = *c->batches[id];
+    BatchGuard guard{c, {id}};  // dropped unless the build completes
+    b.payload_bytes = (size_t)(total & ((1ull << kBsibCountShift) - 1));
+    CHK(pool_take(c, b.keys, 2 * C + 16));
+    CHK(pool_take(c, b.desc, sizeof(CDesc) * C + 16));
+    CHK(pool_take(c, b.bm, 4 * C + 16));
+    CHK(pool_take(c, b.key_off, 4 * (kMaxKeys + 1)));
+    CHK(pool_take(c, b.bm_off, 4 * ((size_t)n_bm + 1)));
+    CHK(pool_take(c, b.payload, b.payload_bytes + 64));
+    for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+      const size_t k_hi = std::min(K, k_lo + P);
+      if (P < K) CHK(fill(k_lo, k_hi, false));  // several passes: the workspace held another pass since the plan
+      launch_bsib_write(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, c->bsib_info.p, size,
+                        c->bsib_pkeys.as<uint16_t>(), b.desc.as<CDesc>(), b.keys.as<uint16_t>(), b.bm.as<uint32_t>(),
+                        b.payload.as<uint8_t>());
+    }
+    launch_bsib_key_off(s, c->bsib_pkoff.as<uint32_t>(), size, m, b.key_off.as<uint32_t>());
+    HIPCHK(hipGetLastError());
+    pool_put(c, ws);  // whatever takes it next is enqueued on this stream, after the write kernels
+    b.n_bm = (size_t)n_bm;
+    b.n_ctr = C;
+    b.key_major = true;
+    for (int k = 0; k < 3; k++) b.n_kind[k] = (int64_t)hp[4 * m + k];
+    b.max_ser = 0;  // no container above kStagedMax serialized bytes
+    b.h_bm_off.assign(n_bm + 1, 0);
+    b.h_bm_nctr.resize(n_bm);
+    b.h_bm_card.resize(n_bm);
+    b.h_has_run.resize(n_bm);
+    for (int i = 0; i < n_bm; i++) {
+      b.h_bm_nctr[i] = (uint32_t)hp[4 * i];
+      b.h_bm_off[i + 1] = b.h_bm_off[i] + b.h_bm_nctr[i];
+      b.h_bm_card[i] = (int64_t)hp[4 * i + 1];
+      b.h_has_run[i] = hp[4 * i + 3] != 0;
+      b.long_card += b.h_bm_card[i];
+      b.ser_bytes += (int64_t)(header_size(b.h_bm_nctr[i], b.h_has_run[i] != 0) + hp[4 * i + 2]);
+    }
+    HIPCHK(hipMemcpyAsync(b.bm_off.p, b.h_bm_off.data(), 4 * ((size_t)n_bm + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(hipStreamSynchronize(s));
+    dbg(s, what);
+    guard.ids.clear();
+    b.live = true;
+    *out_id = id;
+    return RBG_OK;
+  }
+};
 
 // A bit-sliced index from n (column, value) pairs in device memory (u32 columns, all distinct; i32 values,
 // none negative; any order) as a new key-major batch [ebM, bA[0..nbits-1]]: setValue for every pair
@@ -1234,16 +1294,13 @@ static int bsib_emit(Ctx* c, size_t K, int m, int n_bm, size_t P, DevBuf& ws, co
 // bitmaps gives (bsibuild.hip).  out3 = {nbits, minValue, maxValue}.  Two read-backs: the key count with
 // min / max (a negative value is refused here), then the per-input totals (a repeated column shows as
 // cardinality(ebM) != n and is refused before anything is allocated for the batch).
-// The K x (nbits + 1) bitmaps of the workspace are walked in passes of whole keys under bsib_budget().  One
-// pass: scatter, plan, scan, write from the same workspace.  Several passes: a first sweep scatters and plans
-// every pass (sizes alone), the scan places every container, and a second sweep scatters again and writes
-// -- the payload is allocated once at its exact size.  The pairs are read by every scatter:
+// The K x (nbits + 1) bitmaps are a BsibPlan whose fill is the scatter.  The pairs are read by every scatter:
 // they must not change until the call returns.
 static int ctx_bsi_from_columns(Ctx* c, const uint32_t* col_dev, const int32_t* val_dev, size_t n, bool run_opt,
                                 int32_t* out_id, int32_t* out3) {
   hipStream_t s = c->stream;
   out3[0] = out3[1] = out3[2] = 0;
-  if (n == 0) return ctx_from_values(c, nullptr, 0, run_opt, out_id);  // one empty bitmap: ebM, no slice
+  if (n == 0) return ctx_empty_bitmap(c, out_id);  // ebM, no slice
   if (n > (1ull << 32)) {
     set_err("bsi_from_columns: more pairs than columns");
     return RBG_ERR_ILLEGAL_ARGUMENT;
@@ -1251,10 +1308,9 @@ static int ctx_bsi_from_columns(Ctx* c, const uint32_t* col_dev, const int32_t* 
   CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
   CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
   unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] {min, max} as two i32
-  static const int kMinMaxInit[2] = {INT32_MAX, INT32_MIN};
   HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
   HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxInit, 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxSeedI32, 8, hipMemcpyHostToDevice, s));
   launch_bld_keys(s, col_dev, n, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
   launch_bsib_minmax(s, val_dev, n, reinterpret_cast<int*>(sc + 1));
   HIPCHK(hipGetLastError());
@@ -1269,45 +1325,23 @@ static int ctx_bsi_from_columns(Ctx* c, const uint32_t* col_dev, const int32_t* 
   }
   const int nbits = mx ? 32 - __builtin_clz((uint32_t)mx) : 1;  // Integer.toBinaryString(max).length()
   const int m = nbits + 1;
-  const size_t cells = K * (size_t)m;
   dbg(s, "bsi_from_columns: keys + min / max");
-  CHK(c->bsib_info.ensure(kBsibInfoBytes * cells));
-  CHK(c->bsib_size.ensure(8 * (cells + 1)));
-  CHK(c->bsib_part.ensure(8 * (scan_parts(cells) + 1)));
-  CHK(c->bsib_per.ensure(8 * (4 * (size_t)m + 4)));
-  uint64_t* size = c->bsib_size.as<uint64_t>();
-  unsigned long long* per = c->bsib_per.as<unsigned long long>();
-  HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
-  const size_t P = std::min(K, std::max<size_t>(1, bsib_budget() / (8192 * (size_t)m)));  // keys per pass
-  DevBuf ws;  // back to the pool at the end (freed on an error)
-  CHK(pool_take(c, ws, 8192 * (size_t)m * P));
-  bool precheck = kBldPrecheck;  // RBG_BLD_PRECHECK as in ctx_from_values
-  if (const char* e = std::getenv("RBG_BLD_PRECHECK")) precheck = e[0] == '1';
-  auto scatter = [&](size_t k_lo, size_t k_hi) -> int {
-    HIPCHK(hipMemsetAsync(ws.p, 0, 8192 * (size_t)m * (k_hi - k_lo), s));
+  BsibPlan plan;
+  CHK(plan.begin(c, K, m, 0, run_opt, false));
+  const bool precheck = bld_precheck();
+  auto scatter = [&](size_t k_lo, size_t k_hi, bool) -> int {
+    HIPCHK(hipMemsetAsync(plan.ws.p, 0, 8192 * (size_t)m * (k_hi - k_lo), s));
     launch_bsib_scatter(s, col_dev, val_dev, n, c->bsib_pkoff.as<uint32_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m,
-                        ws.as<uint32_t>(), precheck);
+                        plan.ws.as<uint32_t>(), precheck);
     return RBG_OK;
   };
-  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
-    const size_t k_hi = std::min(K, k_lo + P);
-    CHK(scatter(k_lo, k_hi));
-    launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, run_opt ? 1 : 0, c->bsib_info.p, size, per,
-                     per + 4 * m);
-  }
-  launch_exclusive_scan(s, size, size, cells, c->bsib_part.as<uint64_t>(), size + cells);
-  HIPCHK(hipGetLastError());
-  std::vector<unsigned long long> hp(4 * (size_t)m + 4);
-  uint64_t total = 0;
-  HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&total, size + cells, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  CHK(plan.sweep(true, scatter));
   dbg(s, "bsi_from_columns: scatter + plan");
-  if (hp[1] != n) {  // setValue overwrites: a column given twice would need the pairs' order
+  if (plan.hp[1] != n) {  // setValue overwrites: a column given twice would need the pairs' order
     set_err("bsi_from_columns: a column is given more than once");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  CHK(bsib_emit(c, K, m, m, P, ws, hp, total, scatter, "bsi_from_columns: write", out_id));
+  CHK(plan.emit(m, scatter, "bsi_from_columns: write", out_id));
   out3[0] = nbits;
   out3[1] = mn;
   out3[2] = mx;
@@ -1354,8 +1388,8 @@ static int bsi_add_operand(Ctx* c, int32_t id, int nbits, Batch** B, BsiAddSide*
 // out3 = {n', minValue, maxValue}, min / max from the descent of BSI/:97-138 as Java ints.  An empty ebM of
 // b (:67-69): a copy of a with {nbits_a, min_a, max_a}.  Two read-backs: the key count, then the per-input
 // totals with min / max -- the carry out of the top input slice decides whether the result has one more
-// slice, and out of slice 31 it is refused before a batch exists.  The K x (2 + max(na, nb)) bitmaps of the
-// workspace are walked in key passes under bsib_budget() with the build's two-sweep scheme.
+// slice, and out of slice 31 it is refused before a batch exists.  The K x (2 + max(na, nb)) bitmaps are a
+// BsibPlan whose fill is the add, followed in the sweep by the min / max descent.
 static int ctx_bsi_add(Ctx* c, int32_t batch_a, int nbits_a, int32_t batch_b, int nbits_b, int32_t min_a, int32_t max_a,
                        int32_t* out_id, int32_t* out3) {
   hipStream_t s = c->stream;
@@ -1370,10 +1404,9 @@ static int ctx_bsi_add(Ctx* c, int32_t batch_a, int nbits_a, int32_t batch_b, in
   CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
   CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
   unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] {min, max} as two u32
-  static const uint32_t kMinMaxInit[2] = {0xFFFFFFFFu, 0u};
   HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
   HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxInit, 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxSeedU32, 8, hipMemcpyHostToDevice, s));
   launch_bsia_keys(s, A->keys.as<uint16_t>(), A->n_ctr, B->keys.as<uint16_t>(), b_empty ? 0 : B->n_ctr,
                    c->flag.as<uint8_t>());
   launch_bld_keys(s, nullptr, 0, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
@@ -1382,48 +1415,30 @@ static int ctx_bsi_add(Ctx* c, int32_t batch_a, int nbits_a, int32_t batch_b, in
   HIPCHK(hipMemcpyAsync(h, sc, 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   const size_t K = (size_t)h[0];
-  const size_t cells = K * (size_t)m;
   dbg(s, "bsi_add: keys");
-  CHK(c->bsib_info.ensure(kBsibInfoBytes * cells + 16));
-  CHK(c->bsib_size.ensure(8 * (cells + 1)));
-  CHK(c->bsib_part.ensure(8 * (scan_parts(cells) + 1)));
-  CHK(c->bsib_per.ensure(8 * (4 * (size_t)m + 4)));
-  CHK(c->bsia_run.ensure(K + 16));
-  uint64_t* size = c->bsib_size.as<uint64_t>();
-  unsigned long long* per = c->bsib_per.as<unsigned long long>();
-  HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
-  const size_t P = std::min(K, std::max<size_t>(1, bsib_budget() / (8192 * (size_t)m)));  // keys per pass
-  DevBuf ws;  // back to the pool at the end (freed on an error)
-  if (K) CHK(pool_take(c, ws, 8192 * (size_t)m * P));
-  auto fill = [&](size_t k_lo, size_t k_hi) -> int {  // every cell of the pass is written: no memset
-    launch_bsi_add(s, sa, sb, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, ws.as<uint8_t>(),
+  BsibPlan plan;
+  CHK(plan.begin(c, K, m, 0, false, true));
+  auto fill = [&](size_t k_lo, size_t k_hi, bool first) -> int {  // every cell of the pass is written: no memset
+    launch_bsi_add(s, sa, sb, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, plan.ws.as<uint8_t>(),
                    c->bsia_run.as<uint8_t>());
+    if (first && !b_empty)
+      launch_bsia_minmax(s, plan.ws.as<uint8_t>(), (uint32_t)(k_hi - k_lo), m, reinterpret_cast<uint32_t*>(sc + 1));
     return RBG_OK;
   };
-  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
-    const size_t k_hi = std::min(K, k_lo + P);
-    CHK(fill(k_lo, k_hi));
-    if (!b_empty) launch_bsia_minmax(s, ws.as<uint8_t>(), (uint32_t)(k_hi - k_lo), m, reinterpret_cast<uint32_t*>(sc + 1));
-    launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, 0, c->bsib_info.p, size, per, per + 4 * m,
-                     c->bsia_run.as<uint8_t>());
-  }
-  launch_exclusive_scan(s, size, size, cells, c->bsib_part.as<uint64_t>(), size + cells);
-  HIPCHK(hipGetLastError());
-  std::vector<unsigned long long> hp(4 * (size_t)m + 4);
-  uint64_t total = 0;
   uint32_t mm[2] = {0, 0};
-  HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&total, size + cells, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(mm, sc + 1, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  auto read_mm = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(mm, sc + 1, 8, hipMemcpyDeviceToHost, s));
+    return RBG_OK;
+  };
+  CHK(plan.sweep(true, fill, read_mm));
   dbg(s, "bsi_add: add + plan");
-  const bool grown = hp[4 * (size_t)(m - 1) + 1] != 0;  // a carry left the top input slice
+  const bool grown = plan.hp[4 * (size_t)(m - 1) + 1] != 0;  // a carry left the top input slice
   if (grown && top == 32) {
     set_err("bsi_add: the sum needs more than 32 slices");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
   const int nbits = top + (grown ? 1 : 0);
-  CHK(bsib_emit(c, K, m, 1 + nbits, P, ws, hp, total, fill, "bsi_add: write", out_id));
+  CHK(plan.emit(1 + nbits, fill, "bsi_add: write", out_id));
   out3[0] = nbits;
   if (b_empty) {  // the reference returns before it recomputes them
     out3[1] = min_a;
@@ -1527,6 +1542,58 @@ static int ctx_bsi_to_pairs_host(Ctx* c, int32_t batch, int nbits, int has_found
   return RBG_OK;
 }
 
+// The shared front of the queries that walk ebM & fixed (fixed = the foundSet or ebM) in parallelExec's batches
+// (BBSI/:99-136): ctx_bsi_in and ctx_bsi_transpose.
+struct BsiFixed {
+  Batch* B;
+  BsiValArgs a;
+  int64_t card;        // fixed.getCardinality(), an int
+  int64_t ebm_card;
+  int64_t batch_size;  // min(max(card / parallelism, parallelism), 65536) (Java int arithmetic)
+  bool empty;          // fixed or ebM holds no column: the result is one empty bitmap
+};
+
+// the argument checks (op: the name in the messages) and the host's numbers
+static int bsi_fixed_operand(Ctx* c, const char* op, int32_t batch, int nbits, int has_found, int parallelism,
+                             BsiFixed* f) {
+  if (parallelism < 1) {
+    set_err(std::string(op) + ": parallelism must be positive");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (nbits < 0 || nbits > 32) {
+    set_err(std::string(op) + ": an index holds at most 32 slices");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  CHK(bsi_val_operand(c, batch, nbits, has_found, &f->B, &f->a));
+  const std::vector<int64_t>& cards = f->B->h_bm_card;
+  const size_t fx = has_found ? (size_t)nbits + 1 : 0;
+  f->card = cards.size() > fx ? cards[fx] : 0;
+  if (f->card > INT32_MAX) {
+    set_err(std::string(op) + ": the foundSet (or ebM) holds more than 2^31 - 1 columns");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  f->ebm_card = cards.empty() ? 0 : cards[0];
+  f->empty = f->card == 0 || f->ebm_card == 0;
+  f->batch_size = std::min<int64_t>(std::max<int64_t>(f->card / parallelism, parallelism), 65536);
+  return RBG_OK;
+}
+
+// The candidate keys (those ebM and fixed share) into ckeys / ckoff with their count in scalar[0], which the
+// caller has zeroed, and into bsiv_cards the exclusive scan of the keys' cardinalities in fixed: the rank in
+// fixed of a key's first column.
+static int bsi_fixed_keys(Ctx* c, const BsiFixed& f, int has_found, DevBuf& ckeys, DevBuf& ckoff) {
+  CHK(ckeys.ensure(2 * kMaxKeys + 16));
+  CHK(ckoff.ensure(4 * (kMaxKeys + 1)));
+  CHK(c->bsiv_cards.ensure(8 * (kMaxKeys + 1)));
+  CHK(c->bsiv_part.ensure(8 * (scan_parts(kMaxKeys) + 1)));
+  uint64_t* rank = c->bsiv_cards.as<uint64_t>();
+  launch_bsiin_keys(c->stream, f.a, has_found, c->flag.as<uint8_t>(), rank);
+  launch_bld_keys(c->stream, nullptr, 0, c->flag.as<uint8_t>(), ckeys.as<uint16_t>(), ckoff.as<uint32_t>(),
+                  c->scalar.as<unsigned long long>());
+  launch_exclusive_scan(c->stream, rank, rank, kMaxKeys, c->bsiv_part.as<uint64_t>(), rank + kMaxKeys);
+  return RBG_OK;
+}
+
 constexpr size_t kBsiInHostSort = 1024;  // ctx_bsi_in: longer value lists are sorted on the device
 
 // BitSliceIndexBase.parallelIn(parallelism, foundSet, values, pool) (BBSI/:611-639) over the resident index
@@ -1535,45 +1602,22 @@ constexpr size_t kBsiInHostSort = 1024;  // ctx_bsi_in: longer value lists are s
 // parallelism enters through parallelExec's batchSize (BBSI/:99-136) alone, which decides whether a full
 // container is a bitmap or RunContainer.full().  values: n_values host ints in any order,
 // repeats allowed; the device gets a sorted distinct copy.  An empty fixed, ebM or list: one empty bitmap.  Two
-// read-backs: the candidate key count, then the plan's totals.  The K x 8 KiB workspace is walked in key
-// passes under bsib_budget() with the build's two-sweep scheme.
+// read-backs: the candidate key count, then the plan's totals.  The K x 8 KiB workspace is a BsibPlan of
+// one cell per key whose fill is the membership kernel.
 static int ctx_bsi_in(Ctx* c, int32_t batch, int nbits, int has_found, const int32_t* values, size_t n_values,
                       int parallelism, int32_t* out_id) {
   hipStream_t s = c->stream;
-  if (parallelism < 1) {
-    set_err("bsi_in: parallelism must be positive");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  if (nbits < 0 || nbits > 32) {
-    set_err("bsi_in: an index holds at most 32 slices");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
   if (n_values > (size_t)INT32_MAX) {
     set_err("bsi_in: more than 2^31 - 1 values in the list");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  Batch* B;
-  BsiValArgs a;
-  CHK(bsi_val_operand(c, batch, nbits, has_found, &B, &a));
-  const size_t fx = has_found ? (size_t)nbits + 1 : 0;
-  const int64_t card = B->h_bm_card.size() > fx ? B->h_bm_card[fx] : 0;  // fixed.getCardinality(), an int
-  if (card > INT32_MAX) {
-    set_err("bsi_in: the foundSet (or ebM) holds more than 2^31 - 1 columns");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  const bool ebm_empty = B->h_bm_card.empty() || B->h_bm_card[0] == 0;
-  if (card == 0 || ebm_empty || n_values == 0) return ctx_from_values(c, nullptr, 0, false, out_id);
-  // parallelExec: batchSize = min(max(card / parallelism, parallelism), 65536) (Java int arithmetic)
-  const int64_t batch_size = std::min<int64_t>(std::max<int64_t>(card / parallelism, parallelism), 65536);
-  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
-  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
-  CHK(c->bsiv_cards.ensure(8 * (kMaxKeys + 1)));
-  CHK(c->bsiv_part.ensure(8 * (scan_parts(kMaxKeys) + 1)));
-  uint64_t* rank = c->bsiv_cards.as<uint64_t>();
+  BsiFixed f;
+  CHK(bsi_fixed_operand(c, "bsi_in", batch, nbits, has_found, parallelism, &f));
+  if (f.empty || n_values == 0) return ctx_empty_bitmap(c, out_id);
   unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] the distinct list entries
   // the list as 32-bit patterns (membership is their equality), ascending and distinct, in device memory: a
   // short one is sorted here, a long one on the device
-  DevBuf dl, ws;  // back to the pool at the end (freed on an error)
+  DevBuf dl;  // back to the pool at the end (freed on an error)
   size_t n_list = 0;
   CHK(pool_take(c, dl, 4 * n_values + 16));
   if (n_values <= kBsiInHostSort) {
@@ -1596,9 +1640,7 @@ static int ctx_bsi_in(Ctx* c, int32_t batch, int nbits, int has_found, const int
     pool_put(c, scratch);  // whatever takes them next is enqueued on this stream, after the sort
     pool_put(c, temp);
   }
-  launch_bsiin_keys(s, a, has_found, c->flag.as<uint8_t>(), rank);
-  launch_bld_keys(s, nullptr, 0, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
-  launch_exclusive_scan(s, rank, rank, kMaxKeys, c->bsiv_part.as<uint64_t>(), rank + kMaxKeys);
+  CHK(bsi_fixed_keys(c, f, has_found, c->bsib_pkeys, c->bsib_pkoff));
   HIPCHK(hipGetLastError());
   unsigned long long h[2] = {};
   HIPCHK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, s));
@@ -1608,39 +1650,19 @@ static int ctx_bsi_in(Ctx* c, int32_t batch, int nbits, int has_found, const int
   dbg(s, "bsi_in: keys");
   if (K == 0) {  // ebM and the foundSet share no key
     pool_put(c, dl);
-    return ctx_from_values(c, nullptr, 0, false, out_id);
+    return ctx_empty_bitmap(c, out_id);
   }
-  constexpr int m = 1;
-  CHK(c->bsib_info.ensure(kBsibInfoBytes * K + 16));
-  CHK(c->bsib_size.ensure(8 * (K + 1)));
-  CHK(c->bsib_part.ensure(8 * (scan_parts(K) + 1)));
-  CHK(c->bsib_per.ensure(8 * (4 * (size_t)m + 4)));
-  CHK(c->bsia_run.ensure(K + 16));
-  uint64_t* size = c->bsib_size.as<uint64_t>();
-  unsigned long long* per = c->bsib_per.as<unsigned long long>();
-  HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
-  const size_t P = std::min(K, std::max<size_t>(1, bsib_budget() / 8192));  // keys per pass
-  CHK(pool_take(c, ws, 8192 * P));
-  auto fill = [&](size_t k_lo, size_t k_hi) -> int {  // every cell of the pass is written: no memset
-    launch_bsi_in(s, a, has_found, dl.as<uint32_t>(), (uint32_t)n_list, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo,
-                  (uint32_t)k_hi, rank, batch_size == 65536, ws.as<uint8_t>(), c->bsia_run.as<uint8_t>());
+  BsibPlan plan;
+  CHK(plan.begin(c, K, 1, 0, false, true));
+  auto fill = [&](size_t k_lo, size_t k_hi, bool) -> int {  // every cell of the pass is written: no memset
+    launch_bsi_in(s, f.a, has_found, dl.as<uint32_t>(), (uint32_t)n_list, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo,
+                  (uint32_t)k_hi, c->bsiv_cards.as<uint64_t>(), f.batch_size == 65536, plan.ws.as<uint8_t>(),
+                  c->bsia_run.as<uint8_t>());
     return RBG_OK;
   };
-  for (size_t k_lo = 0; k_lo < K; k_lo += P) {
-    const size_t k_hi = std::min(K, k_lo + P);
-    CHK(fill(k_lo, k_hi));
-    launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, 0, c->bsib_info.p, size, per, per + 4 * m,
-                     c->bsia_run.as<uint8_t>());
-  }
-  launch_exclusive_scan(s, size, size, K, c->bsib_part.as<uint64_t>(), size + K);
-  HIPCHK(hipGetLastError());
-  std::vector<unsigned long long> hp(4 * (size_t)m + 4);
-  uint64_t total = 0;
-  HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(&total, size + K, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
+  CHK(plan.sweep(true, fill));
   dbg(s, "bsi_in: in + plan");
-  const int st = bsib_emit(c, K, m, 1, P, ws, hp, total, fill, "bsi_in: write", out_id);  // synchronises
+  const int st = plan.emit(1, fill, "bsi_in: write", out_id);  // synchronises
   pool_put(c, dl);
   return st;
 }
@@ -1690,8 +1712,8 @@ constexpr uint64_t kBsitSparse = 256;
 // result key is a bitmap or RunContainer.full().  No column of fixed in ebM: one empty bitmap,
 // {0, 0, 0}.  Read-backs: the result key count, then the plan's totals with min / max and the number of full
 // keys.  Per result key the workspace holds m = 1 + bitlen(min(card(ebM), card(fixed))) cells of 8 KiB (no
-// count exceeds that many bits) and a count table of 256 KiB, walked in key passes under bsib_budget() with
-// the build's two-sweep scheme.  Only when a key is full, batchSize > 4096 and fixed spans two batches: the
+// count exceeds that many bits) and a count table of 256 KiB: a BsibPlan with the table as a key's extra bytes,
+// whose fill counts and writes the cells.  Only when a key is full, batchSize > 4096 and fixed spans two batches: the
 // values of the full keys are set in one bitmap per (full key, batch), a workgroup per full key applies the
 // rule over its batches (above the byte budget: the (rank, value) pairs go to the host instead), and the plan
 // runs again.
@@ -1699,45 +1721,22 @@ static int ctx_bsi_transpose(Ctx* c, int32_t batch, int nbits, int has_found, in
                              int32_t* out3) {
   hipStream_t s = c->stream;
   out3[0] = out3[1] = out3[2] = 0;
-  if (parallelism < 1) {
-    set_err("bsi_transpose: parallelism must be positive");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  if (nbits < 0 || nbits > 32) {
-    set_err("bsi_transpose: an index holds at most 32 slices");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  Batch* B;
-  BsiValArgs a;
-  CHK(bsi_val_operand(c, batch, nbits, has_found, &B, &a));
-  const size_t fx = has_found ? (size_t)nbits + 1 : 0;
-  const int64_t card = B->h_bm_card.size() > fx ? B->h_bm_card[fx] : 0;  // fixed.getCardinality(), an int
-  if (card > INT32_MAX) {
-    set_err("bsi_transpose: the foundSet (or ebM) holds more than 2^31 - 1 columns");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  const int64_t ebm_card = B->h_bm_card.empty() ? 0 : B->h_bm_card[0];
-  if (card == 0 || ebm_card == 0) return ctx_from_values(c, nullptr, 0, false, out_id);
-  // parallelExec: batchSize = min(max(card / parallelism, parallelism), 65536) (Java int arithmetic)
-  const int64_t batch_size = std::min<int64_t>(std::max<int64_t>(card / parallelism, parallelism), 65536);
-  const uint32_t grid = B->h_bm_nctr[0];  // the keys of ebM: every candidate key is one of them
-  CHK(c->bsit_ckeys.ensure(2 * kMaxKeys + 16));
-  CHK(c->bsit_ckoff.ensure(4 * (kMaxKeys + 1)));
+  BsiFixed f;
+  CHK(bsi_fixed_operand(c, "bsi_transpose", batch, nbits, has_found, parallelism, &f));
+  if (f.empty) return ctx_empty_bitmap(c, out_id);
+  const BsiValArgs a = f.a;
+  const int64_t card = f.card, ebm_card = f.ebm_card, batch_size = f.batch_size;
+  const uint32_t grid = f.B->h_bm_nctr[0];  // the keys of ebM: every candidate key is one of them
   CHK(c->bsit_rflag.ensure(kMaxKeys));
   CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
   CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
-  CHK(c->bsiv_cards.ensure(8 * (kMaxKeys + 1)));
-  CHK(c->bsiv_part.ensure(8 * (scan_parts(kMaxKeys) + 1)));
-  uint64_t* rank = c->bsiv_cards.as<uint64_t>();
   // [0] candidate keys, [1] K' result keys, [2] {min, max} as two u32, [3] full result keys, [4] pairs
   unsigned long long* sc = c->scalar.as<unsigned long long>();
-  static const uint32_t kMinMaxInit[2] = {0xFFFFFFFFu, 0u};
   HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-  HIPCHK(hipMemcpyAsync(sc + 2, kMinMaxInit, 8, hipMemcpyHostToDevice, s));
+  HIPCHK(hipMemcpyAsync(sc + 2, kMinMaxSeedU32, 8, hipMemcpyHostToDevice, s));
   HIPCHK(hipMemsetAsync(c->bsit_rflag.p, 0, kMaxKeys, s));
-  launch_bsiin_keys(s, a, has_found, c->flag.as<uint8_t>(), rank);
-  launch_bld_keys(s, nullptr, 0, c->flag.as<uint8_t>(), c->bsit_ckeys.as<uint16_t>(), c->bsit_ckoff.as<uint32_t>(), sc);
-  launch_exclusive_scan(s, rank, rank, kMaxKeys, c->bsiv_part.as<uint64_t>(), rank + kMaxKeys);
+  CHK(bsi_fixed_keys(c, f, has_found, c->bsit_ckeys, c->bsit_ckoff));
+  uint64_t* rank = c->bsiv_cards.as<uint64_t>();
   BsiTrSweep sw{};
   sw.rflag = c->bsit_rflag.as<uint8_t>();
   launch_bsitr_sweep(s, 0, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, sw);
@@ -1749,7 +1748,7 @@ static int ctx_bsi_transpose(Ctx* c, int32_t batch, int nbits, int has_found, in
   HIPCHK(hipStreamSynchronize(s));
   dbg(s, "bsi_transpose: keys");
   const size_t K = (size_t)h[1];  // result keys
-  if (K == 0) return ctx_from_values(c, nullptr, 0, false, out_id);  // no column of fixed is in ebM
+  if (K == 0) return ctx_empty_bitmap(c, out_id);  // no column of fixed is in ebM
   const uint64_t most = (uint64_t)std::min<int64_t>(card, ebm_card);  // no count is larger
   // Sparse shapes (fewer than kBsitSparse columns per result key): a count table of 256 KiB per key would be
   // zeroed and read for a handful of counts, so the values are sorted and run-length encoded instead and the
@@ -1792,59 +1791,34 @@ static int ctx_bsi_transpose(Ctx* c, int32_t batch, int nbits, int has_found, in
     return st;
   }
   const int m = 1 + (64 - __builtin_clzll(most));
-  const size_t cells = K * (size_t)m;
-  CHK(c->bsib_info.ensure(kBsibInfoBytes * cells + 16));
-  CHK(c->bsib_size.ensure(8 * (cells + 1)));
-  CHK(c->bsib_part.ensure(8 * (scan_parts(cells) + 1)));
-  CHK(c->bsib_per.ensure(8 * (4 * (size_t)m + 4)));
-  CHK(c->bsia_run.ensure(K + 16));
+  constexpr size_t kTab = 4 * 65536;  // a result key's count table: after the cells of a pass
+  BsibPlan plan;
+  CHK(plan.begin(c, K, m, kTab, false, true));
   CHK(c->bsit_kcard.ensure(4 * K + 16));
   CHK(c->bsit_full.ensure(K + 16));
-  uint64_t* size = c->bsib_size.as<uint64_t>();
-  unsigned long long* per = c->bsib_per.as<unsigned long long>();
-  HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
   HIPCHK(hipMemsetAsync(c->bsia_run.p, 0, K, s));
   HIPCHK(hipMemsetAsync(c->bsit_kcard.p, 0, 4 * K, s));
   HIPCHK(hipMemsetAsync(c->bsit_full.p, 0, K, s));
-  constexpr size_t kTab = 4 * 65536;  // a result key's count table
-  const size_t per_key = kTab + 8192 * (size_t)m;
-  const size_t P = std::min(K, std::max<size_t>(1, bsib_budget() / per_key));  // result keys per pass
-  DevBuf ws;  // the cells of a pass, then its count tables; back to the pool at the end (freed on an error)
-  CHK(pool_take(c, ws, per_key * P));
-  uint32_t* tab = reinterpret_cast<uint32_t*>(ws.as<uint8_t>() + 8192 * (size_t)m * P);
+  uint32_t* tab = reinterpret_cast<uint32_t*>(plan.ws.as<uint8_t>() + 8192 * (size_t)m * plan.P);
   sw.rkoff = c->bsib_pkoff.as<uint32_t>();
   sw.tab = tab;
-  auto fill_stats = [&](size_t k_lo, size_t k_hi, bool stats) -> int {  // every cell of the pass is written
+  auto fill = [&](size_t k_lo, size_t k_hi, bool stats) -> int {  // every cell of the pass is written
     HIPCHK(hipMemsetAsync(tab, 0, kTab * (k_hi - k_lo), s));
     BsiTrSweep p = sw;
     p.k_lo = (uint32_t)k_lo;
     p.k_hi = (uint32_t)k_hi;
     launch_bsitr_sweep(s, 1, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, p);
-    launch_bsitr_cells(s, tab, (uint32_t)k_lo, (uint32_t)k_hi, m, ws.as<uint8_t>(), stats,
+    launch_bsitr_cells(s, tab, (uint32_t)k_lo, (uint32_t)k_hi, m, plan.ws.as<uint8_t>(), stats,
                        reinterpret_cast<uint32_t*>(sc + 2), c->bsit_kcard.as<uint32_t>(), c->bsit_full.as<uint8_t>(),
                        sc + 3);
     return RBG_OK;
   };
-  auto fill = [&](size_t k_lo, size_t k_hi) -> int { return fill_stats(k_lo, k_hi, false); };
-  std::vector<unsigned long long> hp(4 * (size_t)m + 4);
-  uint64_t total = 0;
-  unsigned long long h3[2] = {};  // {min, max}, full keys
-  auto plan_all = [&](bool first) -> int {
-    for (size_t k_lo = 0; k_lo < K; k_lo += P) {
-      const size_t k_hi = std::min(K, k_lo + P);
-      if (first || P < K) CHK(fill_stats(k_lo, k_hi, first));
-      launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, 0, c->bsib_info.p, size, per, per + 4 * m,
-                       c->bsia_run.as<uint8_t>());
-    }
-    launch_exclusive_scan(s, size, size, cells, c->bsib_part.as<uint64_t>(), size + cells);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&total, size + cells, 8, hipMemcpyDeviceToHost, s));
-    if (first) HIPCHK(hipMemcpyAsync(h3, sc + 2, 16, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
+  unsigned long long h3[2] = {};  // {min, max}, full keys: the first sweep's statistics
+  auto read_h3 = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(h3, sc + 2, 16, hipMemcpyDeviceToHost, s));
     return RBG_OK;
   };
-  CHK(plan_all(true));
+  CHK(plan.sweep(true, fill, read_h3));
   dbg(s, "bsi_transpose: count + plan");
   if (h3[1] && batch_size > 4096 && card > batch_size) {  // a full key fed by several batches of bitmap size
     const size_t n_full = (size_t)h3[1];
@@ -1875,8 +1849,7 @@ static int ctx_bsi_transpose(Ctx* c, int32_t batch, int nbits, int has_found, in
       HIPCHK(hipGetLastError());
       pool_put(c, dt);  // whatever takes them next is enqueued on this stream, after the kernels
       pool_put(c, bits);
-      HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
-      CHK(plan_all(false));  // a flagged key is a run container of one run: sizes and kinds again
+      CHK(plan.sweep(false, fill));  // a flagged key is a run container of one run: sizes and kinds again
       dbg(s, "bsi_transpose: full keys");
     } else {
       // the bitmaps exceed the budget: the (rank, value) pairs of the full keys go to the host
@@ -1916,15 +1889,14 @@ static int ctx_bsi_transpose(Ctx* c, int32_t batch, int nbits, int has_found, in
         CHK(pinned_ensure(c, K));
         std::memcpy(c->pinned, run.data(), K);
         HIPCHK(hipMemcpyAsync(c->bsia_run.p, c->pinned, K, hipMemcpyHostToDevice, s));
-        HIPCHK(hipMemsetAsync(per, 0, 8 * (4 * (size_t)m + 4), s));
-        CHK(plan_all(false));  // the flagged keys are a run container of one run: sizes and kinds again
+        CHK(plan.sweep(false, fill));  // the flagged keys are a run container of one run: sizes and kinds again
         dbg(s, "bsi_transpose: full keys (host)");
       }
     }
   }
   const uint32_t mn = (uint32_t)h3[0], mx = (uint32_t)(h3[0] >> 32);
   const int nb = mx ? 32 - __builtin_clz(mx) : 0;
-  CHK(bsib_emit(c, K, m, 1 + nb, P, ws, hp, total, fill, "bsi_transpose: write", out_id));
+  CHK(plan.emit(1 + nb, fill, "bsi_transpose: write", out_id));
   out3[0] = nb;
   out3[1] = (int32_t)mn;
   out3[2] = (int32_t)mx;

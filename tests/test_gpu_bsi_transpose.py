@@ -237,16 +237,40 @@ def test_full_key_cases_with_the_flag_from_the_host(eng, monkeypatch, number):
     assert _kinds(r.ebm) == ((0, 0, 1) if run else (0, 1, 0)), number
 
 
-def test_two_full_keys_next_to_other_keys(eng):
+_two_full = {}
+
+
+def _two_full_keys():
     """batchSize 20,000 over 180,000 columns: result key 3 is case 1 (a run container), key 2 holds seven values,
     key 5 becomes full in a batch of exactly 4,096 distinct values (a bitmap) -- the full keys' positions among the
-    full keys differ from their result key indexes, and their flags from each other"""
-    _, v1, _, _, _ = full_case(1)  # 80,000 columns
-    a = np.arange
-    low5 = np.concatenate([a(61440), a(61440, 65536), np.full(20000 - 4096, 61440)])
-    vals = np.concatenate([v1, (2 << 16) + a(18560) % 7, (5 << 16) + low5])
-    assert vals.size == 180000
-    r = _check(eng, index_of(a(vals.size), vals), 9)
+    full keys differ from their result key indexes, and their flags from each other; the index and its reference
+    at parallelism 9 (shared, left unchanged)"""
+    if not _two_full:
+        _, v1, _, _, _ = full_case(1)  # 80,000 columns
+        a = np.arange
+        low5 = np.concatenate([a(61440), a(61440, 65536), np.full(20000 - 4096, 61440)])
+        vals = np.concatenate([v1, (2 << 16) + a(18560) % 7, (5 << 16) + low5])
+        assert vals.size == 180000
+        o = index_of(a(vals.size), vals)
+        _two_full.update(o=o, want=transpose_reference(o, None, 9))
+    return _two_full
+
+
+def test_two_full_keys_next_to_other_keys(eng):
+    c = _two_full_keys()
+    r = _check(eng, c["o"], 9, want=c["want"])
+    assert _kinds(r.ebm) == (1, 1, 1) and O.stats(r.ebm)["card"] == 2 * 65536 + 7
+
+
+def test_two_full_keys_in_three_passes(eng, monkeypatch):
+    """the same with a budget of exactly one result key's bytes: one key per pass, and still above the 2 x 9 x
+    8192 bytes of the per-(full key, batch) bitmaps, so the flags are computed on the device and the sweep that
+    follows them has to fill every pass again"""
+    c = _two_full_keys()
+    per_key = 4 * 65536 + 8192 * (1 + (180000).bit_length())
+    assert per_key == 417792 and per_key >= 2 * 9 * 8192
+    monkeypatch.setenv("RBG_BSI_BUILD_WS", str(per_key))
+    r = _check(eng, c["o"], 9, want=c["want"])
     assert _kinds(r.ebm) == (1, 1, 1) and O.stats(r.ebm)["card"] == 2 * 65536 + 7
 
 
