@@ -450,9 +450,9 @@ int rbg_ctx_batch_fetch_range(rbg_ctx* ctx, int32_t batch, size_t first, size_t 
  * the portable format only by rbg_ctx_serialize / rbg_ctx_fetch. */
 int rbg_ctx_pairwise(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib);
 /* rbg_ctx_pairwise followed by rbg_ctx_serialize (RoaringBitmap.and/or/xor/andNot, then serialize,
- * RB/RoaringBitmap.java:377-473,3017-3019), as one pipeline: the key universe is cut into
- * RBG_SER_PIPE (default 4) ranges and range r's placement and payload copies run on a second stream
- * while range r + 1 computes.  The same bytes as the two calls. */
+ * RB/RoaringBitmap.java:377-473,3017-3019) in one call: the same launches and the same bytes as the
+ * two calls.  (Overlapping the serialization of one key range with the compute of the next was measured
+ * slower at every split and removed: profiles/r05/experiments/c2_pipelined_serialization.txt.) */
 int rbg_ctx_pairwise_serialized(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib);
 /* rbg_ctx_pairwise restricted to keys [key_lo, key_hi): one key-range shard of the op (each
  * key's result depends on that key's containers only, RB/RoaringBitmap.java:382-399); the
@@ -611,9 +611,6 @@ int rbg_ctx_bsi_to_pairs(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, 
  * known on return (from the batch's cardinalities). */
 int rbg_ctx_bsi_to_pairs_device(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int columns64, int values64,
                                 void* columns_dev, void* values_dev, uint64_t* n_out);
-/* Retired diagnostic (the per-phase clock builds of rounds 2-5 are gone; their results are in
- * profiles/): writes 20 zeros.  Kept so bindings of earlier rounds still link. */
-int rbg_debug_stamps(uint64_t* out20, int reset);
 /* Containers per input bitmap of a batch (out has n == bitmaps entries). */
 int rbg_ctx_batch_counts(rbg_ctx* ctx, int32_t batch, uint32_t* out, size_t n);
 /* Algorithmic input bytes per key (payload + 4 B descriptor per container) of the

@@ -370,11 +370,6 @@ __device__ __forceinline__ uint64_t mat_unit_word(const CDesc& d, const uint8_t*
   return x;
 }
 
-// the per-workgroup probe build of k_bsi_reg was retired in round 6 (its results: profiles/r05/experiments)
-void debug_bsi_stamps(uint64_t* out20, bool) {
-  for (int i = 0; i < 20; i++) out20[i] = 0;
-}
-
 // task record of a result written by k_bsi_reg / k_bsi_defer (wg_place's record)
 __device__ __forceinline__ void bsi_rec(uint32_t t, const OutCtx& oc, bool keep, const uint8_t* src, uint32_t len,
                                         uint32_t card, uint32_t key, int kind) {

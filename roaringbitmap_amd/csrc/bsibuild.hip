@@ -74,7 +74,6 @@ __device__ __forceinline__ uint32_t bsib_next_lane_or(uint32_t x, uint32_t last)
 // takes part in every scan; a lane past the end or outside the pass holds a word index no pair has and no
 // bits.  ws: (k_hi - k_lo) x m bitmaps; the word index (< 2^31: the engine bounds a pass) of input j is
 // idx + 2048 j.
-template <bool PRE>
 __global__ __launch_bounds__(256) void k_bsib_scatter(const uint32_t* __restrict__ col, const int32_t* __restrict__ val,
                                                       uint64_t n, const uint32_t* __restrict__ pkey_off, uint32_t k_lo,
                                                       uint32_t k_hi, int m, uint32_t* __restrict__ ws) {
@@ -106,7 +105,7 @@ __global__ __launch_bounds__(256) void k_bsib_scatter(const uint32_t* __restrict
       BSIB_STEP(s31, 0x143, 0xc)   // row_bcast:31 -> rows 2, 3
       if (bits && last) {
         uint32_t* w = ws + ((uint64_t)idx + 2048u * (uint32_t)j);
-        const uint32_t cur = PRE ? __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+        const uint32_t cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((cur & bits) != bits) atomicOr(w, bits);
       }
     }
@@ -247,11 +246,10 @@ void launch_bsib_minmax(hipStream_t s, const int32_t* v, uint64_t n, int* mm) {
 }
 
 void launch_bsib_scatter(hipStream_t s, const uint32_t* col, const int32_t* val, uint64_t n, const uint32_t* pkey_off,
-                         uint32_t k_lo, uint32_t k_hi, int m, uint32_t* ws, bool precheck) {
+                         uint32_t k_lo, uint32_t k_hi, int m, uint32_t* ws) {
   if (!n || k_hi <= k_lo) return;
   const dim3 grid(bsib_grid(n, 256, 256 * 16)), block(256);
-  if (precheck) hipLaunchKernelGGL(k_bsib_scatter<true>, grid, block, 0, s, col, val, n, pkey_off, k_lo, k_hi, m, ws);
-  else hipLaunchKernelGGL(k_bsib_scatter<false>, grid, block, 0, s, col, val, n, pkey_off, k_lo, k_hi, m, ws);
+  hipLaunchKernelGGL(k_bsib_scatter, grid, block, 0, s, col, val, n, pkey_off, k_lo, k_hi, m, ws);
 }
 
 void launch_bsib_plan(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t k_hi, int m, int run_optimize,

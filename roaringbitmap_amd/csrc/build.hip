@@ -87,9 +87,10 @@ __device__ __forceinline__ uint32_t next_lane_or(uint32_t x, uint32_t last) {
 
 // Every wave runs whole rounds of 64 values (the trip count is wave-uniform, so every lane takes
 // part in every scan); a lane past the end holds a word index no value has and no bits.
-// PRE: the word is read first (from L2, where the atomics execute) and the atomic skipped when its bits
+// The word is read first (from L2, where the atomics execute) and the atomic skipped when its bits
 // are all set already.  Bits are only ever set, so a stale read can cost an atomic but never lose one.
-template <bool PRE>
+// (18x on 2^27 values of one key, -16 % on sorted dense input: DESIGN §3.9,
+// profiles/from_values/build_perf.txt)
 __global__ __launch_bounds__(256) void k_bld_scatter(const uint32_t* __restrict__ v, uint64_t n,
                                                      const uint32_t* __restrict__ key_off,
                                                      uint32_t* __restrict__ ws) {
@@ -115,7 +116,7 @@ __global__ __launch_bounds__(256) void k_bld_scatter(const uint32_t* __restrict_
     BLD_STEP(0x143, 0xc)  // row_bcast:31 -> rows 2, 3
     const uint32_t nxt = next_lane_or(idx, 0xFFFFFFFFu);
     if (bits && nxt != idx) {
-      const uint32_t cur = PRE ? __hip_atomic_load(&ws[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
+      const uint32_t cur = __hip_atomic_load(&ws[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if ((cur & bits) != bits) atomicOr(&ws[idx], bits);
     }
   }
@@ -223,12 +224,10 @@ void launch_bld_keys(hipStream_t s, const uint32_t* v, uint64_t n, uint8_t* flag
   hipLaunchKernelGGL(k_bld_key_scan, dim3(256), dim3(256), 0, s, (const uint8_t*)flag, keys, key_off, n_ctr);
 }
 
-void launch_bld_scatter(hipStream_t s, const uint32_t* v, uint64_t n, const uint32_t* key_off, uint32_t* ws,
-                        bool precheck) {
+void launch_bld_scatter(hipStream_t s, const uint32_t* v, uint64_t n, const uint32_t* key_off, uint32_t* ws) {
   if (!n) return;
   const dim3 grid(bld_grid(n, 256, 256 * 16)), block(256);
-  if (precheck) hipLaunchKernelGGL(k_bld_scatter<true>, grid, block, 0, s, v, n, key_off, ws);
-  else hipLaunchKernelGGL(k_bld_scatter<false>, grid, block, 0, s, v, n, key_off, ws);
+  hipLaunchKernelGGL(k_bld_scatter, grid, block, 0, s, v, n, key_off, ws);
 }
 
 void launch_bld_plan(hipStream_t s, const uint8_t* ws, uint64_t n_ctr, int run_optimize, void* info, uint64_t* size,

@@ -153,8 +153,6 @@ struct DecBufs {  // scratch of the device decode (decode.hip), reused across lo
       size, cpart;
 };
 
-constexpr int kPipeMax = 16;  // key ranges of a pipelined pairwise op + serialization
-
 struct Ctx {
   int device = 0;
   DecBufs dec;
@@ -162,10 +160,6 @@ struct Ctx {
   uint32_t epoch = 0;
   DevBuf pc_cnt, pc_part, pc_items, pc_large;  // batched andCardinality scratch
   hipStream_t stream = nullptr;
-  // pipelined op + serialization (ctx_pairwise_ser): placement and payload copies of key range r
-  // run on stream2 while range r + 1 computes on stream
-  hipStream_t stream2 = nullptr;
-  hipEvent_t pipe_ev[kPipeMax + 1] = {};
   std::vector<std::unique_ptr<Batch>> batches;
   uint64_t* zlb = nullptr;    // look-back state the next plan kernel zeroes (null: none)
   uint64_t* ztile = nullptr;
@@ -251,9 +245,6 @@ Ctx::~Ctx() {
   prof_free();
   if (pinned) (void)hipHostFree(pinned);
   batches.clear();
-  for (hipEvent_t e : pipe_ev)
-    if (e) (void)hipEventDestroy(e);
-  if (stream2) (void)hipStreamDestroy(stream2);
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -342,8 +333,8 @@ static int ctx_init(Ctx* c, int device) {
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   CHK(c->by_key.ensure(sizeof(PTask) * kMaxKeys));  // Task (wide) or PTask (pairwise) records
   CHK(c->flag.ensure(kMaxKeys));
-  // (+ 32768: the pairwise direct mode lays its tasks out wave-major in regions of a multiple of
-  // 4 records, at most 4 per resident wave (<= 8192 waves) past the task count)
+  // (+ 32768 records past the largest task list: sized for the removed key-order pairwise form's
+  // wave-major layout; kept so no op's buffer shrinks)
   CHK(c->tasks.ensure(sizeof(PTask) * (kMaxKeys + 32768)));
   CHK(c->ntasks.ensure(64));
   CHK(c->wg_count.ensure(4 * 256));
@@ -964,11 +955,6 @@ static int ctx_point(Ctx* c, int op, int32_t batch, size_t i, const uint32_t* q_
   CHK(ctx_rankdir(c, B));
   const PointArgs pa{B->key_off.as<uint32_t>(), o.desc, B->payload.as<uint8_t>(), B->rd_cum.as<uint64_t>(),
                      B->rd_off.as<uint64_t>(), B->rd_aux.as<uint8_t>(), (uint32_t)o.n};
-  // RBG_PQ_NODIR=1 (measurement only, read at every call): rank with a bitmap's popcounts from word 0
-  if (op == PT_RANK) {
-    const char* e = std::getenv("RBG_PQ_NODIR");
-    if (e && e[0] == '1') op = PT_RANK_NODIR;
-  }
   launch_point(c->stream, op, pa, q_dev, n, out_dev);
   HIPCHK(hipGetLastError());
   return RBG_OK;
@@ -1045,16 +1031,6 @@ static int ctx_to_values_host(Ctx* c, int32_t batch, size_t i, uint64_t first, u
 // (build.hip).  Two read-backs: the container count (to size the workspace of 8 KiB bitmaps) and the
 // totals (payload size, kinds, cardinality).  The values are read by two kernels: they must not change
 // until the call returns.
-// the scatter reads a word before its atomic (18x on 2^27 values of one key, -16 % on sorted dense input:
-// DESIGN §3.9)
-constexpr bool kBldPrecheck = true;
-// RBG_BLD_PRECHECK=0 / 1 (measurement only, read at every call): the scatter without / with the read in front
-// of every atomic
-static bool bld_precheck() {
-  const char* e = std::getenv("RBG_BLD_PRECHECK");
-  return e ? e[0] == '1' : kBldPrecheck;
-}
-
 static int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32_t* out_id) {
   hipStream_t s = c->stream;
   const int32_t id = new_batch(c);
@@ -1085,7 +1061,7 @@ static int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt
   if (C) {
     CHK(pool_take(c, ws, 8192 * C));
     HIPCHK(hipMemsetAsync(ws.p, 0, 8192 * C, s));
-    launch_bld_scatter(s, v_dev, n, b.key_off.as<uint32_t>(), ws.as<uint32_t>(), bld_precheck());
+    launch_bld_scatter(s, v_dev, n, b.key_off.as<uint32_t>(), ws.as<uint32_t>());
     CHK(c->bld_info.ensure(kBldInfoBytes * C));
     CHK(c->bld_size.ensure(8 * C + 16));
     CHK(c->bld_part.ensure(8 * (scan_parts(C) + 1)));
@@ -1328,11 +1304,10 @@ static int ctx_bsi_from_columns(Ctx* c, const uint32_t* col_dev, const int32_t* 
   dbg(s, "bsi_from_columns: keys + min / max");
   BsibPlan plan;
   CHK(plan.begin(c, K, m, 0, run_opt, false));
-  const bool precheck = bld_precheck();
   auto scatter = [&](size_t k_lo, size_t k_hi, bool) -> int {
     HIPCHK(hipMemsetAsync(plan.ws.p, 0, 8192 * (size_t)m * (k_hi - k_lo), s));
     launch_bsib_scatter(s, col_dev, val_dev, n, c->bsib_pkoff.as<uint32_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m,
-                        plan.ws.as<uint32_t>(), precheck);
+                        plan.ws.as<uint32_t>());
     return RBG_OK;
   };
   CHK(plan.sweep(true, scatter));
@@ -1903,76 +1878,6 @@ static int ctx_bsi_transpose(Ctx* c, int32_t batch, int nbits, int has_found, in
   return RBG_OK;
 }
 
-// op RBG_OR_INPLACE: x1.or(x2) in place (RB/RoaringBitmap.java:2481-2523), the OR with Container.ior's
-// types (k_ior_fix)
-// RoaringBitmap.and / or / xor / andNot + serialize of a dense key range as K key ranges in one
-// pipeline (ctx_pairwise with pipe_k > 1): range r's compute launch runs on the context stream; its
-// placement tiles (k_place: the look-back reads the tiles the earlier ranges published, so every record
-// gets its global output index and payload offset) and its payload copies (k_serialize part 2) run on
-// stream2 while range r + 1 computes.  The header (cookie, run flags, descriptors, offsets) follows the
-// last range; the context stream then waits for stream2.  Same records, same bytes as the op followed
-// by ctx_serialize: only the order of the launches differs.  Ranges are whole placement tiles.
-// RBG_PIPE_PW_WG / RBG_PIPE_COPY_WG: workgroups per CU of the compute / copy launches (defaults:
-// resident maximum, 1).
-static int pairwise_pipelined(Ctx* c, int op, int K, PwDirect pd, Batch* A, Batch* B, OutCtx oc) {
-  hipStream_t s = c->stream;
-  if (!c->stream2) {
-    HIPCHK(hipStreamCreateWithFlags(&c->stream2, hipStreamNonBlocking));
-    for (hipEvent_t& e : c->pipe_ev) HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-  }
-  hipStream_t s2 = c->stream2;
-  K = std::min(K, kPipeMax);
-  const uint32_t n = pd.nkeys;
-  // range bounds in whole tiles
-  const uint32_t tiles = (n + kPlaceTile - 1) / kPlaceTile;
-  K = (int)std::max<uint32_t>(1, std::min<uint32_t>((uint32_t)K, tiles));
-  const int pw_wg = getenv("RBG_PIPE_PW_WG") ? atoi(getenv("RBG_PIPE_PW_WG")) : 0;
-  const int cp_wg = getenv("RBG_PIPE_COPY_WG") ? atoi(getenv("RBG_PIPE_COPY_WG")) : 1;
-  int cus = 256;
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, c->device);
-  c->mark(0);
-  c->mark(1);
-  // the first range's record -> the previous op's stream2 work (a pending header of the last
-  // pipelined op) is complete before this op reuses the records: stream waits for it at the end of
-  // every pipelined op, so nothing is needed here
-  uint32_t t_lo = 0;
-  for (int r = 0; r < K; r++) {
-    const uint32_t t_hi = r == K - 1 ? n : (uint32_t)(((uint64_t)tiles * (r + 1) / K) * kPlaceTile);
-    PwDirect d = pd;
-    d.key_lo = pd.key_lo + (int)t_lo;
-    d.nkeys = t_hi - t_lo;
-    if (r) d.zlb = d.ztile = nullptr;  // zeroed once, by the first range's launch
-    OutCtx o = oc;
-    o.recs = oc.recs + t_lo;
-    o.scratch = oc.scratch + (size_t)t_lo * kSlotBytes;
-    const int want = grid_for((d.nkeys + 3) / 4, 16384);
-    const int grid = pw_wg > 0 ? std::min(want, pw_wg * cus) : want;
-    launch_pairwise(s, op, 0, grid, c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), A->payload.as<uint8_t>(),
-                    B->payload.as<uint8_t>(), o, c->task_card.as<uint32_t>(), &d);
-    HIPCHK(hipEventRecord(c->pipe_ev[r], s));
-    HIPCHK(hipStreamWaitEvent(s2, c->pipe_ev[r], 0));
-    launch_place_tiles(s2, c->ntasks.as<uint32_t>(), oc, c->info.as<ResultInfo>(), t_lo, t_hi);
-    launch_serialize_part(s2, c->ntasks.as<uint32_t>(), oc, 2, t_lo, t_hi, cp_wg * cus);
-    t_lo = t_hi;
-  }
-  c->mark(2);
-  launch_serialize_part(s2, c->ntasks.as<uint32_t>(), oc, 1, 0, 0xFFFFFFFFu, 256);
-  HIPCHK(hipEventRecord(c->pipe_ev[kPipeMax], s2));
-  HIPCHK(hipStreamWaitEvent(s, c->pipe_ev[kPipeMax], 0));
-  c->place_pending = false;
-  c->serialized = true;
-  c->last = 1;
-  c->mark(3);
-  HIPCHK(hipGetLastError());
-  return RBG_OK;
-}
-
-// key ranges of a pipelined op + serialization (RBG_SER_PIPE; default 1 = the op, then the serialization: pipelining
-// off, measured slower at every split)
-static int pipe_ranges() {
-  const char* e = getenv("RBG_SER_PIPE");  // read per call (tests vary it)
-  return e ? std::max(1, atoi(e)) : 1;  // measured: 2-16 ranges are slower than the two calls
-}
 // ImmutableRoaringBitmap.and / andNot and MutableRoaringBitmap's static and / andNot
 // (RB/buffer/ImmutableRoaringBitmap.java:299-325, 441-471; RB/buffer/MutableRoaringBitmap.java:235-301):
 // the pairwise plan, then k_pair_buf (the buffer package's container types).  A run result above
@@ -2128,8 +2033,10 @@ static int ctx_add_offset(Ctx* c, int32_t ia, size_t ma, int64_t offset) {
   return op_end(c);
 }
 
+// op RBG_OR_INPLACE: x1.or(x2) in place (RB/RoaringBitmap.java:2481-2523), the OR with Container.ior's
+// types (k_ior_fix)
 static int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, bool card_only, int key_lo = 0,
-                        int key_hi = kMaxKeys, int pipe_k = 0) {
+                        int key_hi = kMaxKeys) {
   if (op == RBG_AND_BUFFER || op == RBG_ANDNOT_BUFFER) {
     if (card_only) return RBG_ERR_ILLEGAL_ARGUMENT;
     return ctx_pairwise_buffer(c, op == RBG_AND_BUFFER ? OP_AND : OP_ANDNOT, ia, ma, ib, mb, key_lo, key_hi);
@@ -2166,51 +2073,43 @@ static int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_
     case OP_ANDNOT: ub = na; break;
     default: ub = std::min<size_t>((size_t)na + nb, kMaxKeys); break;
   }
-  // Dense key ranges (the op's task bound covers at least half of the range) skip the plan
-  // launch: the compute kernel takes key key_lo + t as task t and resolves it itself (one
-  // record and scratch slot per key of the range).  Sparse ones are planned and compacted
-  // first, so the kernel sees only keys with work.  RBG_PAIRWISE_PLAN=1 always plans.
-  static const bool force_plan = getenv("RBG_PAIRWISE_PLAN") != nullptr;
+  // Dense key ranges (the op's task bound covers at least half of the range) take every key of the
+  // range as a task (one record and scratch slot per key, key key_lo + t at position t).  Sparse ones
+  // are planned and compacted first, so the kernel sees only keys with work.
   const size_t nkeys = key_hi > key_lo ? (size_t)(key_hi - key_lo) : 0;
-  const bool direct = nkeys > 0 && 2 * ub >= nkeys && !force_plan;
+  const bool dense = nkeys > 0 && 2 * ub >= nkeys;
   OutCtx oc;
-  CHK(prepare_output(c, direct ? std::max(ub, nkeys) : ub, A->payload_bytes + B->payload_bytes + kStagedMax * ub,
+  CHK(prepare_output(c, dense ? std::max(ub, nkeys) : ub, A->payload_bytes + B->payload_bytes + kStagedMax * ub,
                      &oc, card_only));
   c->pending_src = {ia, ib};
   c->mark(0);
-  PwDirect pd{A->key_off.as<uint32_t>(), da, B->key_off.as<uint32_t>(), db, key_lo, (uint32_t)nkeys,
-              c->ntasks.as<uint32_t>(), c->zlb, c->ztile, (uint32_t)nkeys};
-  if (direct && pipe_k > 1 && !card_only) return pairwise_pipelined(c, op, pipe_k, pd, A, B, oc);
-  if (!direct) {
+  const PwDirect pd{key_lo};
+  if (dense) {
+    // tasks binned by estimated cost so every wave draws the same mix (k_plan_balanced)
+    // ... run by one 16-wave workgroup per CU that claims the CU's tasks through LDS (k_pair_cu)
+    launch_plan_balanced(s, plan_op, card_only ? 1 : 0, key_lo, (uint32_t)nkeys, A->key_off.as<uint32_t>(), da,
+                         A->payload.as<uint8_t>(), B->key_off.as<uint32_t>(), db, B->payload.as<uint8_t>(),
+                         c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->task_card.as<uint32_t>(), c->zlb,
+                         c->ztile);
+  } else {
     launch_plan_pairwise(s, plan_op, key_lo, key_hi, A->key_off.as<uint32_t>(), da, A->payload.as<uint8_t>(),
                          B->key_off.as<uint32_t>(), db, B->payload.as<uint8_t>(), c->wg_epoch.as<uint64_t>(),
                          next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), c->zlb, c->ztile, oc.err);
     dbg(s, "plan");
   }
-  // dense ranges: tasks binned by estimated cost so every wave draws the same mix (k_plan_balanced;
-  // RBG_PW_BALANCE=0: the direct form, tasks in key order)
-  const char* bal_env = getenv("RBG_PW_BALANCE");
-  const bool balanced = direct && (!bal_env || atoi(bal_env) != 0);
-  // ... run by one 16-wave workgroup per CU that claims the CU's tasks through LDS (k_pair_cu)
-  if (balanced)
-    launch_plan_balanced(s, plan_op, card_only ? 1 : 0, key_lo, (uint32_t)nkeys, A->key_off.as<uint32_t>(), da,
-                         A->payload.as<uint8_t>(), B->key_off.as<uint32_t>(), db, B->payload.as<uint8_t>(),
-                         c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->task_card.as<uint32_t>(), c->zlb,
-                         c->ztile);
   c->mark(1);
-  // the compute kernel sums its kept results per tile for the serialization (k_serialize_agg) when a
-  // plan kernel has zeroed the sums first: the balanced (dense) and planned (sparse) forms; the direct
-  // form zeroes inside the compute kernel itself
-  if (!card_only && (balanced || !direct)) {
+  // the compute kernel sums its kept results per tile for the serialization (k_serialize_agg): either
+  // plan kernel has zeroed the sums first
+  if (!card_only) {
     oc.tile_agg = reinterpret_cast<unsigned long long*>(oc.tile_status + 2 * kMaxTiles);
     c->pending.tile_agg = oc.tile_agg;
     c->agg_ok = true;
   }
   // 4 waves (tasks) per workgroup, clamped to the resident grid
-  const int grid = grid_for(((direct ? nkeys : ub) + 3) / 4, 16384);
+  const int grid = grid_for(((dense ? nkeys : ub) + 3) / 4, 16384);
   launch_pairwise(s, op, card_only ? 1 : 0, grid, c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(),
                   A->payload.as<uint8_t>(), B->payload.as<uint8_t>(), oc, c->task_card.as<uint32_t>(),
-                  direct ? &pd : nullptr, balanced);
+                  dense ? &pd : nullptr);
   dbg(s, "pairwise");
   c->mark(2);
   if (card_only) {
@@ -3940,7 +3839,7 @@ int rbg_pairwise(int op, const uint8_t* a, size_t a_len, const uint8_t* b, size_
   const size_t lens[2] = {a_len, b_len};
   int32_t ids[2];
   CHK(os.load_separate(bufs, lens, 2, ids));  // one upload for both operands
-  CHK(ctx_pairwise(c, op, ids[0], 0, ids[1], 0, false, 0, kMaxKeys, op <= RBG_ANDNOT ? pipe_ranges() : 0));
+  CHK(ctx_pairwise(c, op, ids[0], 0, ids[1], 0, false));
   return ctx_fetch(c, out);
 }
 
@@ -4467,9 +4366,8 @@ int rbg_ctx_release(rbg_ctx* ctx, int32_t batch) {
       std::find(c.pending_src.begin(), c.pending_src.end(), batch) != c.pending_src.end())
     CHK(ctx_serialize(&c));
   // No host sync: the buffers go to this context's pool, and whatever reuses them is enqueued on
-  // the same stream after every launch that reads them (a pipelined op's second stream is joined
-  // back into it at the op's end); a pooled buffer that is freed goes through hipFree, which waits
-  // for the device.
+  // the same stream after every launch that reads them; a pooled buffer that is freed goes through
+  // hipFree, which waits for the device.
   for (DevBuf* d : {&b->keys, &b->desc, &b->bm, &b->key_off, &b->bm_off, &b->payload, &b->ro_stats,
                     &b->bsi_tasks, &b->bsi_nt, &b->bsi_table, &b->rd_cum, &b->rd_off, &b->rd_aux})
     pool_put(&c, *d);
@@ -4520,8 +4418,8 @@ int rbg_ctx_pairwise_serialized(rbg_ctx* ctx, int op, int32_t a, size_t ia, int3
   Ctx* c;
   CHK(session(ctx, &c));
   if (op < 0 || op > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
-  CHK(ctx_pairwise(c, op, a, ia, b, ib, false, 0, kMaxKeys, pipe_ranges()));
-  return ctx_serialize(c);  // no-op after the pipelined form
+  CHK(ctx_pairwise(c, op, a, ia, b, ib, false));
+  return ctx_serialize(c);
 }
 int rbg_ctx_pairwise_range(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib, int key_lo, int key_hi) {
   Ctx* c;
@@ -4797,12 +4695,6 @@ int rbg_bsi_get_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const*
   int32_t id;
   CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, (size_t)nbits, nullptr, 0, &id));
   return ctx_bsi_get_values_host(c, id, nbits, 0, columns, n, out);
-}
-int rbg_debug_stamps(uint64_t* out20, int reset) {
-  if (!out20) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (getenv("RBG_DEBUG_BSI")) debug_bsi_stamps(out20, reset != 0);
-  else debug_stamps(out20, reset != 0);
-  return RBG_OK;
 }
 int rbg_ctx_pair_bytes(rbg_ctx* ctx, int32_t batch, int64_t* out2) {
   if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;

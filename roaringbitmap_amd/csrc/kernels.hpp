@@ -241,28 +241,15 @@ void launch_plan_pairwise(hipStream_t s, int op, int key_lo, int key_hi, const u
                           uint64_t* wg_epoch, uint32_t epoch, PTask* tasks, uint32_t* n_tasks, uint64_t* zlb,
                           uint64_t* ztile, uint32_t* err);
 // mode 0: materialise results (task slots + records); mode 1: andCardinality into task_card
-// Direct mode of the pairwise compute kernel (no plan launch): task t = key key_lo + t over
-// nkeys keys, resolved by the kernel through both operands' key CSR; it also writes the task
-// count (n_tasks_out) and zeroes the op's look-back state (zlb, ztile), as the plan would.
+// A dense key range of the pairwise compute kernel: the record of key k is at position k - key_lo.
 struct PwDirect {
-  const uint32_t* koa;
-  const CDesc* da;
-  const uint32_t* kob;
-  const CDesc* db;
   int key_lo;
-  uint32_t nkeys;
-  uint32_t* n_tasks_out;
-  uint64_t* zlb;
-  uint64_t* ztile;
-  uint32_t n_tasks_write;  // the task count block 0 writes to n_tasks_out (a pipelined op's total over its ranges)
 };
-// direct: null = tasks / nt from launch_plan_pairwise; balanced (with direct): tasks / nt[0..1] from
-// launch_plan_balanced, records at key positions (direct->key_lo)
-// balanced: k_plan_balanced's list (dense ranges), run by k_pair_cu (one 16-wave workgroup per CU, tasks
-// claimed from the CU's share)
+// dense: null = tasks / nt from launch_plan_pairwise (sparse ranges), run by k_pair_wave; else tasks /
+// nt[0..1] from launch_plan_balanced (dense ranges), records at key positions (dense->key_lo), run by
+// k_pair_cu (one 16-wave workgroup per CU, tasks claimed from the CU's share)
 void launch_pairwise(hipStream_t s, int op, int mode, int grid, const PTask* tasks, const uint32_t* nt,
-                     const uint8_t* pa, const uint8_t* pb, OutCtx oc, uint32_t* task_card, const PwDirect* direct,
-                     bool balanced = false);
+                     const uint8_t* pa, const uint8_t* pb, OutCtx oc, uint32_t* task_card, const PwDirect* dense);
 // dense key ranges: every key's task resolved and ordered by estimated cost within its 256-key segment
 // (heaviest first, rotated by the segment index) into tasks[]; n_tasks[0] = n_tasks[1] = nkeys (records
 // and list positions, one per key: keys without a task are marked, with an empty record / a zero count)
@@ -270,10 +257,6 @@ void launch_plan_balanced(hipStream_t s, int op, int mode, int key_lo, uint32_t 
                           const CDesc* da, const uint8_t* pa, const uint32_t* kob, const CDesc* db, const uint8_t* pb,
                           PTask* tasks, uint32_t* n_tasks, OutCtx oc, uint32_t* task_card, uint64_t* zlb,
                           uint64_t* ztile);
-// retired diagnostic (per-phase clock totals of the pairwise kernel): zeroes
-void debug_stamps(uint64_t* out20, bool reset);
-// retired diagnostic (per-workgroup clocks of k_bsi_reg): zeroes
-void debug_bsi_stamps(uint64_t* out20, bool reset);
 void launch_wide(hipStream_t s, int mode, int grid, const Task* tasks, const uint32_t* nt, WideArgs args, OutCtx oc,
                  uint32_t* task_card);
 // result materialisation: k_place = compaction scan over the task records
@@ -285,14 +268,6 @@ void launch_place(hipStream_t s, const uint32_t* nt, OutCtx oc, ResultInfo* info
 // one workgroup per kAggTile records, no look-back; also writes info, the totals word and the result's
 // cardinality like k_place.  max_tasks: an upper bound of *nt (the grid)
 void launch_serialize_agg(hipStream_t s, const uint32_t* nt, OutCtx oc, ResultInfo* info, size_t max_tasks);
-// the placement tiles covering tasks [t_lo, t_hi) (t_lo a multiple of the 1,024-record tile), for a
-// pipelined op whose key ranges are placed one launch each, in order
-void launch_place_tiles(hipStream_t s, const uint32_t* nt, OutCtx oc, ResultInfo* info, uint32_t t_lo, uint32_t t_hi);
-constexpr uint32_t kPlaceTile = 1024;
-// one part of k_serialize: part 1 = the header (cookie, run flags, descriptors, offsets; every record
-// placed), part 2 = the payload copies of records [t_lo, t_hi); grid: workgroups to launch (clamped)
-void launch_serialize_part(hipStream_t s, const uint32_t* nt, OutCtx oc, int part, uint32_t t_lo, uint32_t t_hi,
-                           int grid);
 void launch_spec_fix(hipStream_t s, const uint32_t* nt, OutCtx oc);
 void launch_serialize(hipStream_t s, const uint32_t* nt, OutCtx oc);
 // key shard of a global bitmap: payloads into payload_dst, 4 B descriptors into desc, global
@@ -488,9 +463,8 @@ void launch_rsel_write(hipStream_t s, const CDesc* desc, const uint32_t* bm, con
 
 // rankdir.hip: the rank directory of a single-bitmap key-major batch and the point queries over it
 // (rank / select / contains / nextValue / previousValue, RB/RoaringBitmap.java:1693, 2574-2624, 2820-2883)
-// == RBG_PQ_* (roaring_mi355x.h); PT_RANK_NODIR (internal, RBG_PQ_NODIR=1): rank with a bitmap's popcounts from
-// word 0, the baseline the directory is measured against
-enum PointOp : int { PT_RANK = 0, PT_SELECT = 1, PT_CONTAINS = 2, PT_NEXT = 3, PT_PREV = 4, PT_RANK_NODIR = 16 };
+// == RBG_PQ_* (roaring_mi355x.h)
+enum PointOp : int { PT_RANK = 0, PT_SELECT = 1, PT_CONTAINS = 2, PT_NEXT = 3, PT_PREV = 4 };
 struct PointArgs {
   const uint32_t* key_off;  // the batch's key CSR (65,537 entries)
   const CDesc* desc;
@@ -518,10 +492,8 @@ void launch_to_values(hipStream_t s, PointArgs a, uint64_t first, uint64_t count
 // flag: 65,536 bytes, zeroed by the caller; keys: min(n, 65536) u16; key_off: 65,537 u32; *n_ctr = C
 void launch_bld_keys(hipStream_t s, const uint32_t* v, uint64_t n, uint8_t* flag, uint16_t* keys, uint32_t* key_off,
                      unsigned long long* n_ctr);
-// ws: C bitmaps of 8 KiB, zeroed by the caller; precheck: read a word before its atomic and skip the
-// atomic when the bits are set already
-void launch_bld_scatter(hipStream_t s, const uint32_t* v, uint64_t n, const uint32_t* key_off, uint32_t* ws,
-                        bool precheck);
+// ws: C bitmaps of 8 KiB, zeroed by the caller
+void launch_bld_scatter(hipStream_t s, const uint32_t* v, uint64_t n, const uint32_t* key_off, uint32_t* ws);
 constexpr size_t kBldInfoBytes = 8;  // per container: the plan's (card, nruns, kind)
 // size[i] = slot bytes of container i; totals (u64, zeroed by the caller) += {#A, #B, #R, serialized
 // payload bytes, cardinality}
@@ -539,7 +511,7 @@ void launch_bsib_minmax(hipStream_t s, const int32_t* v, uint64_t n, int* mm);
 // the columns), m = nbits + 1 inputs.  ws: (k_hi - k_lo) x m bitmaps of 8 KiB, zeroed by the caller, below
 // 2^31 words.
 void launch_bsib_scatter(hipStream_t s, const uint32_t* col, const int32_t* val, uint64_t n, const uint32_t* pkey_off,
-                         uint32_t k_lo, uint32_t k_hi, int m, uint32_t* ws, bool precheck);
+                         uint32_t k_lo, uint32_t k_hi, int m, uint32_t* ws);
 constexpr size_t kBsibInfoBytes = 8;  // per (key index, input) cell: the plan's (card, nruns, kind)
 // a cell's size word: container count (0 / 1) << kBsibCountShift | slot bytes; one scan places both
 constexpr int kBsibCountShift = 40;

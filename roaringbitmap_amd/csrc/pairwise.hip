@@ -477,22 +477,6 @@ __device__ __forceinline__ void bitmap_class_task(uint32_t t, const PTask& tk, c
   w_place(t, true, nullptr, true, lds, len, (uint32_t)c, tk.key, kind, oc);
 }
 
-// 32 B task record through the scalar cache (wave-uniform address)
-
-// ---------------------------------------------------------------------------
-// Direct mode: the compute kernel resolves its tasks itself (no plan launch).  Task t is key
-// key_lo + t (see k_pair_wave).  A key without a task (by the op's key rule,
-// RB/RoaringBitmap.java:382-400 and, :864-896 or, :1076-1113 xor, :449-471 andNot) gives an
-// empty record (or a zero count).
-// does key k give a task of op OP (the plan kernel's rule)
-template <int OP>
-__device__ __forceinline__ bool has_task(const PTask& t) {
-  const bool ia = t.kind_a != kAbsent, ib = t.kind_b != kAbsent;
-  if (OP == OP_OR || OP == OP_XOR) return ia || ib;
-  if (OP == OP_ANDNOT) return ia;
-  return ia && ib;
-}
-
 template <int OP, int MODE>
 __device__ __forceinline__ void any_task(uint32_t t, const PTask& tk, const uint8_t* pa, const uint8_t* pb,
                                          const OutCtx& oc, uint32_t* task_card, uint32_t* lds) {
@@ -509,71 +493,19 @@ __device__ __forceinline__ void any_task(uint32_t t, const PTask& tk, const uint
 // and bitmap-class tasks share the launch: separate kernels per class were
 // measured 15 % slower on the C2 mix (tail + an extra dependent index load).
 // MODE 0: materialise results.  MODE 1: andCardinality only (task_card[t]).
-// DIRECT false: planned task list (key order, sparse key ranges); true: direct (task t = key key_lo + t; the
-// pipelined op's key ranges, and dense ranges with RBG_PW_BALANCE=0)
-template <int OP, int MODE, bool DIRECT>
+// The planned task list (key order, sparse key ranges); dense ranges run k_pair_cu below.
+template <int OP, int MODE>
 __global__ __launch_bounds__(256, 4) void k_pair_wave(const PTask* __restrict__ tasks,
                                                       const uint32_t* __restrict__ n_tasks, const uint8_t* pa,
-                                                      const uint8_t* pb, OutCtx oc, uint32_t* __restrict__ task_card,
-                                                      PwDirect dsrc) {
+                                                      const uint8_t* pb, OutCtx oc, uint32_t* __restrict__ task_card) {
   __shared__ __align__(16) uint32_t lds_all[kWaves][kWaveLds];
-  if (DIRECT) {
-    // the plan kernel's other duties: the task count and the op's zeroed look-back state
-    plan_zero(dsrc.zlb, dsrc.ztile);
-    if (blockIdx.x == 0 && threadIdx.x == 0) dsrc.n_tasks_out[0] = dsrc.n_tasks_write;
-  }
-  const uint32_t nt = DIRECT ? dsrc.nkeys : uni(*n_tasks);
+  const uint32_t nt = uni(*n_tasks);
   const int w = threadIdx.x >> 6;
   uint32_t* lds = lds_all[w];
   const uint32_t stride = gridDim.x * kWaves;
   const uint32_t t0 = uni(blockIdx.x * kWaves + w);
   if (t0 >= nt) return;
   uint32_t t = t0;
-  if (DIRECT) {
-    // The wave first resolves all of its tasks at once (lane k: task t0 + k * stride, vector
-    // loads through both key CSRs) into its own region of the task buffer, wave-major, then
-    // runs them with the planned form's one scalar record load per task.  (Resolving each
-    // task through a chain of scalar loads in the loop made every load's result wait at the
-    // loop head: SMEM returns out of order, so any use waits for all of them.)
-    // tasks of the first wave (the most), rounded to 4 records (128 B): no scalar-cache line
-    // holds records of two waves
-    const uint32_t per = (((nt + stride - 1) / stride) + 3) & ~3u;
-    PTask* mine = const_cast<PTask*>(tasks) + (size_t)t0 * per;
-    const int l = lane_id();
-    for (uint32_t k0 = 0; k0 < per; k0 += 64) {
-      const uint32_t k = k0 + (uint32_t)l, tk = t0 + k * stride;
-      if (k < per && tk < nt) {
-        const uint32_t key = (uint32_t)dsrc.key_lo + tk;
-        PTask r;
-        resolve(dsrc.koa, dsrc.da, pa, key, r.slot_a, r.card_a, r.kind_a, r.nruns_a);
-        resolve(dsrc.kob, dsrc.db, pb, key, r.slot_b, r.card_b, r.kind_b, r.nruns_b);
-        r.key = (uint16_t)key;
-        mine[k] = r;
-      }
-    }
-    // the records are read back through the scalar cache (a fresh line per wave region: no
-    // other wave writes it, and the scalar cache holds nothing of it yet)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the stores are in the L2 the scalar loads read
-    uint32_t k = 0;
-    PTask cur = load_task(mine, 0);
-    for (;;) {
-      const uint32_t tn = t + stride;
-      PTask nxt;
-      if (tn < nt) nxt = load_task(mine, k + 1);  // in flight while this task runs
-      if (has_task<OP>(cur)) {
-        any_task<OP, MODE>(t, cur, pa, pb, oc, task_card, lds);
-      } else if (MODE == 1) {
-        if (l == 0) task_card[t] = 0;
-      } else {
-        w_place(t, false, nullptr, true, lds, 0, 0, cur.key, DK_A, oc);
-      }
-      if (tn >= nt) break;
-      t = tn;
-      k++;
-      cur = nxt;
-    }
-    return;
-  }
   PTask cur = load_task(tasks, t);
   for (;;) {
     const uint32_t tn = t + stride;
@@ -644,29 +576,14 @@ __global__ __launch_bounds__(1024, 1) void k_pair_cu(const PTask* __restrict__ t
 
 template <int OP, int MODE>
 static void launch_pw(hipStream_t s, int grid, const PTask* tasks, const uint32_t* nt, const uint8_t* pa,
-                      const uint8_t* pb, OutCtx oc, uint32_t* task_card, const PwDirect* direct, bool balanced) {
-  if (direct && balanced) {  // one workgroup per CU, all of them resident
+                      const uint8_t* pb, OutCtx oc, uint32_t* task_card, const PwDirect* dense) {
+  if (dense) {  // one workgroup per CU, all of them resident
     const int g = std::max(1, resident_grid((const void*)&k_pair_cu<OP, MODE>, 1024));
-    hipLaunchKernelGGL((k_pair_cu<OP, MODE>), dim3(g), dim3(1024), 0, s, tasks, nt, pa, pb, oc, task_card, *direct);
+    hipLaunchKernelGGL((k_pair_cu<OP, MODE>), dim3(g), dim3(1024), 0, s, tasks, nt, pa, pb, oc, task_card, *dense);
     return;
   }
-  if (direct) {
-    // Direct mode lays each wave's tasks out in a region of per = ceil(nt / stride) + 3 (rounded to 4)
-    // records, stride = 4 g waves: at most nt + 4 stride records.  The task buffer holds
-    // kMaxKeys + 32768 (engine.cpp: ctx_init), so stride <= 8192 waves: g <= 2048 workgroups.
-    const int g = std::max(1, std::min({grid, resident_grid((const void*)&k_pair_wave<OP, MODE, true>), 2048}));
-    hipLaunchKernelGGL((k_pair_wave<OP, MODE, true>), dim3(g), dim3(256), 0, s, tasks, nt, pa, pb, oc, task_card,
-                       *direct);
-    return;
-  }
-  const int g = std::max(1, std::min(grid, resident_grid((const void*)&k_pair_wave<OP, MODE, false>)));
-  hipLaunchKernelGGL((k_pair_wave<OP, MODE, false>), dim3(g), dim3(256), 0, s, tasks, nt, pa, pb, oc, task_card,
-                     PwDirect{});
-}
-
-// the diagnostic per-phase stamps builds were retired in round 6 (their results are in profiles/r02-r05)
-void debug_stamps(uint64_t* out20, bool) {
-  for (int i = 0; i < 20; i++) out20[i] = 0;
+  const int g = std::max(1, std::min(grid, resident_grid((const void*)&k_pair_wave<OP, MODE>)));
+  hipLaunchKernelGGL((k_pair_wave<OP, MODE>), dim3(g), dim3(256), 0, s, tasks, nt, pa, pb, oc, task_card);
 }
 
 template <int OP, int MODE>
@@ -703,10 +620,10 @@ void launch_plan_pairwise(hipStream_t s, int op, int key_lo, int key_hi, const u
 }
 
 void launch_pairwise(hipStream_t s, int op, int mode, int grid, const PTask* tasks, const uint32_t* nt, const uint8_t* pa,
-                     const uint8_t* pb, OutCtx oc, uint32_t* task_card, const PwDirect* direct, bool balanced) {
-#define RBG_LPW(O)                                                                             \
-  if (mode == 0) launch_pw<O, 0>(s, grid, tasks, nt, pa, pb, oc, task_card, direct, balanced); \
-  else launch_pw<O, 1>(s, grid, tasks, nt, pa, pb, oc, task_card, direct, balanced);
+                     const uint8_t* pb, OutCtx oc, uint32_t* task_card, const PwDirect* dense) {
+#define RBG_LPW(O)                                                                  \
+  if (mode == 0) launch_pw<O, 0>(s, grid, tasks, nt, pa, pb, oc, task_card, dense); \
+  else launch_pw<O, 1>(s, grid, tasks, nt, pa, pb, oc, task_card, dense);
   switch (op) {
     case OP_AND: RBG_LPW(OP_AND) break;
     case OP_OR: RBG_LPW(OP_OR) break;

@@ -78,9 +78,6 @@ struct PtHit {
   bool in;        // low is one of them
 };
 
-// DIR = false: the bitmap rank without its directory (popcounts from word 0), the baseline the
-// directory is measured against (PT_RANK_NODIR)
-template <bool DIR>
 __device__ __forceinline__ PtHit rank_in(const PointArgs& a, uint32_t ci, const CDesc d, uint32_t low) {
   const uint8_t* slot = a.payload + d.slot;
   if (d.kind == DK_A) {
@@ -96,13 +93,6 @@ __device__ __forceinline__ PtHit rank_in(const PointArgs& a, uint32_t ci, const 
   if (d.kind == DK_B) {
     const uint32_t wi = low >> 6, bit = low & 63;
     const uint64_t mask = ~0ull >> (63 - bit);
-    if (!DIR) {
-      const uint64_t* w = reinterpret_cast<const uint64_t*>(slot);
-      uint32_t r = 0;
-      for (uint32_t i = 0; i < wi; i++) r += (uint32_t)__popcll(w[i]);
-      const uint64_t x = w[wi];
-      return PtHit{r + (uint32_t)__popcll(x & mask), ((x >> bit) & 1) != 0};
-    }
     const uint32_t blk = wi >> 3, k = wi & 7;
     const uint16_t* dir = reinterpret_cast<const uint16_t*>(a.aux + a.aux_off[ci]);
     const uint4* p = reinterpret_cast<const uint4*>(slot) + 4 * blk;
@@ -228,10 +218,10 @@ __global__ __launch_bounds__(256) void k_point(const PointArgs a, const uint32_t
       PtHit h{0, false};
       if (present) {
         d = a.desc[ci];
-        h = rank_in<OP != PT_RANK_NODIR>(a, ci, d, low);
+        h = rank_in(a, ci, d, low);
       }
       const uint64_t r = base + h.rank;  // rankLong(x), RB/RoaringBitmap.java:2574-2592
-      if (OP == PT_RANK || OP == PT_RANK_NODIR) {
+      if (OP == PT_RANK) {
         res = (long long)r;
       } else if (OP == PT_CONTAINS) {
         res = h.in ? 1 : 0;
@@ -284,8 +274,7 @@ void launch_point(hipStream_t s, int op, PointArgs a, const uint32_t* q, uint64_
     case PT_SELECT: hipLaunchKernelGGL(k_point<PT_SELECT>, grid, block, 0, s, a, q, n, out); break;
     case PT_CONTAINS: hipLaunchKernelGGL(k_point<PT_CONTAINS>, grid, block, 0, s, a, q, n, out); break;
     case PT_NEXT: hipLaunchKernelGGL(k_point<PT_NEXT>, grid, block, 0, s, a, q, n, out); break;
-    case PT_PREV: hipLaunchKernelGGL(k_point<PT_PREV>, grid, block, 0, s, a, q, n, out); break;
-    default: hipLaunchKernelGGL(k_point<PT_RANK_NODIR>, grid, block, 0, s, a, q, n, out); break;
+    default: hipLaunchKernelGGL(k_point<PT_PREV>, grid, block, 0, s, a, q, n, out); break;
   }
 }
 

@@ -153,8 +153,8 @@ class Engine:
         check(lib().rbg_ctx_add_offset(self._ctx, int(a), int(ia), int(offset)))
 
     def pairwise_serialized(self, op, a, b, ia=0, ib=0):
-        """pairwise(op) + serialize() as one pipeline (rbg_ctx_pairwise_serialized): the result's
-        placement and payload copies for one key range overlap the next range's compute."""
+        """pairwise(op) + serialize() in one call (rbg_ctx_pairwise_serialized): the same launches and the
+        same bytes as the two calls."""
         check(lib().rbg_ctx_pairwise_serialized(self._ctx, _lib.OP[op], int(a), int(ia), int(b), int(ib)))
 
     def and_cardinality(self, a, b, ia=0, ib=0):

@@ -4,8 +4,9 @@ Build: n = 2^20, 2^24, 2^27 values, device-resident, in four distributions (unif
 over 2^26, sorted arange, all in one key); ms per Engine.from_values with and without run_optimize, and
 the route the engine had before: the host builder (rbg_from_values: one thread's sort) followed by
 Engine.load (upload + device decode), on the same values in the same process, its bytes asserted equal.
-Also the scatter kernel's two variants (RBG_BLD_PRECHECK=0 / 1: atomics alone, a read in front of every
-atomic).  All of them alternate in every round; medians are reported (the host route runs once at 2^27).
+All of them alternate in every round; medians are reported (the host route runs once at 2^27).  (The
+scatter kernel without the read in front of every atomic, which this script also alternated, was removed
+from the engine; its numbers are in profiles/from_values/build_perf.txt.)
 Bytes per build: the two reads of the input (4 n each), the workspace of C 8 KiB bitmaps zeroed once and
 read twice, and the payload written.  Arguments: [largest log2 n] [quick: the device builds alone].
 
@@ -96,16 +97,10 @@ for n in SIZES:
                 stats = eng.batch_stats(b)
             eng.release(b)
         kept.clear()
-        # gpu: the engine's default; atomics alone / read first: the scatter without / with the read in
-        # front of every atomic (RBG_BLD_PRECHECK, the engine's measurement switch, read at every call)
-        ms = {"gpu": [], "gpu ro": [], "atomics alone": [], "read first": [], "host+load": []}
+        ms = {"gpu": [], "gpu ro": [], "host+load": []}
         for _ in range(ROUNDS):
             ms["gpu"].append(window(lambda: gpu_build(False)) * 1e3)
             ms["gpu ro"].append(window(lambda: gpu_build(True)) * 1e3)
-            for key, sw in (("atomics alone", "0"), ("read first", "1")):
-                os.environ["RBG_BLD_PRECHECK"] = sw
-                ms[key].append(window(lambda: gpu_build(False)) * 1e3)
-                del os.environ["RBG_BLD_PRECHECK"]
             if QUICK or (n > 1 << 24 and ms["host+load"]):  # 6 to 9 s each at 2^27: one round
                 continue
             t0 = time.perf_counter()
@@ -121,8 +116,7 @@ for n in SIZES:
         print(f"n=2^{n.bit_length() - 1} {name}: C={C} (A {stats['array']} / B {stats['bitmap']}) "
               f"gpu {m:.3f} ms, gpu+runOptimize {med(ms['gpu ro']):.3f} ms, host from_values+load "
               f"{med(ms['host+load']):.1f} ms ({med(ms['host+load']) / m:.0f}x); {moved / 1e6:.1f} MB moved, "
-              f"{moved / m / 1e6:.1f} GB/s, {n / m / 1e6:.2f} G values/s; atomics alone "
-              f"{med(ms['atomics alone']):.3f} ms, read first {med(ms['read first']):.3f} ms; rounds gpu "
+              f"{moved / m / 1e6:.1f} GB/s, {n / m / 1e6:.2f} G values/s; rounds gpu "
               + " ".join(f"{x:.3f}" for x in ms["gpu"]), flush=True)
         assert m <= med(ms["host+load"]), "the device build is slower than the host route"
         del t, host

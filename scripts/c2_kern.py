@@ -1,6 +1,7 @@
-"""One line per task order: the C2 AND compute kernel and andCardinality kernel (engine phase events, N launches),
+"""The C2 AND compute kernel and andCardinality kernel (engine phase events, N launches)
 and the headline step (op + serialization), under the library in RBG_LIB (variant builds).  Bytes checked
-against the default form's sha (argv[1], optional)."""
+against the default form's sha (argv[1], optional).  (The key-order task form this script also timed was
+removed from the engine; its numbers are in profiles/r05/experiments/c2_balanced_order.txt.)"""
 import hashlib, os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -24,19 +25,17 @@ def kern(card=False):
     return ph[0] / max(k, 1), ph[1] / max(k, 1)
 
 
-for bal in ("0", "1"):
-    os.environ["RBG_PW_BALANCE"] = bal
-    for _ in range(3):
-        e.pairwise("and", a, b)
+for _ in range(3):
     e.pairwise("and", a, b)
-    sha = hashlib.sha256(e.fetch().serialize()).hexdigest()[:16]
-    pl, ka = kern()
-    _, kc = kern(card=True)
-    t0 = time.perf_counter()
-    for _ in range(N):
-        e.pairwise("and", a, b)
-        e.serialize()
-    e.sync()
-    st = (time.perf_counter() - t0) / N
-    print(f"lib={lib} balance={bal} plan_ms={pl:.4f} and_kernel_ms={ka:.4f} card_kernel_ms={kc:.4f} "
-          f"step_ms={st * 1e3:.4f} sha={sha}", flush=True)
+e.pairwise("and", a, b)
+sha = hashlib.sha256(e.fetch().serialize()).hexdigest()[:16]
+pl, ka = kern()
+_, kc = kern(card=True)
+t0 = time.perf_counter()
+for _ in range(N):
+    e.pairwise("and", a, b)
+    e.serialize()
+e.sync()
+st = (time.perf_counter() - t0) / N
+print(f"lib={lib} plan_ms={pl:.4f} and_kernel_ms={ka:.4f} card_kernel_ms={kc:.4f} "
+      f"step_ms={st * 1e3:.4f} sha={sha}", flush=True)

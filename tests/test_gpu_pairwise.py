@@ -405,8 +405,8 @@ def test_many_run_inputs_all_ops(gpu, nruns):
 
 @pytest.mark.parametrize("seed", range(4))
 def test_dense_key_range_direct_mode(gpu, seed):
-    """Dense key ranges run without the plan launch (the compute kernel resolves key key_lo + t
-    itself, csrc/pairwise.hip direct mode): every op and cardinality over a key range where each
+    """Dense key ranges take every key of the range as a task (record t = key key_lo + t,
+    k_plan_balanced + k_pair_cu in csrc/pairwise.hip): every op and cardinality over a key range where each
     operand holds most keys, some keys in one operand only (empty records for AND / ANDNOT), and
     keys absent from both, against the oracle (RB/RoaringBitmap.java:382-400, :449-471, :864-896,
     :1076-1113)."""
@@ -428,15 +428,14 @@ def test_dense_key_range_direct_mode(gpu, seed):
     e.release(bb)
 
 
-@pytest.mark.parametrize("balance", ["0", "1"])
 @pytest.mark.parametrize("seed", range(3))
-def test_dense_range_task_orders(gpu, seed, balance, monkeypatch):
-    """Dense key ranges in both task orders: key order (RBG_PW_BALANCE=0, the direct form) and binned by
-    estimated cost (k_plan_balanced: the task list out of key order, records still at key positions,
-    empty records / zero counts for keys without a task) claimed per CU (k_pair_cu).  Every op, the
-    key-range form and andCardinality over a range that covers every key, against the oracle."""
+def test_dense_range_task_orders(gpu, seed):
+    """Dense key ranges: tasks binned by estimated cost (k_plan_balanced: the task list out of key order,
+    records still at key positions, empty records / zero counts for keys without a task) claimed per CU
+    (k_pair_cu).  Every op, the key-range form and andCardinality over a range that covers every key,
+    against the oracle; and the op + serialization in one call (pairwise_serialized, over the whole key
+    space: the planned form at this size, the dense one is test_gpu_fullsize's), twice back to back."""
     from roaringbitmap_amd import Engine
-    monkeypatch.setenv("RBG_PW_BALANCE", balance)
     rng = np.random.default_rng(4100 + seed)
     n = int(rng.integers(300, 1500))
     keys = np.arange(n)
@@ -453,6 +452,10 @@ def test_dense_range_task_orders(gpu, seed, balance, monkeypatch):
         exp = O.pairwise(op, a, b)
         want = sum(1 for c in decode(exp) if lo <= c[0] < hi)
         assert rs["containers"] == want, (seed, op)
+    for op in OPS:
+        for _ in range(2):
+            e.pairwise_serialized(op, ba, bb)
+        assert e.fetch().serialize() == O.pairwise(op, a, b), (seed, op)
     e.and_cardinality(ba, bb)
     assert e.card() == O.pairwise_card("and", a, b)
     e.release(ba)
