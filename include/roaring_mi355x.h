@@ -301,6 +301,21 @@ int rbg_bsi_get_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const*
 int rbg_bsi_add(const uint8_t* ebm_a, size_t ebm_a_len, const uint8_t* const* slices_a, const size_t* lens_a, int na,
                 int32_t min_a, int32_t max_a, const uint8_t* ebm_b, size_t ebm_b_len, const uint8_t* const* slices_b,
                 const size_t* lens_b, int nb, rbg_buffer* outs, int32_t* out3);
+/* RoaringBitmapSliceIndex.setValues(List<Pair>) (RoaringBitmapSliceIndex.java:349-357: ensureCapacityInternal
+ * over the list's min and max, :315-326, then setValueInternal per pair in order, :304-313; setValue, :299-302,
+ * is n == 1; the buffer package's MutableBitSliceIndex.setValues, buffer/MutableBitSliceIndex.java:146-195, gives
+ * the same bytes) of n >= 1 (columns[i], values[i]) pairs on the index (ebm, slices[0..nbits-1]) with the fields
+ * min_value / max_value, on the device: outs[0] = ebM, outs[1 + i] = bA[i] afterwards as portable bytes (outs
+ * must have room for 33 buffers; 1 + out3[0] are written, each released with rbg_free), out3 = {bit count,
+ * minValue, maxValue} -- the fields as the reference leaves them, not the true extremes.  A column may be
+ * given many times: its last pair decides.  Only bits below the resulting bit count are kept (the reference's
+ * else-if lowers minValue alone when a list goes below it and above maxValue at once).  RBG_ERR_ILLEGAL_ARGUMENT:
+ * a negative value, n == 0 (the reference's max().getAsInt() throws), nbits above 32, a run container in a
+ * slice, a run container in ebM that is not full (a full one stays a run container: RunContainer.add returns
+ * this, RunContainer.java:248-263). */
+int rbg_bsi_set_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
+                       int nbits, int32_t min_value, int32_t max_value, const uint32_t* columns, const int32_t* values,
+                       size_t n, rbg_buffer* outs, int32_t* out3);
 /* BitSliceIndexBase.parallelIn(parallelism, foundSet, values, pool) of the buffer package's index
  * (buffer/BitSliceIndexBase.java:611-639): WHERE value IN (values).  The result is
  * {c in ebM and fixed : value(c) in values}, fixed = the foundSet, or ebM when found is NULL, as the
@@ -561,6 +576,24 @@ int rbg_ctx_bsi_from_columns_device(rbg_ctx* ctx, const void* columns_dev, const
  * under rbg_ctx_bsi_from_columns' byte budget (RBG_BSI_BUILD_WS).  Synchronous. */
 int rbg_ctx_bsi_add(rbg_ctx* ctx, int32_t batch_a, int nbits_a, int32_t batch_b, int nbits_b, int32_t min_a,
                     int32_t max_a, int32_t* out_batch, int32_t* out3);
+/* RoaringBitmapSliceIndex.setValues(List<Pair>) (RoaringBitmapSliceIndex.java:349-357, with
+ * ensureCapacityInternal :315-326 and setValueInternal :304-313; rbg_bsi_set_values above) of n >= 1 pairs on
+ * a resident index, the key-major unpacked batch [ebM, bA[0..nbits-1]] (no trailing foundSet) with the fields
+ * min_value / max_value, as a new batch [ebM', bA'[0..n'-1]]: field for field what rbg_ctx_load of the
+ * reference's bitmaps after the call gives, usable wherever a built or loaded index is.  out3 = {n', minValue,
+ * maxValue}.  The operand stays as it is.  columns (uint32, repeated at will: the last pair of a column
+ * decides) and values (int32) are host arrays.  RBG_ERR_ILLEGAL_ARGUMENT, with no batch made: a negative
+ * value, n == 0, a batch of another shape, nbits above 32, a run container in a slice or one in ebM that is
+ * not full.  The workspace (1 + n' bitmaps of 8 KiB and a last-pair table of 256 KiB per present key, the
+ * operand's keys and the columns') is walked in passes under rbg_ctx_bsi_from_columns' byte budget
+ * (RBG_BSI_BUILD_WS).  Synchronous. */
+int rbg_ctx_bsi_set_values(rbg_ctx* ctx, int32_t batch, int nbits, int32_t min_value, int32_t max_value,
+                           const uint32_t* columns, const int32_t* values, size_t n, int32_t* out_batch, int32_t* out3);
+/* The same from device memory; whatever produced the pairs must be ordered before the context stream, and
+ * they must not change until the call returns (every pass reads them). */
+int rbg_ctx_bsi_set_values_device(rbg_ctx* ctx, int32_t batch, int nbits, int32_t min_value, int32_t max_value,
+                                  const void* columns_dev, const void* values_dev, size_t n, int32_t* out_batch,
+                                  int32_t* out3);
 /* BitSliceIndexBase.parallelIn (buffer/BitSliceIndexBase.java:611-639; rbg_bsi_in above) over a resident
  * index, the key-major unpacked batch [ebM, bA[0..nbits-1], foundSet if has_found], as a new one-bitmap
  * batch: field for field what rbg_ctx_load of the reference's result gives, usable wherever a loaded bitmap

@@ -57,6 +57,7 @@ EXPORTED = [
     "rbg_bsi_from_columns", "rbg_bsi_get_values", "rbg_ctx_bsi_from_columns", "rbg_ctx_bsi_from_columns_device",
     "rbg_ctx_bsi_get_values", "rbg_ctx_bsi_get_values_device", "rbg_ctx_bsi_to_pairs", "rbg_ctx_bsi_to_pairs_device",
     "rbg_bsi_add", "rbg_ctx_bsi_add", "rbg_bsi_in", "rbg_ctx_bsi_in", "rbg_bsi_transpose", "rbg_ctx_bsi_transpose",
+    "rbg_bsi_set_values", "rbg_ctx_bsi_set_values", "rbg_ctx_bsi_set_values_device",
 ]
 
 _lib = None
@@ -109,6 +110,9 @@ def _declare(L):
     L.rbg_bsi_add.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, i32, i32,
                               u8p, sz, P(ctypes.c_char_p), P(sz), ci, vp, i32p]
     L.rbg_ctx_bsi_add.argtypes = [vp, i32, ci, i32, ci, i32, i32, i32p, i32p]
+    L.rbg_bsi_set_values.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, i32, i32, u32p, i32p, sz, vp, i32p]
+    L.rbg_ctx_bsi_set_values.argtypes = [vp, i32, ci, i32, i32, u32p, i32p, sz, i32p, i32p]
+    L.rbg_ctx_bsi_set_values_device.argtypes = [vp, i32, ci, i32, i32, vp, vp, sz, i32p, i32p]
     L.rbg_bsi_in.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, u8p, sz, i32p, sz, ci, buf]
     L.rbg_ctx_bsi_in.argtypes = [vp, i32, ci, ci, i32p, sz, ci, i32p]
     L.rbg_bsi_transpose.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, u8p, sz, ci, vp, i32p]

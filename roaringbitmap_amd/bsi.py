@@ -11,8 +11,9 @@ Construction (setValue) is host-side by default; from_columns(..., gpu=True) bui
 device (csrc/bsibuild.hip), and getValues / toPairList read values back in bulk (csrc/bsival.hip with
 gpu=True).  add(otherBsi) (BSI/:66-95) sums two indexes in one fused device pass (csrc/bsiadd.hip) when
 neither holds a run container, and replays the reference's and / xor chain with the pairwise device ops
-otherwise.  The buffer index's parallelIn (BBSI/:611-639), WHERE value IN (...), is one fused pass too
-(csrc/bsiin.hip), and its parallelTransposeWithCount (BBSI/:551-597), GROUP BY value / COUNT(*), one device
+otherwise.  setValue / setValues (BSI/:299-357) write pairs into an existing index, repeated columns included:
+numpy on the host by default, one device call (csrc/bsiset.hip) with gpu=True.  The buffer index's parallelIn
+(BBSI/:611-639), WHERE value IN (...), is one fused pass too (csrc/bsiin.hip), and its parallelTransposeWithCount (BBSI/:551-597), GROUP BY value / COUNT(*), one device
 call (csrc/bsitr.hip).
 """
 import ctypes
@@ -78,6 +79,74 @@ class RoaringBitmapSliceIndex:
         obj = cls(ebm, ba, mn, mx)
         obj.runOptimized = bool(run_optimize)
         return obj
+
+    def setValue(self, columnId, value):
+        """BSI/:299-302 setValue(columnId, value), in place: setValues of the one pair."""
+        self.setValues([columnId], [value])
+
+    def setValues(self, columns, values, gpu=False):
+        """BSI/:349-357 setValues(List<Pair>) as two arrays, in place: ensureCapacityInternal (:315-326) over the
+        pairs' min and max, then per pair in order bA[i].add / remove(column) by bit i of the value and
+        ebM.add(column) (:304-313) -- a column given many times keeps its last value, and minValue / maxValue
+        / bitCount() are the reference's fields (the else-if of :320-325 included), not the true extremes.  A
+        negative value or no pair raises IllegalArgumentException.  runOptimized stays as it was.
+        Host default, no device: numpy over toArray() of the slices and from_values, so every container has
+        the type its cardinality gives -- for a run-free index, or one whose only run containers are in an
+        ebM that the pairs leave unchanged; otherwise IllegalArgumentException (try gpu=True).
+        gpu=True: the one-shot device pass (rbg_bsi_set_values, csrc/bsiset.hip), which also takes an ebM
+        with full run containers and new columns; it refuses a run container in a slice and one in ebM that
+        is not full."""
+        c = np.asarray(columns, dtype=np.int64).reshape(-1)
+        v = np.asarray(values, dtype=np.int64).reshape(-1)
+        if c.size != v.size:
+            raise IllegalArgumentException("columns and values differ in length")
+        if v.size == 0:
+            raise IllegalArgumentException("setValues: no pair given")
+        if v.min() < 0 or v.max() >= 1 << 31:
+            raise IllegalArgumentException("Values should be non-negative and below 2^31")
+        if len(self.bA) > 32:
+            raise IllegalArgumentException("setValues: an index holds at most 32 slices")
+        c = np.ascontiguousarray(c.astype(np.uint32))
+        ebm_cls = type(self.ebM)
+        if gpu:
+            v = np.ascontiguousarray(v.astype(np.int32))
+            arr, lens = self._slices()
+            e = self.ebM.serialize()
+            outs = (_lib.rbg_buffer * 33)()
+            out3 = (ctypes.c_int32 * 3)()
+            check(lib().rbg_bsi_set_values(e, len(e), arr, lens, len(self.bA), self.minValue, self.maxValue,
+                                           c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                           v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size, outs, out3))
+            self.ebM = ebm_cls(take(outs[0]))
+            self.bA = [RoaringBitmap(take(outs[1 + k])) for k in range(int(out3[0]))]
+            self.minValue, self.maxValue = int(out3[1]), int(out3[2])
+            return
+        if any(b.container_stats()[2] > 0 for b in self.bA):
+            raise IllegalArgumentException("setValues: a slice holds a run container")
+        rev = c[::-1]
+        cols, first = np.unique(rev, return_index=True)  # the last pair of every column
+        win = v[::-1][first]
+        old = self.ebM.toArray()
+        ebm_same = bool(np.isin(cols, old).all())
+        if not ebm_same and self.ebM.container_stats()[2] > 0:
+            raise IllegalArgumentException("setValues: ebM holds a run container and the pairs add a column; "
+                                           "the host form cannot type it, try gpu=True")
+        bmin, bmax, depth = int(v.min()), int(v.max()), len(self.bA)
+        if old.size == 0:  # ensureCapacityInternal
+            self.minValue, self.maxValue = bmin, bmax
+            depth = max(depth, len(bin(bmax)) - 2)
+        elif self.minValue > bmin:
+            self.minValue = bmin
+        elif self.maxValue < bmax:
+            self.maxValue = bmax
+            depth = max(depth, len(bin(bmax)) - 2)
+        ba = []
+        for i in range(depth):
+            kept = np.setdiff1d(self.bA[i].toArray(), cols) if i < len(self.bA) else cols[:0]
+            ba.append(RoaringBitmap.from_values(np.concatenate([kept, cols[(win >> i) & 1 == 1]])))
+        self.bA = ba
+        if not ebm_same:
+            self.ebM = ebm_cls.from_values(np.union1d(old, cols))
 
     def merge(self, otherBsi):
         """BSI/:379-405 ("designed for distributed computing"; the two indexes hold disjoint

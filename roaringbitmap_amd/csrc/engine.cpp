@@ -1425,6 +1425,116 @@ static int ctx_bsi_add(Ctx* c, int32_t batch_a, int nbits_a, int32_t batch_b, in
   return RBG_OK;
 }
 
+// RoaringBitmapSliceIndex.setValues(List<Pair>) (BSI/:349-357; setValue, :299-313, is n == 1; the buffer
+// package's MutableBitSliceIndex.setValues, buffer/MutableBitSliceIndex.java:146-195) of n >= 1 pairs in device
+// memory (u32 columns, repeated at will; i32 values, none negative; the pair with the highest index decides a
+// column) on a resident index, the key-major batch [ebM, bA[0..nbits-1]] with the caller's min / max, as a new
+// batch [ebM', bA'[0..d'-1]]: what ctx_load of the reference's bitmaps after the call gives (bsiset.hip; the
+// operand untouched).  out3 = {d', minValue, maxValue} by ensureCapacityInternal (BSI/:315-326) over the
+// batch's own extremes -- its else-if included: a batch below min and above max lowers min alone, and the
+// high bits of its values are dropped.  Two read-backs: the key count with min / max (a negative value is
+// refused here), then the plan's totals with the run-container refusal (a slice may hold none, ebM only full
+// ones, which stay run containers).  The K x (1 + d') bitmaps are a BsibPlan whose fill expands the operand
+// and applies the pairs, with the last-pair table of 256 KiB as a key's extra bytes.  The pairs are read by
+// every pass: they must not change until the call returns.
+static int ctx_bsi_set_values(Ctx* c, int32_t batch, int nbits, int32_t min_v, int32_t max_v, const uint32_t* col_dev,
+                              const int32_t* val_dev, size_t n, int32_t* out_id, int32_t* out3) {
+  hipStream_t s = c->stream;
+  Batch* A;
+  CHK(get_batch(c, batch, &A));
+  if (nbits < 0 || nbits > 32) {
+    set_err("bsi_set_values: an index holds at most 32 slices");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (!A->key_major || A->packed || A->n_bm != (size_t)(1 + nbits)) {
+    set_err("bsi_set_values: batch must be key-major, unpacked and hold ebM and nbits slices");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (n == 0 || n > 0xFFFFFFFFull) {  // values.stream().max().getAsInt() throws on an empty list
+    set_err(n ? "bsi_set_values: more pairs than a 32-bit pair index holds" : "bsi_set_values: no pair given");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  const BsiAddSide sa{A->key_off.as<uint32_t>(), A->desc.as<CDesc>(), A->bm.as<uint32_t>(), A->payload.as<uint8_t>(),
+                      nbits};
+  const bool was_empty = A->h_bm_card.empty() || A->h_bm_card[0] == 0;
+  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
+  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
+  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] {min, max} as two i32, [2] refused
+  HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
+  HIPCHK(hipMemsetAsync(sc, 0, 64, s));
+  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxSeedI32, 8, hipMemcpyHostToDevice, s));
+  launch_bsia_keys(s, A->keys.as<uint16_t>(), A->n_ctr, nullptr, 0, c->flag.as<uint8_t>());
+  launch_bld_keys(s, col_dev, n, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
+  launch_bsib_minmax(s, val_dev, n, reinterpret_cast<int*>(sc + 1));
+  HIPCHK(hipGetLastError());
+  unsigned long long h[2] = {};
+  HIPCHK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  const size_t K = (size_t)h[0];
+  const int32_t mn = (int32_t)(uint32_t)h[1], mx = (int32_t)(uint32_t)(h[1] >> 32);
+  if (mn < 0) {
+    set_err("Values should be non-negative");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  dbg(s, "bsi_set_values: keys + min / max");
+  const int need = mx ? 32 - __builtin_clz((uint32_t)mx) : 1;  // Integer.toBinaryString(max).length()
+  int d = nbits;
+  if (was_empty) {  // ensureCapacityInternal
+    min_v = mn;
+    max_v = mx;
+    d = std::max(d, need);
+  } else if (min_v > mn) {
+    min_v = mn;
+  } else if (max_v < mx) {
+    max_v = mx;
+    d = std::max(d, need);
+  }
+  const int m = 1 + d;
+  constexpr size_t kTab = 4 * 65536;  // a key's last-pair table: after the cells of a pass
+  BsibPlan plan;
+  CHK(plan.begin(c, K, m, kTab, false, true));
+  uint32_t* tab = reinterpret_cast<uint32_t*>(plan.ws.as<uint8_t>() + 8192 * (size_t)m * plan.P);
+  auto fill = [&](size_t k_lo, size_t k_hi, bool) -> int {  // every cell of the pass is written: no memset
+    launch_bsis_expand(s, sa, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, plan.ws.as<uint8_t>(),
+                       c->bsia_run.as<uint8_t>(), reinterpret_cast<uint32_t*>(sc + 2));
+    HIPCHK(hipMemsetAsync(tab, 0, kTab * (k_hi - k_lo), s));
+    launch_bsis_last(s, col_dev, n, c->bsib_pkoff.as<uint32_t>(), (uint32_t)k_lo, (uint32_t)k_hi, tab);
+    launch_bsis_apply(s, col_dev, val_dev, n, c->bsib_pkoff.as<uint32_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, tab,
+                      plan.ws.as<uint32_t>());
+    return RBG_OK;
+  };
+  uint32_t bad = 0;
+  auto read_bad = [&]() -> int {
+    HIPCHK(hipMemcpyAsync(&bad, sc + 2, 4, hipMemcpyDeviceToHost, s));
+    return RBG_OK;
+  };
+  CHK(plan.sweep(true, fill, read_bad));
+  dbg(s, "bsi_set_values: expand + apply + plan");
+  if (bad) {
+    set_err("bsi_set_values: a slice holds a run container, or ebM one that is not full");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  CHK(plan.emit(m, fill, "bsi_set_values: write", out_id));
+  out3[0] = d;
+  out3[1] = min_v;
+  out3[2] = max_v;
+  return RBG_OK;
+}
+
+// the same from host memory: the pairs go to the device through the context's pinned buffer
+static int ctx_bsi_set_values_host(Ctx* c, int32_t batch, int nbits, int32_t min_v, int32_t max_v, const uint32_t* col,
+                                   const int32_t* val, size_t n, int32_t* out_id, int32_t* out3) {
+  DevBuf dc, dv;
+  CHK(pool_take(c, dc, 4 * n + 16));
+  CHK(pool_take(c, dv, 4 * n + 16));
+  CHK(upload_words(c, dc.p, col, n));
+  CHK(upload_words(c, dv.p, val, n));
+  const int st = ctx_bsi_set_values(c, batch, nbits, min_v, max_v, dc.as<uint32_t>(), dv.as<int32_t>(), n, out_id, out3);
+  pool_put(c, dc);
+  pool_put(c, dv);
+  return st;
+}
+
 // A batch as the operand of the BSI read-outs (bsival.hip): key-major [ebM, nbits slices, foundSet?]
 static int bsi_val_operand(Ctx* c, int32_t id, int nbits, int has_found, Batch** B, BsiValArgs* a) {
   CHK(get_batch(c, id, B));
@@ -4630,6 +4740,41 @@ int rbg_bsi_add(const uint8_t* ebm_a, size_t ebm_a_len, const uint8_t* const* sl
   CHK(bsi_load(os, ebm_a, ebm_a_len, slices_a, lens_a, (size_t)na, nullptr, 0, &ia));
   CHK(bsi_load(os, ebm_b, ebm_b_len, slices_b, lens_b, (size_t)nb, nullptr, 0, &ib));
   CHK(ctx_bsi_add(c, ia, na, ib, nb, min_a, max_a, &id, out3));
+  os.adopt(id);
+  return ctx_batch_fetch_range(c, id, 0, 1 + (size_t)out3[0], outs);
+}
+
+/* ---- RoaringBitmapSliceIndex.setValues (BSI/:349-357; bsiset.hip) ---- */
+
+int rbg_ctx_bsi_set_values(rbg_ctx* ctx, int32_t batch, int nbits, int32_t min_value, int32_t max_value,
+                           const uint32_t* columns, const int32_t* values, size_t n, int32_t* out_batch, int32_t* out3) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!out_batch || !out3 || (n && (!columns || !values))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_set_values_host(c, batch, nbits, min_value, max_value, columns, values, n, out_batch, out3);
+}
+
+int rbg_ctx_bsi_set_values_device(rbg_ctx* ctx, int32_t batch, int nbits, int32_t min_value, int32_t max_value,
+                                  const void* columns_dev, const void* values_dev, size_t n, int32_t* out_batch,
+                                  int32_t* out3) {
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!out_batch || !out3 || (n && (!columns_dev || !values_dev))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_bsi_set_values(c, batch, nbits, min_value, max_value, reinterpret_cast<const uint32_t*>(columns_dev),
+                            reinterpret_cast<const int32_t*>(values_dev), n, out_batch, out3);
+}
+
+int rbg_bsi_set_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
+                       int nbits, int32_t min_value, int32_t max_value, const uint32_t* columns, const int32_t* values,
+                       size_t n, rbg_buffer* outs, int32_t* out3) {
+  if (!outs || !out3 || nbits < 0 || nbits > 32 || (n && (!columns || !values))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  if (!ebm || (nbits && (!slices || !slice_lens))) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t ia, id;
+  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, (size_t)nbits, nullptr, 0, &ia));
+  CHK(ctx_bsi_set_values_host(c, ia, nbits, min_value, max_value, columns, values, n, &id, out3));
   os.adopt(id);
   return ctx_batch_fetch_range(c, id, 0, 1 + (size_t)out3[0], outs);
 }

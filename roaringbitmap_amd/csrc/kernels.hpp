@@ -548,6 +548,22 @@ void launch_bsi_add(hipStream_t s, BsiAddSide a, BsiAddSide b, const uint16_t* p
 // unsigned, set to {~0u, 0} by the caller
 void launch_bsia_minmax(hipStream_t s, const uint8_t* ws, uint32_t n_keys, int m, uint32_t* mm);
 
+// bsiset.hip: n (column, value) pairs, in order, written into a key-major batch [ebM, bA[0..a.n-1]]
+// (RoaringBitmapSliceIndex.setValues, BSI/:349-357) in the workspace layout of the build above, m = 1 + d' cells
+// per present key (the operand's keys and the columns'), d' >= a.n the depth after ensureCapacityInternal.
+// One pass over the key indices [k_lo, k_hi): the operand's containers into the cells (every cell written) and
+// ebm_run[k_lo..k_hi) = 1 where ebM's container is a full run container; *bad |= 1 for any other run container
+void launch_bsis_expand(hipStream_t s, BsiAddSide a, const uint16_t* pkeys, uint32_t k_lo, uint32_t k_hi, int m,
+                        uint8_t* ws, uint8_t* ebm_run, uint32_t* bad);
+// tab[(key index - k_lo) * 65536 + (column & 0xFFFF)] = the highest pair index + 1 of the column; tab zeroed by
+// the caller, n < 2^32
+void launch_bsis_last(hipStream_t s, const uint32_t* col, uint64_t n, const uint32_t* pkey_off, uint32_t k_lo,
+                      uint32_t k_hi, uint32_t* tab);
+// the pair that holds its column's tab entry sets the column in cell 0 and sets or clears it in cells 1..m-1 by
+// the bits of its value; ws: the pass's cells, below 2^31 words
+void launch_bsis_apply(hipStream_t s, const uint32_t* col, const int32_t* val, uint64_t n, const uint32_t* pkey_off,
+                       uint32_t k_lo, uint32_t k_hi, int m, const uint32_t* tab, uint32_t* ws);
+
 // bsival.hip: values out of a key-major batch [ebM, bA[0..nbits-1], foundSet?]
 struct BsiValArgs {
   const uint32_t* key_off;  // the batch's key CSR (65,537 entries)

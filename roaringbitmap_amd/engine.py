@@ -455,6 +455,52 @@ class Engine:
                                     ctypes.byref(out), out3))
         return out.value, int(out3[0]), int(out3[1]), int(out3[2])
 
+    def bsi_set_values(self, batch, nbits, columns, values, min_value=0, max_value=0):
+        """RoaringBitmapSliceIndex.setValues(List<Pair>) (BSI/:349-357; setValue, :299-313, with one pair) on a
+        resident index, the key-major batch [ebM, bA[0..nbits-1]] with the fields min_value / max_value, on the
+        device (rbg_ctx_bsi_set_values) -> (batch, nbits, minValue, maxValue): a new batch, the one load() of
+        the reference's bitmaps after the call gives, as bsi / bsi_buffer / bsi_get_values / bsi_to_pairs /
+        bsi_add take it.  The operand stays.  The pairs apply in order: a column given many times keeps its last
+        value.  nbits / minValue / maxValue follow ensureCapacityInternal (BSI/:315-326): they are the
+        reference's fields, not the true extremes, and only bits below the new nbits are kept.  A negative
+        value, no pair at all, a batch of another shape, a run container in a slice or one in ebM that is not
+        full: IllegalArgumentException, no batch made.  numpy arrays or sequences are uploaded; torch tensors
+        on this engine's GPU are read in place (rbg_ctx_bsi_set_values_device), as in bsi_from_columns.
+        Synchronous either way."""
+        out = ctypes.c_int32()
+        out3 = (ctypes.c_int32 * 3)()
+        if type(columns).__module__.split(".")[0] == "torch":
+            import torch
+            if type(values).__module__.split(".")[0] != "torch":
+                raise ValueError("bsi_set_values: columns and values must both be tensors or both arrays")
+            if columns.numel() != values.numel():
+                raise _lib.IllegalArgumentException("columns and values differ in length")
+            if values.dtype == torch.int64 and values.numel() and bool(((values < 0) | (values >= 1 << 31)).any()):
+                raise _lib.IllegalArgumentException("Values should be non-negative and below 2^31")
+            c = self._words("bsi_set_values", columns)
+            v = self._words("bsi_set_values", values)
+            done = self._handshake(columns.device)
+            n = c.numel()
+            check(lib().rbg_ctx_bsi_set_values_device(
+                self._ctx, int(batch), int(nbits), int(min_value), int(max_value),
+                ctypes.c_void_p(c.data_ptr()) if n else None, ctypes.c_void_p(v.data_ptr()) if n else None, n,
+                ctypes.byref(out), out3))
+            done()
+            return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+        c = np.asarray(columns, dtype=np.int64).reshape(-1)
+        v = np.asarray(values, dtype=np.int64).reshape(-1)
+        if c.size != v.size:
+            raise _lib.IllegalArgumentException("columns and values differ in length")
+        if v.size and (v.min() < 0 or v.max() >= 1 << 31):
+            raise _lib.IllegalArgumentException("Values should be non-negative and below 2^31")
+        c = np.ascontiguousarray(c.astype(np.uint32))
+        v = np.ascontiguousarray(v.astype(np.int32))
+        check(lib().rbg_ctx_bsi_set_values(self._ctx, int(batch), int(nbits), int(min_value), int(max_value),
+                                           c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                           v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size,
+                                           ctypes.byref(out), out3))
+        return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+
     def bsi_in(self, batch, nbits, values, parallelism=1, has_found=False) -> int:
         """BitSliceIndexBase.parallelIn (BBSI/:611-639), WHERE value IN (values), over a resident index
         [ebM, bA[0..nbits-1], foundSet?] in one fused device pass (rbg_ctx_bsi_in) -> batch id of a new
