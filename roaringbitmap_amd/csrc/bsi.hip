@@ -842,7 +842,7 @@ __global__ __launch_bounds__(256) void k_bsi_defer(const Task* __restrict__ task
 // follows the poll order of its container-pointer queue (key, then larger cardinality first,
 // ties in heap order, which depends on every earlier key).  With three orInputs or more,
 // k_bsi_owen_pre first records every orInput's type per key and the host replays the queue
-// (engine.cpp: owen_order); the chain of a key then rebuilds each orInput's bits in that
+// (engine_bsi.cpp: owen_order); the chain of a key then rebuilds each orInput's bits in that
 // order.  With two or fewer the order does not matter (lazyOR is symmetric) and the
 // orInputs are chained as the spine makes them.
 

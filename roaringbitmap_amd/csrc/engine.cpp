@@ -1,7 +1,8 @@
 // Host side of the MI355X Roaring engine: device contexts, batch upload
 // (staged H2D of the serialized bytes -> device decode into the slotted arena,
 // decode.hip), op pipelines and
-// the exported C ABI of include/roaring_mi355x.h.
+// the exported C ABI of include/roaring_mi355x.h.  The bit-sliced-index pipelines and their entry points
+// are engine_bsi.cpp; engine.hpp holds what the two units share.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -20,38 +21,13 @@
 
 #include <sys/mman.h>
 
-#include "../../include/roaring_mi355x.h"
+#include "engine.hpp"
 #include "format.hpp"
-#include "kernels.hpp"
 
 namespace rbg {
 
 static thread_local std::string g_err;
-static void set_err(const std::string& s) { g_err = s; }
-
-#define HIPCHK(x)                                                            \
-  do {                                                                       \
-    hipError_t e_ = (x);                                                     \
-    if (e_ != hipSuccess) {                                                  \
-      set_err(std::string(#x) + " failed: " + hipGetErrorString(e_));        \
-      return e_ == hipErrorOutOfMemory ? RBG_ERR_OUT_OF_MEMORY : RBG_ERR_DEVICE; \
-    }                                                                        \
-  } while (0)
-
-#define CHK(x)              \
-  do {                      \
-    int st_ = (x);          \
-    if (st_ != RBG_OK) return st_; \
-  } while (0)
-
-constexpr size_t kSlack = 256;  // every device buffer carries read slack (group_copy)
-constexpr int kMaxKeys = 65536;
-constexpr size_t kLbHeader = 256;  // look-back state: error @64, result card @96
-// The largest serialized container a kernel stages in its scratch slot (a bitmap, 8192 B, or a run
-// container of 2048 runs; kSlotBytes, device.hpp, is this rounded up).  Every op's payload bound counts
-// on it: each result container is staged (<= kStagedMax B) or a clone of one input container.
-constexpr size_t kStagedMax = 8194;
-// tile statuses (kMaxTiles, device.hpp) follow the 65536 task statuses, tile cardinalities them
+void set_err(const std::string& s) { g_err = s; }
 
 // RBG_DEBUG_SYNC=1: synchronise and report after every pipeline stage (debugging aid)
 static bool debug_sync() {
@@ -62,7 +38,7 @@ static bool debug_sync() {
   }
   return v == 1;
 }
-static void dbg(hipStream_t s, const char* what) {
+void dbg(hipStream_t s, const char* what) {
   if (!debug_sync()) return;
   static auto last = std::chrono::steady_clock::now();
   hipError_t e = hipStreamSynchronize(s);
@@ -73,165 +49,10 @@ static void dbg(hipStream_t s, const char* what) {
   std::fflush(stderr);
 }  // look-back state: ticket @0, error word @64, statuses @256
 
-struct DevBuf {
-  void* p = nullptr;
-  size_t cap = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  DevBuf(DevBuf&& o) noexcept : p(o.p), cap(o.cap) {
-    o.p = nullptr;
-    o.cap = 0;
-  }
-  DevBuf& operator=(DevBuf&& o) noexcept {
-    if (this != &o) {
-      if (p) (void)hipFree(p);
-      p = o.p;
-      cap = o.cap;
-      o.p = nullptr;
-      o.cap = 0;
-    }
-    return *this;
-  }
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  int ensure(size_t bytes);  // defined after Ctx: an out-of-memory allocation empties the contexts' pools
-  template <class T>
-  T* as() const {
-    return reinterpret_cast<T*>(p);
-  }
-};
-
 // runOptimize's device statistics (Batch::ro_stats): from byte 64 the k_runopt workgroups' partial
 // counts (4 u64 each), from ro_flags_off(groups) the per-bitmap run flags, computed only when the host
 // asks (ensure_stats).
 static size_t ro_flags_off(size_t groups) { return (64 + 32 * groups + 255) & ~(size_t)255; }
-struct Batch {
-  bool live = false;
-  bool key_major = false;  // containers sorted by (key, input); else by (input, key)
-  bool gapped = false;     // slots not back to back (runOptimize result: a hole after a shrunk container)
-  bool packed = false;     // array payloads packed at 2 B granularity (C3 uniform synthetic
-                           // batches): wide ops and fetches only
-  size_t n_bm = 0, n_ctr = 0;
-  DevBuf keys, desc, bm, key_off, bm_off, payload;
-  size_t payload_bytes = 0;
-  std::vector<uint32_t> h_bm_off;   // bitmap-major container ranges (n_bm + 1), or counts prefix
-  std::vector<uint32_t> h_bm_nctr;  // containers per input bitmap
-  std::vector<int64_t> h_bm_card;   // long cardinality per input bitmap
-  int64_t n_kind[3] = {0, 0, 0};
-  int64_t ser_bytes = 0;
-  int64_t long_card = 0;
-  size_t max_ser = 0;  // Σ serialized payload of containers larger than kStagedMax (long run inputs)
-  int32_t bsi_min = 0, bsi_max = 0;  // synthetic C5: min / max of the indexed values
-  bool pair_cap_known = false;        // batched andCardinality: item capacity computed
-  // made by runOptimize: kinds / payload bytes / run flags still in ro_stats (device: 5 u64 totals,
-  // plan partial counts, run flags: ro_flags_off) until ensure_stats derives them
-  bool stats_pending = false;
-  DevBuf ro_stats;
-  size_t ro_groups = 0;  // plan workgroups whose partial counts ro_stats holds
-  std::vector<uint8_t> h_has_run;
-  // BSI compare over this batch (ebM = input 0): the task list (keys of ebM) and the per-key input
-  // table, planned by the first query and kept (ctx_bsi)
-  bool bsi_cached = false;
-  DevBuf bsi_tasks, bsi_nt, bsi_table;
-  // rank directory of a single-bitmap key-major batch (rankdir.hip): built on the device by the first
-  // point query and kept (ctx_rankdir)
-  bool rd_ready = false;
-  DevBuf rd_cum, rd_off, rd_aux;
-  uint64_t pair_items_cap = 0;
-  // host copy of the container table for fetches (batches are immutable once loaded):
-  // h_desc in container order, h_pos[h_pos_off[i] .. h_pos_off[i+1]) = bitmap i's containers
-  bool h_index = false;
-  bool h_chain_identity = false;  // horizontal_order found the batch order to be the chain order
-  std::vector<CDesc> h_desc;
-  std::vector<uint32_t> h_pos, h_pos_off;
-};
-
-struct DecBufs {  // scratch of the device decode (decode.hip), reused across loads
-  DevBuf meta, head, nctr, base, nch, chbase, chmap, flag, err, card, cons, part, q, qkey, sort, skey, iota, perm,
-      size, cpart;
-};
-
-struct Ctx {
-  int device = 0;
-  DecBufs dec;
-  DevBuf wg_epoch;         // pairwise plan: per-workgroup task counts tagged with the op epoch
-  uint32_t epoch = 0;
-  DevBuf pc_cnt, pc_part, pc_items, pc_large;  // batched andCardinality scratch
-  hipStream_t stream = nullptr;
-  std::vector<std::unique_ptr<Batch>> batches;
-  uint64_t* zlb = nullptr;    // look-back state the next plan kernel zeroes (null: none)
-  uint64_t* ztile = nullptr;
-  DevBuf bsi_defer, bsi_cnts, bsi_kin, bsi_table;  // scratch of the register-resident BSI kernels
-  DevBuf bsi_claims;  // k_bsi_reg's unit-pool counters (zero between queries)
-  DevBuf bsi_sums;  // kBsiMaxInputs + 1 u64: per-slice |bA[x] & found|, found count
-  void* bsi_sums_dst = nullptr;  // rbg_ctx_bsi_sums_target: (sum, count) also written here by every sum
-  // buffer-package BSI: owenGreatEqual's orInput types / task keys / chain order, and the arena of
-  // result run containers above 2047 runs (BigRuns; big_ctl = {bytes used, overflow})
-  DevBuf owen_tb, owen_keys, owen_ord, big, big_ctl;
-  DevBuf ones;  // 8192 bytes of 0xFF: the full bitmap container of an in-place OR (k_ior_fix)
-  DevBuf ornot_plan;  // OrNotPlan of the last orNot
-  DevBuf rd_part;         // scan scratch of the rank directory build
-  DevBuf pt_q, pt_out;    // point queries from host memory: the queries and results on the device
-  DevBuf bld_info, bld_size, bld_part;  // construction from values (build.hip): the plan's table, slot sizes, scan
-  DevBuf tv_out;                        // expansion to host memory: one window of values on the device
-  // a BSI batch from (column, value) pairs (bsibuild.hip): the present keys and their CSR, the plan's cell
-  // table, the cells' size words (scanned in place) and scan scratch, the per-input totals
-  DevBuf bsib_pkeys, bsib_pkoff, bsib_info, bsib_size, bsib_part, bsib_per;
-  DevBuf bsia_run;  // the sum of two indexes (bsiadd.hip): per present key, ebM' is a full run container
-  // parallelTransposeWithCount (bsitr.hip): the candidate input keys and their CSR, the result-key flags, per
-  // result key its distinct values and whether it is full
-  DevBuf bsit_ckeys, bsit_ckoff, bsit_rflag, bsit_kcard, bsit_full;
-  DevBuf bsiv_cards, bsiv_part;  // toPairList (bsival.hip): ebM's cardinality per key (scanned in place)
-  DevBuf gather_items, gather_out;  // batch fetch: slot gather list and download buffer
-  DevBuf order;                     // horizontal_*: chain order of every key segment
-  DevBuf ro_info, ro_size, ro_part;  // range selection scratch (kept: no allocation per call)
-  DevBuf rs_card, rs_keep, rs_bm;
-  // device buffers of released batches kept for the next batch of a similar size (hipMalloc /
-  // hipFree of a 0.36 GB payload cost more than runOptimize's kernels); bounded by kPoolMax
-  std::vector<DevBuf> pool;
-  size_t pool_bytes = 0;
-  std::mutex pool_mu;  // the pool may be emptied by another thread's out-of-memory allocation
-  ResultInfo last_ri{};   // the pending result's facts, once ctx_info has read them (fetch_shard_device)
-  bool ri_valid = false;
-  int bsi_nbits = 0;
-  DevBuf by_key, flag, tasks, ntasks, wg_count, lb, recs, kind_by_out, info, task_card, result, cards, skip, raw,
-      scalar, scratch;
-  size_t result_cap = 0;
-  OutCtx pending{};         // output state of the last materialising op
-  std::vector<int32_t> pending_src;  // batches the pending result's pass-through records point into
-  size_t pending_ub = 0;
-  bool serialized = false;  // pending result already in the portable layout
-  bool place_pending = false;  // the op's k_place not launched yet (serialization then places too)
-  // the pending result's records were summed per tile by its compute kernel (OutCtx::tile_agg): its
-  // serialization places and copies in one launch (k_serialize_agg) instead of k_place + k_serialize
-  bool agg_ok = false;
-  size_t n_cards = 0;
-  int last = 0;  // 0 none, 1 serialized result, 2 cardinality, 3 batch cardinalities
-  void* pinned = nullptr;
-  size_t pinned_cap = 0;
-  // HIP-event phase timing: 4 events per op (start, after plan+compact, after
-  // compute, after finalize+emit); read back without per-op host syncs.
-  std::vector<hipEvent_t> prof_ev;
-  size_t prof_cap = 0, prof_n = 0;
-  DevBuf rd_ctr;  // while profiling: bytes the early-exit workShyAnd kernels read (rbg_ctx_profile_bytes)
-  void prof_free() {
-    for (hipEvent_t e : prof_ev) (void)hipEventDestroy(e);
-    prof_ev.clear();
-    prof_cap = prof_n = 0;
-  }
-  bool prof_compute_only = false;  // events around the compute launch only (rbg_ctx_profile_compute)
-  void mark(int phase) {
-    if (prof_compute_only && (phase == 0 || phase == 3)) {
-      if (phase == 3 && prof_n < prof_cap) prof_n++;  // the op's record is complete
-      return;
-    }
-    if (prof_n < prof_cap) (void)hipEventRecord(prof_ev[4 * prof_n + phase], stream);
-    if (phase == 3 && prof_n < prof_cap) prof_n++;
-  }
-  ~Ctx();
-};
 
 // every live context, for release_pools_on
 static std::mutex g_ctx_mu;
@@ -349,7 +170,7 @@ static int ctx_init(Ctx* c, int device) {
   return RBG_OK;
 }
 
-static int pinned_ensure(Ctx* c, size_t bytes) {
+int pinned_ensure(Ctx* c, size_t bytes) {
   if (c->pinned_cap >= bytes) return RBG_OK;
   if (c->pinned) (void)hipHostFree(c->pinned);
   c->pinned = nullptr;
@@ -410,12 +231,12 @@ static int ensure_stats(Ctx* c, Batch* b) {
   return RBG_OK;
 }
 
-static int get_batch(Ctx* c, int32_t id, Batch** out) {
+int get_batch(Ctx* c, int32_t id, Batch** out) {
   CHK(find_batch(c, id, out));
   return ensure_stats(c, *out);
 }
 
-static int32_t new_batch(Ctx* c) {
+int32_t new_batch(Ctx* c) {
   for (size_t i = 0; i < c->batches.size(); i++)
     if (!c->batches[i]) {
       c->batches[i].reset(new Batch());
@@ -429,7 +250,7 @@ constexpr size_t kPoolMax = 2ull << 30;    // bytes of released buffers a contex
 constexpr size_t kPoolMaxBuf = 1ull << 30;  // larger buffers are freed at once
 
 // a released batch buffer into the context's pool (reused only by later work on the same stream)
-static void pool_put(Ctx* c, DevBuf& b) {
+void pool_put(Ctx* c, DevBuf& b) {
   if (!b.p) return;
   std::lock_guard<std::mutex> g(c->pool_mu);
   if (b.cap > kPoolMaxBuf) {
@@ -446,7 +267,7 @@ static void pool_put(Ctx* c, DevBuf& b) {
 
 // dst sized for `bytes`: the smallest pooled buffer that holds it (at most twice as large),
 // else a fresh allocation
-static int pool_take(Ctx* c, DevBuf& dst, size_t bytes) {
+int pool_take(Ctx* c, DevBuf& dst, size_t bytes) {
   if (dst.p && dst.cap >= bytes) return RBG_OK;
   std::unique_lock<std::mutex> lk(c->pool_mu);
   size_t best = c->pool.size();
@@ -464,16 +285,6 @@ static int pool_take(Ctx* c, DevBuf& dst, size_t bytes) {
   c->pool.erase(c->pool.begin() + (std::ptrdiff_t)best);
   return RBG_OK;
 }
-
-// drops the listed batches on scope exit
-struct BatchGuard {
-  Ctx* c;
-  std::vector<int32_t> ids;
-  ~BatchGuard() {
-    for (int32_t id : ids)
-      if (id >= 0 && (size_t)id < c->batches.size()) c->batches[id].reset();
-  }
-};
 
 // ---------------------------------------------------------------------------
 // upload: the host concatenates the serialized inputs (16 B aligned) and copies
@@ -734,8 +545,8 @@ static int ctx_decode_raw(Ctx* c, const uint64_t* off, const size_t* lens, size_
   return RBG_OK;
 }
 
-static int ctx_load_impl(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, bool key_major,
-                         int32_t* out_id, bool pack_arrays = false) {
+int ctx_load_impl(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, bool key_major, int32_t* out_id,
+                  bool pack_arrays) {
   std::vector<uint64_t> off;
   CHK(ctx_upload_raw(c, bufs, lens, n, &off));
   return ctx_decode_raw(c, off.data(), lens, n, key_major, out_id, pack_arrays);
@@ -749,7 +560,7 @@ static int ctx_load(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size
 
 // n serialized bitmaps in ONE upload, each decoded into a batch of its own (the operands of a
 // pairwise op: one staging pass and DMA for both); ids[i] = batch of bitmap i
-static int ctx_load_separate(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* ids) {
+int ctx_load_separate(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* ids) {
   std::vector<uint64_t> off;
   CHK(ctx_upload_raw(c, bufs, lens, n, &off));
   BatchGuard g{c, {}};
@@ -771,7 +582,7 @@ static uint64_t header_reserve(size_t max_tasks) {
   return round16(8 + (max_tasks + 7) / 8 + 8 * (uint64_t)max_tasks + 16);
 }
 
-static int grid_for(size_t tasks, size_t cap = 4096) {
+int grid_for(size_t tasks, size_t cap) {
   size_t g = std::min(tasks, cap);
   return (int)std::max<size_t>(g, 1);
 }
@@ -779,7 +590,7 @@ static int grid_for(size_t tasks, size_t cap = 4096) {
 // Output state of a materialising op: per-task records + scratch slots (the
 // device-resident result), and the portable-format buffer the serialization
 // writes into on fetch.  Card-only ops need no output state.
-static int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* oc, bool card_only) {
+int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* oc, bool card_only) {
   uint8_t* lb = c->lb.as<uint8_t>();
   *oc = OutCtx{};
   oc->err = reinterpret_cast<uint32_t*>(lb + 64);
@@ -817,7 +628,7 @@ static int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* 
 // Placement of a materialising op's result (k_place) is deferred until something needs it
 // (serialization, result statistics, a key-shard fetch): an op whose caller only wants the
 // result to exist on the device (a BSI query followed by its sum) does not pay for it.
-static void defer_place(Ctx* c) {
+void defer_place(Ctx* c) {
   c->place_pending = true;
   c->last = 1;
 }
@@ -884,38 +695,12 @@ static void op_begin(Ctx* c, std::initializer_list<int32_t> src) {
   c->mark(0);
   c->mark(1);
 }
-static int op_end(Ctx* c) {
+int op_end(Ctx* c) {
   c->mark(2);
   defer_place(c);
   c->mark(3);
   HIPCHK(hipGetLastError());
   return RBG_OK;
-}
-
-// An op whose kernel may keep run containers above 2047 runs reserves them in the context's big-run
-// arena (Ctx::big; big_ctl = {bytes reserved, overflow flag}).  pass(BigRuns) enqueues one complete
-// attempt, its prepare_output included (the payload bound counts big.cap).  The arena is checked after
-// the pass (a synchronisation); a pass that overflowed counted every reservation, so the arena is grown
-// to that size and the pass run once more.  use_arena false: the pass runs once with no arena, nothing
-// is read back.
-template <class Pass>
-static int with_big_runs(Ctx* c, bool use_arena, const char* what, Pass&& pass) {
-  if (!use_arena) return pass(BigRuns{nullptr, nullptr, 0});
-  if (!c->big_ctl.p) CHK(c->big_ctl.ensure(16));
-  if (!c->big.p) CHK(c->big.ensure(16ull << 20));
-  for (int attempt = 0;; attempt++) {
-    HIPCHK(hipMemsetAsync(c->big_ctl.p, 0, 16, c->stream));
-    CHK(pass(BigRuns{c->big.as<uint8_t>(), c->big_ctl.as<unsigned long long>(), c->big.cap}));
-    unsigned long long used[2] = {0, 0};
-    HIPCHK(hipMemcpyAsync(used, c->big_ctl.p, 16, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (!used[1]) return RBG_OK;
-    if (attempt) {
-      set_err(std::string(what) + ": the run-container arena overflowed twice");
-      return RBG_ERR_DEVICE;
-    }
-    CHK(c->big.ensure(used[0] + (used[0] >> 3) + 4096));
-  }
 }
 
 // The rank directory of a batch resolve() accepts (rankdir.hip): the container prefix cum, and per bitmap
@@ -1104,10 +889,10 @@ static int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt
 }
 
 // one empty bitmap as a new batch: the result of a query that no column can satisfy
-static int ctx_empty_bitmap(Ctx* c, int32_t* out_id) { return ctx_from_values(c, nullptr, 0, false, out_id); }
+int ctx_empty_bitmap(Ctx* c, int32_t* out_id) { return ctx_from_values(c, nullptr, 0, false, out_id); }
 
 // n 32-bit words from host memory into dst (device), through the context's pinned buffer, a chunk at a time
-static int upload_words(Ctx* c, void* dst, const void* src, size_t n) {
+int upload_words(Ctx* c, void* dst, const void* src, size_t n) {
   constexpr size_t kChunk = 16u << 20;  // words per staged copy (64 MiB)
   if (!n) return RBG_OK;
   CHK(pinned_ensure(c, 4 * std::min(n, kChunk)));
@@ -1129,863 +914,6 @@ static int ctx_from_values_host(Ctx* c, const uint32_t* v, size_t n, bool run_op
   const int st = ctx_from_values(c, in.as<uint32_t>(), n, run_opt, out_id);
   pool_put(c, in);
   return st;
-}
-
-// the seeds of a {min, max} pair that kernels lower and raise with atomics: signed values, unsigned values
-static const int32_t kMinMaxSeedI32[2] = {INT32_MAX, INT32_MIN};
-static const uint32_t kMinMaxSeedU32[2] = {0xFFFFFFFFu, 0u};
-
-// Workspace bytes of one pass of the BSI build (bsibuild.hip).  RBG_BSI_BUILD_WS=<bytes> overrides the
-// default, read at every call (tests force several passes at small shapes); a pass always holds at least
-// one key's m bitmaps and stays below 2^31 words.
-constexpr size_t kBsibBudget = 1ull << 30;  // a released workspace of this size still goes to the pool (kPoolMaxBuf)
-static size_t bsib_budget() {
-  const char* e = std::getenv("RBG_BSI_BUILD_WS");
-  const unsigned long long v = e ? std::strtoull(e, nullptr, 10) : 0;
-  return (size_t)std::min<unsigned long long>(v ? v : kBsibBudget, 4ull << 30);
-}
-
-// A planned workspace (bsibuild.hip's cells): K present keys x m cells of 8 KiB, walked P whole keys per pass
-// under bsib_budget().  begin sizes the scratch and takes the workspace, sweep fills and plans every pass and
-// scans the sizes, emit writes the batch.  One pass: fill, plan, scan, write from the same workspace.  Several:
-// the sweep plans every pass (sizes alone), the scan places every container, and emit fills each pass again
-// before it writes -- the payload is allocated once at its exact size.
-// fill(k_lo, k_hi, first) enqueues whatever leaves the cells of keys [k_lo, k_hi) at the front of ws; first: the
-// call comes from the first sweep (a caller's once-only statistics), not from a later sweep or from emit.
-struct BsibPlan {
-  Ctx* c;
-  size_t K = 0;
-  int m = 0;
-  size_t key_bytes = 0;  // of ws per key: the m cells, then whatever the caller keeps after a pass's cells
-  size_t P = 0;          // keys per pass
-  DevBuf ws;             // back to the pool at the end of emit (freed on an error)
-  std::vector<unsigned long long> hp;  // the plan's per-input totals: 4 per cell column, then the three kind counts
-  uint64_t total = 0;                  // the scan's total: containers << kBsibCountShift | payload bytes
-  bool run_opt = false;                // the plan types as runOptimize() does
-  bool ebm_run = false;                // the plan reads bsia_run: per key, column 0 is a full run container
-
-  size_t cells() const { return K * (size_t)m; }
-  size_t per_bytes() const { return 8 * (4 * (size_t)m + 4); }
-
-  int begin(Ctx* ctx, size_t n_keys, int n_cols, size_t extra_key_bytes, bool run_optimize, bool reads_ebm_run) {
-    c = ctx, K = n_keys, m = n_cols, run_opt = run_optimize, ebm_run = reads_ebm_run;
-    key_bytes = 8192 * (size_t)m + extra_key_bytes;
-    CHK(c->bsib_info.ensure(kBsibInfoBytes * cells() + 16));
-    CHK(c->bsib_size.ensure(8 * (cells() + 1)));
-    CHK(c->bsib_part.ensure(8 * (scan_parts(cells()) + 1)));
-    CHK(c->bsib_per.ensure(per_bytes()));
-    if (ebm_run) CHK(c->bsia_run.ensure(K + 16));
-    HIPCHK(hipMemsetAsync(c->bsib_per.p, 0, per_bytes(), c->stream));
-    hp.assign(4 * (size_t)m + 4, 0);
-    P = std::min(K, std::max<size_t>(1, bsib_budget() / key_bytes));
-    if (K) CHK(pool_take(c, ws, key_bytes * P));  // bsi_add of two empty indexes has no key
-    return RBG_OK;
-  }
-
-  // Every pass filled (a later sweep: only when there are several, the one pass is still in ws) and planned,
-  // the sizes scanned, hp and total read back.  more(): the caller's own device-to-host copies, enqueued in
-  // front of the one synchronise.
-  template <class Fill, class More>
-  int sweep(bool first, Fill&& fill, More&& more) {
-    hipStream_t s = c->stream;
-    uint64_t* size = c->bsib_size.as<uint64_t>();
-    unsigned long long* per = c->bsib_per.as<unsigned long long>();
-    if (!first) HIPCHK(hipMemsetAsync(per, 0, per_bytes(), s));
-    for (size_t k_lo = 0; k_lo < K; k_lo += P) {
-      const size_t k_hi = std::min(K, k_lo + P);
-      if (first || P < K) CHK(fill(k_lo, k_hi, first));
-      launch_bsib_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, run_opt ? 1 : 0, c->bsib_info.p, size, per,
-                       per + 4 * m, ebm_run ? c->bsia_run.as<uint8_t>() : nullptr);
-    }
-    launch_exclusive_scan(s, size, size, cells(), c->bsib_part.as<uint64_t>(), size + cells());
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(hp.data(), per, 8 * hp.size(), hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(&total, size + cells(), 8, hipMemcpyDeviceToHost, s));
-    CHK(more());
-    HIPCHK(hipStreamSynchronize(s));
-    return RBG_OK;
-  }
-  template <class Fill>
-  int sweep(bool first, Fill&& fill) {
-    return sweep(first, fill, [] { return RBG_OK; });
-  }
-
-  // The batch: the first n_bm cell columns are its bitmaps (any further column holds no container).
-  template <class Fill>
-  int emit(int n_bm, Fill&& fill, const char* what, int32_t* out_id) {
-    hipStream_t s = c->stream;
-    uint64_t* size = c->bsib_size.as<uint64_t>();
-    const size_t C = (size_t)(total >> kBsibCountShift);
-    const int32_t id = new_batch(c);
-    Batch& b = *c->batches[id];
-    BatchGuard guard{c, {id}};  // dropped unless the build completes
-    b.payload_bytes = (size_t)(total & ((1ull << kBsibCountShift) - 1));
-    CHK(pool_take(c, b.keys, 2 * C + 16));
-    CHK(pool_take(c, b.desc, sizeof(CDesc) * C + 16));
-    CHK(pool_take(c, b.bm, 4 * C + 16));
-    CHK(pool_take(c, b.key_off, 4 * (kMaxKeys + 1)));
-    CHK(pool_take(c, b.bm_off, 4 * ((size_t)n_bm + 1)));
-    CHK(pool_take(c, b.payload, b.payload_bytes + 64));
-    for (size_t k_lo = 0; k_lo < K; k_lo += P) {
-      const size_t k_hi = std::min(K, k_lo + P);
-      if (P < K) CHK(fill(k_lo, k_hi, false));  // several passes: the workspace held another pass since the plan
-      launch_bsib_write(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, c->bsib_info.p, size,
-                        c->bsib_pkeys.as<uint16_t>(), b.desc.as<CDesc>(), b.keys.as<uint16_t>(), b.bm.as<uint32_t>(),
-                        b.payload.as<uint8_t>());
-    }
-    launch_bsib_key_off(s, c->bsib_pkoff.as<uint32_t>(), size, m, b.key_off.as<uint32_t>());
-    HIPCHK(hipGetLastError());
-    pool_put(c, ws);  // whatever takes it next is enqueued on this stream, after the write kernels
-    b.n_bm = (size_t)n_bm;
-    b.n_ctr = C;
-    b.key_major = true;
-    for (int k = 0; k < 3; k++) b.n_kind[k] = (int64_t)hp[4 * m + k];
-    b.max_ser = 0;  // no container above kStagedMax serialized bytes
-    b.h_bm_off.assign(n_bm + 1, 0);
-    b.h_bm_nctr.resize(n_bm);
-    b.h_bm_card.resize(n_bm);
-    b.h_has_run.resize(n_bm);
-    for (int i = 0; i < n_bm; i++) {
-      b.h_bm_nctr[i] = (uint32_t)hp[4 * i];
-      b.h_bm_off[i + 1] = b.h_bm_off[i] + b.h_bm_nctr[i];
-      b.h_bm_card[i] = (int64_t)hp[4 * i + 1];
-      b.h_has_run[i] = hp[4 * i + 3] != 0;
-      b.long_card += b.h_bm_card[i];
-      b.ser_bytes += (int64_t)(header_size(b.h_bm_nctr[i], b.h_has_run[i] != 0) + hp[4 * i + 2]);
-    }
-    HIPCHK(hipMemcpyAsync(b.bm_off.p, b.h_bm_off.data(), 4 * ((size_t)n_bm + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(hipStreamSynchronize(s));
-    dbg(s, what);
-    guard.ids.clear();
-    b.live = true;
-    *out_id = id;
-    return RBG_OK;
-  }
-};
-
-// A bit-sliced index from n (column, value) pairs in device memory (u32 columns, all distinct; i32 values,
-// none negative; any order) as a new key-major batch [ebM, bA[0..nbits-1]]: setValue for every pair
-// (BSI/:299-347: ensureCapacityInternal's min / max and bit count, then ebM.add and one add per set bit),
-// with run_opt followed by runOptimize() (BSI/:141-150) -- the batch ctx_load of the host builder's
-// bitmaps gives (bsibuild.hip).  out3 = {nbits, minValue, maxValue}.  Two read-backs: the key count with
-// min / max (a negative value is refused here), then the per-input totals (a repeated column shows as
-// cardinality(ebM) != n and is refused before anything is allocated for the batch).
-// The K x (nbits + 1) bitmaps are a BsibPlan whose fill is the scatter.  The pairs are read by every scatter:
-// they must not change until the call returns.
-static int ctx_bsi_from_columns(Ctx* c, const uint32_t* col_dev, const int32_t* val_dev, size_t n, bool run_opt,
-                                int32_t* out_id, int32_t* out3) {
-  hipStream_t s = c->stream;
-  out3[0] = out3[1] = out3[2] = 0;
-  if (n == 0) return ctx_empty_bitmap(c, out_id);  // ebM, no slice
-  if (n > (1ull << 32)) {
-    set_err("bsi_from_columns: more pairs than columns");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
-  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
-  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] {min, max} as two i32
-  HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
-  HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxSeedI32, 8, hipMemcpyHostToDevice, s));
-  launch_bld_keys(s, col_dev, n, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
-  launch_bsib_minmax(s, val_dev, n, reinterpret_cast<int*>(sc + 1));
-  HIPCHK(hipGetLastError());
-  unsigned long long h[2] = {};
-  HIPCHK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const size_t K = (size_t)h[0];
-  const int32_t mn = (int32_t)(uint32_t)h[1], mx = (int32_t)(uint32_t)(h[1] >> 32);
-  if (mn < 0) {
-    set_err("Values should be non-negative");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  const int nbits = mx ? 32 - __builtin_clz((uint32_t)mx) : 1;  // Integer.toBinaryString(max).length()
-  const int m = nbits + 1;
-  dbg(s, "bsi_from_columns: keys + min / max");
-  BsibPlan plan;
-  CHK(plan.begin(c, K, m, 0, run_opt, false));
-  auto scatter = [&](size_t k_lo, size_t k_hi, bool) -> int {
-    HIPCHK(hipMemsetAsync(plan.ws.p, 0, 8192 * (size_t)m * (k_hi - k_lo), s));
-    launch_bsib_scatter(s, col_dev, val_dev, n, c->bsib_pkoff.as<uint32_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m,
-                        plan.ws.as<uint32_t>());
-    return RBG_OK;
-  };
-  CHK(plan.sweep(true, scatter));
-  dbg(s, "bsi_from_columns: scatter + plan");
-  if (plan.hp[1] != n) {  // setValue overwrites: a column given twice would need the pairs' order
-    set_err("bsi_from_columns: a column is given more than once");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  CHK(plan.emit(m, scatter, "bsi_from_columns: write", out_id));
-  out3[0] = nbits;
-  out3[1] = mn;
-  out3[2] = mx;
-  return RBG_OK;
-}
-
-// the same from host memory: the pairs go to the device through the context's pinned buffer
-static int ctx_bsi_from_columns_host(Ctx* c, const uint32_t* col, const int32_t* val, size_t n, bool run_opt,
-                                     int32_t* out_id, int32_t* out3) {
-  DevBuf dc, dv;
-  CHK(pool_take(c, dc, 4 * n + 16));
-  CHK(pool_take(c, dv, 4 * n + 16));
-  CHK(upload_words(c, dc.p, col, n));
-  CHK(upload_words(c, dv.p, val, n));
-  const int st = ctx_bsi_from_columns(c, dc.as<uint32_t>(), dv.as<int32_t>(), n, run_opt, out_id, out3);
-  pool_put(c, dc);
-  pool_put(c, dv);
-  return st;
-}
-
-// An operand of the fused add: a key-major, unpacked, run-free batch [ebM, bA[0..nbits-1]]
-static int bsi_add_operand(Ctx* c, int32_t id, int nbits, Batch** B, BsiAddSide* side) {
-  CHK(get_batch(c, id, B));
-  const Batch* b = *B;
-  if (nbits < 0 || nbits > 32) {
-    set_err("bsi_add: an index holds at most 32 slices");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  if (!b->key_major || b->packed || b->n_bm != (size_t)(1 + nbits)) {
-    set_err("bsi_add: batch must be key-major, unpacked and hold ebM and nbits slices");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  if (b->n_kind[DK_R] != 0) {
-    set_err("bsi_add: an operand holds a run container; the composed route (and / xor per slice) handles it");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  *side = BsiAddSide{b->key_off.as<uint32_t>(), b->desc.as<CDesc>(), b->bm.as<uint32_t>(), b->payload.as<uint8_t>(), nbits};
-  return RBG_OK;
-}
-
-// RoaringBitmapSliceIndex.add (BSI/:66-95; MutableBitSliceIndex.add, buffer/MutableBitSliceIndex.java:121-130,
-// 201-262) of two resident run-free indexes as a new key-major batch [ebM', bA'[0..n'-1]]: what ctx_load of
-// the reference's result bitmaps gives (bsiadd.hip; both operands untouched, batch_a == batch_b doubles).
-// out3 = {n', minValue, maxValue}, min / max from the descent of BSI/:97-138 as Java ints.  An empty ebM of
-// b (:67-69): a copy of a with {nbits_a, min_a, max_a}.  Two read-backs: the key count, then the per-input
-// totals with min / max -- the carry out of the top input slice decides whether the result has one more
-// slice, and out of slice 31 it is refused before a batch exists.  The K x (2 + max(na, nb)) bitmaps are a
-// BsibPlan whose fill is the add, followed in the sweep by the min / max descent.
-static int ctx_bsi_add(Ctx* c, int32_t batch_a, int nbits_a, int32_t batch_b, int nbits_b, int32_t min_a, int32_t max_a,
-                       int32_t* out_id, int32_t* out3) {
-  hipStream_t s = c->stream;
-  Batch *A, *B;
-  BsiAddSide sa, sb;
-  CHK(bsi_add_operand(c, batch_a, nbits_a, &A, &sa));
-  CHK(bsi_add_operand(c, batch_b, nbits_b, &B, &sb));
-  const bool b_empty = B->h_bm_card.empty() || B->h_bm_card[0] == 0;
-  if (b_empty) sb = BsiAddSide{nullptr, nullptr, nullptr, nullptr, 0};
-  const int top = b_empty ? nbits_a : std::max(nbits_a, nbits_b);
-  const int m = top + 2;
-  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
-  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
-  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] {min, max} as two u32
-  HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
-  HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxSeedU32, 8, hipMemcpyHostToDevice, s));
-  launch_bsia_keys(s, A->keys.as<uint16_t>(), A->n_ctr, B->keys.as<uint16_t>(), b_empty ? 0 : B->n_ctr,
-                   c->flag.as<uint8_t>());
-  launch_bld_keys(s, nullptr, 0, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
-  HIPCHK(hipGetLastError());
-  unsigned long long h[2] = {};
-  HIPCHK(hipMemcpyAsync(h, sc, 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const size_t K = (size_t)h[0];
-  dbg(s, "bsi_add: keys");
-  BsibPlan plan;
-  CHK(plan.begin(c, K, m, 0, false, true));
-  auto fill = [&](size_t k_lo, size_t k_hi, bool first) -> int {  // every cell of the pass is written: no memset
-    launch_bsi_add(s, sa, sb, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, plan.ws.as<uint8_t>(),
-                   c->bsia_run.as<uint8_t>());
-    if (first && !b_empty)
-      launch_bsia_minmax(s, plan.ws.as<uint8_t>(), (uint32_t)(k_hi - k_lo), m, reinterpret_cast<uint32_t*>(sc + 1));
-    return RBG_OK;
-  };
-  uint32_t mm[2] = {0, 0};
-  auto read_mm = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(mm, sc + 1, 8, hipMemcpyDeviceToHost, s));
-    return RBG_OK;
-  };
-  CHK(plan.sweep(true, fill, read_mm));
-  dbg(s, "bsi_add: add + plan");
-  const bool grown = plan.hp[4 * (size_t)(m - 1) + 1] != 0;  // a carry left the top input slice
-  if (grown && top == 32) {
-    set_err("bsi_add: the sum needs more than 32 slices");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  const int nbits = top + (grown ? 1 : 0);
-  CHK(plan.emit(1 + nbits, fill, "bsi_add: write", out_id));
-  out3[0] = nbits;
-  if (b_empty) {  // the reference returns before it recomputes them
-    out3[1] = min_a;
-    out3[2] = max_a;
-  } else {  // an empty ebM' (b's ebM holds a column: cannot be) would leave {~0u, 0}; minValue() gives 0 then
-    out3[1] = mm[0] <= mm[1] ? (int32_t)mm[0] : 0;
-    out3[2] = mm[0] <= mm[1] ? (int32_t)mm[1] : 0;
-  }
-  return RBG_OK;
-}
-
-// RoaringBitmapSliceIndex.setValues(List<Pair>) (BSI/:349-357; setValue, :299-313, is n == 1; the buffer
-// package's MutableBitSliceIndex.setValues, buffer/MutableBitSliceIndex.java:146-195) of n >= 1 pairs in device
-// memory (u32 columns, repeated at will; i32 values, none negative; the pair with the highest index decides a
-// column) on a resident index, the key-major batch [ebM, bA[0..nbits-1]] with the caller's min / max, as a new
-// batch [ebM', bA'[0..d'-1]]: what ctx_load of the reference's bitmaps after the call gives (bsiset.hip; the
-// operand untouched).  out3 = {d', minValue, maxValue} by ensureCapacityInternal (BSI/:315-326) over the
-// batch's own extremes -- its else-if included: a batch below min and above max lowers min alone, and the
-// high bits of its values are dropped.  Two read-backs: the key count with min / max (a negative value is
-// refused here), then the plan's totals with the run-container refusal (a slice may hold none, ebM only full
-// ones, which stay run containers).  The K x (1 + d') bitmaps are a BsibPlan whose fill expands the operand
-// and applies the pairs, with the last-pair table of 256 KiB as a key's extra bytes.  The pairs are read by
-// every pass: they must not change until the call returns.
-static int ctx_bsi_set_values(Ctx* c, int32_t batch, int nbits, int32_t min_v, int32_t max_v, const uint32_t* col_dev,
-                              const int32_t* val_dev, size_t n, int32_t* out_id, int32_t* out3) {
-  hipStream_t s = c->stream;
-  Batch* A;
-  CHK(get_batch(c, batch, &A));
-  if (nbits < 0 || nbits > 32) {
-    set_err("bsi_set_values: an index holds at most 32 slices");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  if (!A->key_major || A->packed || A->n_bm != (size_t)(1 + nbits)) {
-    set_err("bsi_set_values: batch must be key-major, unpacked and hold ebM and nbits slices");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  if (n == 0 || n > 0xFFFFFFFFull) {  // values.stream().max().getAsInt() throws on an empty list
-    set_err(n ? "bsi_set_values: more pairs than a 32-bit pair index holds" : "bsi_set_values: no pair given");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  const BsiAddSide sa{A->key_off.as<uint32_t>(), A->desc.as<CDesc>(), A->bm.as<uint32_t>(), A->payload.as<uint8_t>(),
-                      nbits};
-  const bool was_empty = A->h_bm_card.empty() || A->h_bm_card[0] == 0;
-  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
-  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
-  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] {min, max} as two i32, [2] refused
-  HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
-  HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-  HIPCHK(hipMemcpyAsync(sc + 1, kMinMaxSeedI32, 8, hipMemcpyHostToDevice, s));
-  launch_bsia_keys(s, A->keys.as<uint16_t>(), A->n_ctr, nullptr, 0, c->flag.as<uint8_t>());
-  launch_bld_keys(s, col_dev, n, c->flag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(), sc);
-  launch_bsib_minmax(s, val_dev, n, reinterpret_cast<int*>(sc + 1));
-  HIPCHK(hipGetLastError());
-  unsigned long long h[2] = {};
-  HIPCHK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  const size_t K = (size_t)h[0];
-  const int32_t mn = (int32_t)(uint32_t)h[1], mx = (int32_t)(uint32_t)(h[1] >> 32);
-  if (mn < 0) {
-    set_err("Values should be non-negative");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  dbg(s, "bsi_set_values: keys + min / max");
-  const int need = mx ? 32 - __builtin_clz((uint32_t)mx) : 1;  // Integer.toBinaryString(max).length()
-  int d = nbits;
-  if (was_empty) {  // ensureCapacityInternal
-    min_v = mn;
-    max_v = mx;
-    d = std::max(d, need);
-  } else if (min_v > mn) {
-    min_v = mn;
-  } else if (max_v < mx) {
-    max_v = mx;
-    d = std::max(d, need);
-  }
-  const int m = 1 + d;
-  constexpr size_t kTab = 4 * 65536;  // a key's last-pair table: after the cells of a pass
-  BsibPlan plan;
-  CHK(plan.begin(c, K, m, kTab, false, true));
-  uint32_t* tab = reinterpret_cast<uint32_t*>(plan.ws.as<uint8_t>() + 8192 * (size_t)m * plan.P);
-  auto fill = [&](size_t k_lo, size_t k_hi, bool) -> int {  // every cell of the pass is written: no memset
-    launch_bsis_expand(s, sa, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, plan.ws.as<uint8_t>(),
-                       c->bsia_run.as<uint8_t>(), reinterpret_cast<uint32_t*>(sc + 2));
-    HIPCHK(hipMemsetAsync(tab, 0, kTab * (k_hi - k_lo), s));
-    launch_bsis_last(s, col_dev, n, c->bsib_pkoff.as<uint32_t>(), (uint32_t)k_lo, (uint32_t)k_hi, tab);
-    launch_bsis_apply(s, col_dev, val_dev, n, c->bsib_pkoff.as<uint32_t>(), (uint32_t)k_lo, (uint32_t)k_hi, m, tab,
-                      plan.ws.as<uint32_t>());
-    return RBG_OK;
-  };
-  uint32_t bad = 0;
-  auto read_bad = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(&bad, sc + 2, 4, hipMemcpyDeviceToHost, s));
-    return RBG_OK;
-  };
-  CHK(plan.sweep(true, fill, read_bad));
-  dbg(s, "bsi_set_values: expand + apply + plan");
-  if (bad) {
-    set_err("bsi_set_values: a slice holds a run container, or ebM one that is not full");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  CHK(plan.emit(m, fill, "bsi_set_values: write", out_id));
-  out3[0] = d;
-  out3[1] = min_v;
-  out3[2] = max_v;
-  return RBG_OK;
-}
-
-// the same from host memory: the pairs go to the device through the context's pinned buffer
-static int ctx_bsi_set_values_host(Ctx* c, int32_t batch, int nbits, int32_t min_v, int32_t max_v, const uint32_t* col,
-                                   const int32_t* val, size_t n, int32_t* out_id, int32_t* out3) {
-  DevBuf dc, dv;
-  CHK(pool_take(c, dc, 4 * n + 16));
-  CHK(pool_take(c, dv, 4 * n + 16));
-  CHK(upload_words(c, dc.p, col, n));
-  CHK(upload_words(c, dv.p, val, n));
-  const int st = ctx_bsi_set_values(c, batch, nbits, min_v, max_v, dc.as<uint32_t>(), dv.as<int32_t>(), n, out_id, out3);
-  pool_put(c, dc);
-  pool_put(c, dv);
-  return st;
-}
-
-// A batch as the operand of the BSI read-outs (bsival.hip): key-major [ebM, nbits slices, foundSet?]
-static int bsi_val_operand(Ctx* c, int32_t id, int nbits, int has_found, Batch** B, BsiValArgs* a) {
-  CHK(get_batch(c, id, B));
-  const Batch* b = *B;
-  if (!b->key_major || b->packed || nbits < 0 || nbits + 2 > kBsiMaxInputs ||
-      b->n_bm != (size_t)(1 + nbits + (has_found ? 1 : 0))) {
-    set_err("bsi values: batch must hold ebM, nbits slices and the optional foundSet");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  *a = BsiValArgs{b->key_off.as<uint32_t>(), b->desc.as<CDesc>(), b->bm.as<uint32_t>(), b->payload.as<uint8_t>(), nbits};
-  return RBG_OK;
-}
-
-// getValue (BSI/:181-196) of n columns (device memory, u32, any order, repeats allowed) into out (device
-// memory, i64; -1: ebM lacks the column), in query order, enqueued on the context stream
-static int ctx_bsi_get_values(Ctx* c, int32_t batch, int nbits, int has_found, const uint32_t* q_dev, size_t n,
-                              long long* out_dev) {
-  Batch* B;
-  BsiValArgs a;
-  CHK(bsi_val_operand(c, batch, nbits, has_found, &B, &a));
-  launch_bsi_get_values(c->stream, a, q_dev, n, out_dev);
-  HIPCHK(hipGetLastError());
-  return RBG_OK;
-}
-
-// the same from host memory: staged through the context's pinned buffer, results in out on return
-static int ctx_bsi_get_values_host(Ctx* c, int32_t batch, int nbits, int has_found, const uint32_t* q, size_t n,
-                                   int64_t* out) {
-  CHK(pinned_ensure(c, 12 * n + 64));
-  CHK(c->pt_q.ensure(4 * n));
-  CHK(c->pt_out.ensure(8 * n));
-  uint8_t* pin = reinterpret_cast<uint8_t*>(c->pinned);
-  hipStream_t s = c->stream;
-  HIPCHK(hipStreamSynchronize(s));  // nothing enqueued earlier still reads the staging buffer
-  std::memcpy(pin + 8 * n, q, 4 * n);
-  HIPCHK(hipMemcpyAsync(c->pt_q.p, pin + 8 * n, 4 * n, hipMemcpyHostToDevice, s));
-  CHK(ctx_bsi_get_values(c, batch, nbits, has_found, c->pt_q.as<uint32_t>(), n, c->pt_out.as<long long>()));
-  HIPCHK(hipMemcpyAsync(pin, c->pt_out.p, 8 * n, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  std::memcpy(out, pin, 8 * n);
-  return RBG_OK;
-}
-
-// toPairList() (BBSI/:534-549): every column of ebM, ascending and unsigned, into cols_dev (u32, or i64
-// with cols64) with its value in vals_dev (i32, or i64 with vals64), enqueued on the context stream.
-// *n_out: the pairs, known here from ebM's cardinality; no buffers with n_out: the size alone.
-static int ctx_bsi_to_pairs(Ctx* c, int32_t batch, int nbits, int has_found, bool cols64, bool vals64, void* cols_dev,
-                            void* vals_dev, uint64_t* n_out) {
-  Batch* B;
-  BsiValArgs a;
-  CHK(bsi_val_operand(c, batch, nbits, has_found, &B, &a));
-  const uint64_t total = B->h_bm_card.empty() ? 0 : (uint64_t)B->h_bm_card[0];
-  if (n_out) *n_out = total;
-  if (!total || (!cols_dev && !vals_dev && n_out)) return RBG_OK;
-  if (!cols_dev || !vals_dev) {
-    set_err("bsi_to_pairs: no output buffer");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  CHK(c->bsiv_cards.ensure(8 * (kMaxKeys + 1)));
-  CHK(c->bsiv_part.ensure(8 * (scan_parts(kMaxKeys) + 1)));
-  uint64_t* cards = c->bsiv_cards.as<uint64_t>();
-  launch_bsi_pair_cards(c->stream, a, cards);
-  launch_exclusive_scan(c->stream, cards, cards, kMaxKeys, c->bsiv_part.as<uint64_t>(), cards + kMaxKeys);
-  launch_bsi_pairs(c->stream, a, cards, cols64, vals64, cols_dev, vals_dev);
-  HIPCHK(hipGetLastError());
-  return RBG_OK;
-}
-
-// the same into host memory: both arrays on the device first, then one copy each
-static int ctx_bsi_to_pairs_host(Ctx* c, int32_t batch, int nbits, int has_found, bool cols64, bool vals64, void* cols,
-                                 void* vals, uint64_t* n_out) {
-  uint64_t total = 0;
-  CHK(ctx_bsi_to_pairs(c, batch, nbits, has_found, cols64, vals64, nullptr, nullptr, &total));  // operand check, size
-  if (n_out) *n_out = total;
-  if (!total || (!cols && !vals && n_out)) return RBG_OK;
-  if (!cols || !vals) {
-    set_err("bsi_to_pairs: no output buffer");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  const size_t cb = (cols64 ? 8 : 4) * (size_t)total, vb = (vals64 ? 8 : 4) * (size_t)total;
-  DevBuf dc, dv;
-  CHK(pool_take(c, dc, cb));
-  CHK(pool_take(c, dv, vb));
-  CHK(ctx_bsi_to_pairs(c, batch, nbits, has_found, cols64, vals64, dc.p, dv.p, nullptr));
-  HIPCHK(hipMemcpyAsync(cols, dc.p, cb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipMemcpyAsync(vals, dv.p, vb, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  pool_put(c, dc);
-  pool_put(c, dv);
-  return RBG_OK;
-}
-
-// The shared front of the queries that walk ebM & fixed (fixed = the foundSet or ebM) in parallelExec's batches
-// (BBSI/:99-136): ctx_bsi_in and ctx_bsi_transpose.
-struct BsiFixed {
-  Batch* B;
-  BsiValArgs a;
-  int64_t card;        // fixed.getCardinality(), an int
-  int64_t ebm_card;
-  int64_t batch_size;  // min(max(card / parallelism, parallelism), 65536) (Java int arithmetic)
-  bool empty;          // fixed or ebM holds no column: the result is one empty bitmap
-};
-
-// the argument checks (op: the name in the messages) and the host's numbers
-static int bsi_fixed_operand(Ctx* c, const char* op, int32_t batch, int nbits, int has_found, int parallelism,
-                             BsiFixed* f) {
-  if (parallelism < 1) {
-    set_err(std::string(op) + ": parallelism must be positive");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  if (nbits < 0 || nbits > 32) {
-    set_err(std::string(op) + ": an index holds at most 32 slices");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  CHK(bsi_val_operand(c, batch, nbits, has_found, &f->B, &f->a));
-  const std::vector<int64_t>& cards = f->B->h_bm_card;
-  const size_t fx = has_found ? (size_t)nbits + 1 : 0;
-  f->card = cards.size() > fx ? cards[fx] : 0;
-  if (f->card > INT32_MAX) {
-    set_err(std::string(op) + ": the foundSet (or ebM) holds more than 2^31 - 1 columns");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  f->ebm_card = cards.empty() ? 0 : cards[0];
-  f->empty = f->card == 0 || f->ebm_card == 0;
-  f->batch_size = std::min<int64_t>(std::max<int64_t>(f->card / parallelism, parallelism), 65536);
-  return RBG_OK;
-}
-
-// The candidate keys (those ebM and fixed share) into ckeys / ckoff with their count in scalar[0], which the
-// caller has zeroed, and into bsiv_cards the exclusive scan of the keys' cardinalities in fixed: the rank in
-// fixed of a key's first column.
-static int bsi_fixed_keys(Ctx* c, const BsiFixed& f, int has_found, DevBuf& ckeys, DevBuf& ckoff) {
-  CHK(ckeys.ensure(2 * kMaxKeys + 16));
-  CHK(ckoff.ensure(4 * (kMaxKeys + 1)));
-  CHK(c->bsiv_cards.ensure(8 * (kMaxKeys + 1)));
-  CHK(c->bsiv_part.ensure(8 * (scan_parts(kMaxKeys) + 1)));
-  uint64_t* rank = c->bsiv_cards.as<uint64_t>();
-  launch_bsiin_keys(c->stream, f.a, has_found, c->flag.as<uint8_t>(), rank);
-  launch_bld_keys(c->stream, nullptr, 0, c->flag.as<uint8_t>(), ckeys.as<uint16_t>(), ckoff.as<uint32_t>(),
-                  c->scalar.as<unsigned long long>());
-  launch_exclusive_scan(c->stream, rank, rank, kMaxKeys, c->bsiv_part.as<uint64_t>(), rank + kMaxKeys);
-  return RBG_OK;
-}
-
-constexpr size_t kBsiInHostSort = 1024;  // ctx_bsi_in: longer value lists are sorted on the device
-
-// BitSliceIndexBase.parallelIn(parallelism, foundSet, values, pool) (BBSI/:611-639) over the resident index
-// [ebM, bA[0..nbits-1], foundSet?] as a new one-bitmap key-major batch: what ctx_load of the reference's
-// result gives (bsiin.hip).  The set is {c in ebM & fixed : value(c) in values}, fixed = the foundSet or ebM;
-// parallelism enters through parallelExec's batchSize (BBSI/:99-136) alone, which decides whether a full
-// container is a bitmap or RunContainer.full().  values: n_values host ints in any order,
-// repeats allowed; the device gets a sorted distinct copy.  An empty fixed, ebM or list: one empty bitmap.  Two
-// read-backs: the candidate key count, then the plan's totals.  The K x 8 KiB workspace is a BsibPlan of
-// one cell per key whose fill is the membership kernel.
-static int ctx_bsi_in(Ctx* c, int32_t batch, int nbits, int has_found, const int32_t* values, size_t n_values,
-                      int parallelism, int32_t* out_id) {
-  hipStream_t s = c->stream;
-  if (n_values > (size_t)INT32_MAX) {
-    set_err("bsi_in: more than 2^31 - 1 values in the list");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  BsiFixed f;
-  CHK(bsi_fixed_operand(c, "bsi_in", batch, nbits, has_found, parallelism, &f));
-  if (f.empty || n_values == 0) return ctx_empty_bitmap(c, out_id);
-  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] K, [1] the distinct list entries
-  // the list as 32-bit patterns (membership is their equality), ascending and distinct, in device memory: a
-  // short one is sorted here, a long one on the device
-  DevBuf dl;  // back to the pool at the end (freed on an error)
-  size_t n_list = 0;
-  CHK(pool_take(c, dl, 4 * n_values + 16));
-  if (n_values <= kBsiInHostSort) {
-    std::vector<uint32_t> list(n_values);
-    std::memcpy(list.data(), values, 4 * n_values);
-    std::sort(list.begin(), list.end());
-    list.erase(std::unique(list.begin(), list.end()), list.end());
-    n_list = list.size();
-    CHK(upload_words(c, dl.p, list.data(), n_list));
-    HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-  } else {
-    DevBuf scratch, temp;
-    const size_t tb = bsiin_sort_temp_bytes(n_values);
-    CHK(pool_take(c, scratch, 4 * n_values + 16));
-    CHK(pool_take(c, temp, tb));
-    CHK(upload_words(c, dl.p, values, n_values));
-    HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-    HIPCHK((hipError_t)launch_bsiin_sort_unique(s, temp.p, tb, dl.as<uint32_t>(), scratch.as<uint32_t>(), sc + 1,
-                                                n_values));
-    pool_put(c, scratch);  // whatever takes them next is enqueued on this stream, after the sort
-    pool_put(c, temp);
-  }
-  CHK(bsi_fixed_keys(c, f, has_found, c->bsib_pkeys, c->bsib_pkoff));
-  HIPCHK(hipGetLastError());
-  unsigned long long h[2] = {};
-  HIPCHK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (n_values > kBsiInHostSort) n_list = (size_t)h[1];
-  const size_t K = (size_t)h[0];
-  dbg(s, "bsi_in: keys");
-  if (K == 0) {  // ebM and the foundSet share no key
-    pool_put(c, dl);
-    return ctx_empty_bitmap(c, out_id);
-  }
-  BsibPlan plan;
-  CHK(plan.begin(c, K, 1, 0, false, true));
-  auto fill = [&](size_t k_lo, size_t k_hi, bool) -> int {  // every cell of the pass is written: no memset
-    launch_bsi_in(s, f.a, has_found, dl.as<uint32_t>(), (uint32_t)n_list, c->bsib_pkeys.as<uint16_t>(), (uint32_t)k_lo,
-                  (uint32_t)k_hi, c->bsiv_cards.as<uint64_t>(), f.batch_size == 65536, plan.ws.as<uint8_t>(),
-                  c->bsia_run.as<uint8_t>());
-    return RBG_OK;
-  };
-  CHK(plan.sweep(true, fill));
-  dbg(s, "bsi_in: in + plan");
-  const int st = plan.emit(1, fill, "bsi_in: write", out_id);  // synchronises
-  pool_put(c, dl);
-  return st;
-}
-
-// The full result keys of a transpose that are RunContainer.full(): per key, over the batches
-// of parallelExec that contribute a value to it in order, d_t distinct values in batch t and U_t in the union
-// after it; a run container iff some t >= 2 has U_t == 65536 and d_t > 4096 (Container.ior's full union with
-// a bitmap on the other side).  rank[] / val[]: (rank in fixed, value) of every column whose value lies in a
-// full key, in any order; slot[value >> 16]: the key's index, or -1.
-static void bsit_full_runs(const std::vector<uint32_t>& rank, const std::vector<uint32_t>& val, size_t n,
-                           const std::vector<int32_t>& slot, uint64_t batch_size, std::vector<uint8_t>& run) {
-  std::vector<std::vector<uint64_t>> per(run.size());  // batch << 16 | low half of the value
-  for (size_t i = 0; i < n; i++) {
-    const int32_t ki = slot[val[i] >> 16];
-    if (ki >= 0) per[(size_t)ki].push_back(((uint64_t)rank[i] / batch_size) << 16 | (val[i] & 0xFFFFu));
-  }
-  std::vector<uint8_t> seen(65536);
-  for (size_t ki = 0; ki < per.size(); ki++) {
-    std::vector<uint64_t>& v = per[ki];
-    if (v.empty()) continue;
-    std::sort(v.begin(), v.end());
-    v.erase(std::unique(v.begin(), v.end()), v.end());
-    std::fill(seen.begin(), seen.end(), 0);
-    size_t uni = 0, t = 0;
-    for (size_t i = 0; i < v.size();) {
-      size_t j = i;
-      while (j < v.size() && (v[j] >> 16) == (v[i] >> 16)) {
-        if (!seen[v[j] & 0xFFFFu]) seen[v[j] & 0xFFFFu] = 1, uni++;
-        j++;
-      }
-      t++;
-      if (t >= 2 && uni == 65536 && j - i > 4096) run[ki] = 1;
-      i = j;
-    }
-  }
-}
-
-// ctx_bsi_transpose: below this many columns per result key (an upper bound: min(card(ebM), card(fixed)) / K')
-// the sort route runs.  Measured at 32 (the count tables lose 17 x) and at 16,384 (they win); not tuned between.
-constexpr uint64_t kBsitSparse = 256;
-
-// BitSliceIndexBase.parallelTransposeWithCount(foundSet, parallelism, pool) (BBSI/:551-597) over the resident
-// index [ebM, bA[0..nbits-1], foundSet?] as a new key-major batch [ebM', bA'[0..nbits'-1]]: what ctx_load of
-// the reference's result gives (bsitr.hip).  The result's columns are the distinct 32-bit values of the
-// columns in ebM & fixed (fixed = the foundSet or ebM), its values their counts; out3 = {nbits', min, max}.
-// parallelism enters through parallelExec's batchSize (BBSI/:99-136) alone, which decides whether a full
-// result key is a bitmap or RunContainer.full().  No column of fixed in ebM: one empty bitmap,
-// {0, 0, 0}.  Read-backs: the result key count, then the plan's totals with min / max and the number of full
-// keys.  Per result key the workspace holds m = 1 + bitlen(min(card(ebM), card(fixed))) cells of 8 KiB (no
-// count exceeds that many bits) and a count table of 256 KiB: a BsibPlan with the table as a key's extra bytes,
-// whose fill counts and writes the cells.  Only when a key is full, batchSize > 4096 and fixed spans two batches: the
-// values of the full keys are set in one bitmap per (full key, batch), a workgroup per full key applies the
-// rule over its batches (above the byte budget: the (rank, value) pairs go to the host instead), and the plan
-// runs again.
-static int ctx_bsi_transpose(Ctx* c, int32_t batch, int nbits, int has_found, int parallelism, int32_t* out_id,
-                             int32_t* out3) {
-  hipStream_t s = c->stream;
-  out3[0] = out3[1] = out3[2] = 0;
-  BsiFixed f;
-  CHK(bsi_fixed_operand(c, "bsi_transpose", batch, nbits, has_found, parallelism, &f));
-  if (f.empty) return ctx_empty_bitmap(c, out_id);
-  const BsiValArgs a = f.a;
-  const int64_t card = f.card, ebm_card = f.ebm_card, batch_size = f.batch_size;
-  const uint32_t grid = f.B->h_bm_nctr[0];  // the keys of ebM: every candidate key is one of them
-  CHK(c->bsit_rflag.ensure(kMaxKeys));
-  CHK(c->bsib_pkeys.ensure(2 * kMaxKeys + 16));
-  CHK(c->bsib_pkoff.ensure(4 * (kMaxKeys + 1)));
-  // [0] candidate keys, [1] K' result keys, [2] {min, max} as two u32, [3] full result keys, [4] pairs
-  unsigned long long* sc = c->scalar.as<unsigned long long>();
-  HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-  HIPCHK(hipMemcpyAsync(sc + 2, kMinMaxSeedU32, 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemsetAsync(c->bsit_rflag.p, 0, kMaxKeys, s));
-  CHK(bsi_fixed_keys(c, f, has_found, c->bsit_ckeys, c->bsit_ckoff));
-  uint64_t* rank = c->bsiv_cards.as<uint64_t>();
-  BsiTrSweep sw{};
-  sw.rflag = c->bsit_rflag.as<uint8_t>();
-  launch_bsitr_sweep(s, 0, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, sw);
-  launch_bld_keys(s, nullptr, 0, c->bsit_rflag.as<uint8_t>(), c->bsib_pkeys.as<uint16_t>(), c->bsib_pkoff.as<uint32_t>(),
-                  sc + 1);
-  HIPCHK(hipGetLastError());
-  unsigned long long h[2] = {};
-  HIPCHK(hipMemcpyAsync(h, sc, 16, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  dbg(s, "bsi_transpose: keys");
-  const size_t K = (size_t)h[1];  // result keys
-  if (K == 0) return ctx_empty_bitmap(c, out_id);  // no column of fixed is in ebM
-  const uint64_t most = (uint64_t)std::min<int64_t>(card, ebm_card);  // no count is larger
-  // Sparse shapes (fewer than kBsitSparse columns per result key): a count table of 256 KiB per key would be
-  // zeroed and read for a handful of counts, so the values are sorted and run-length encoded instead and the
-  // (value, count) pairs go through the build, whose containers are typed by cardinality.  That is the
-  // reference's answer whenever no run container can appear (batchSize <= 4096 or a single batch); a call
-  // that could produce one keeps the count tables.  RBG_BSI_TR_ROUTE=count|sort (read at every call) forces
-  // a route where it is exact.
-  const bool no_run = batch_size <= 4096 || card <= batch_size;
-  bool sparse = most < kBsitSparse * (uint64_t)K;
-  if (const char* e = std::getenv("RBG_BSI_TR_ROUTE")) sparse = e[0] == 's' ? true : e[0] == 'c' ? false : sparse;
-  if (sparse && no_run) {
-    DevBuf dv, ds, du, dn, temp;
-    const size_t tb = bsitr_sort_temp_bytes(most);
-    CHK(pool_take(c, dv, 4 * most + 16));
-    CHK(pool_take(c, ds, 4 * most + 16));
-    CHK(pool_take(c, du, 4 * most + 16));
-    CHK(pool_take(c, dn, 4 * most + 16));
-    CHK(pool_take(c, temp, tb));
-    BsiTrSweep p{};
-    p.n_pairs = sc + 4;
-    p.out_val = dv.as<uint32_t>();
-    p.cap = most;
-    launch_bsitr_sweep(s, 3, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, p);
-    HIPCHK(hipGetLastError());
-    unsigned long long n = 0, runs = 0;
-    HIPCHK(hipMemcpyAsync(&n, sc + 4, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    n = std::min<unsigned long long>(n, most);
-    HIPCHK((hipError_t)launch_bsitr_sort_rle(s, temp.p, tb, dv.as<uint32_t>(), ds.as<uint32_t>(), du.as<uint32_t>(),
-                                             dn.as<int32_t>(), sc + 5, n));
-    HIPCHK(hipMemcpyAsync(&runs, sc + 5, 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    dbg(s, "bsi_transpose: sort + run lengths");
-    const int st = ctx_bsi_from_columns(c, du.as<uint32_t>(), dn.as<int32_t>(), (size_t)runs, false, out_id, out3);
-    pool_put(c, dv);  // whatever takes them next is enqueued on this stream, after the build
-    pool_put(c, ds);
-    pool_put(c, du);
-    pool_put(c, dn);
-    pool_put(c, temp);
-    return st;
-  }
-  const int m = 1 + (64 - __builtin_clzll(most));
-  constexpr size_t kTab = 4 * 65536;  // a result key's count table: after the cells of a pass
-  BsibPlan plan;
-  CHK(plan.begin(c, K, m, kTab, false, true));
-  CHK(c->bsit_kcard.ensure(4 * K + 16));
-  CHK(c->bsit_full.ensure(K + 16));
-  HIPCHK(hipMemsetAsync(c->bsia_run.p, 0, K, s));
-  HIPCHK(hipMemsetAsync(c->bsit_kcard.p, 0, 4 * K, s));
-  HIPCHK(hipMemsetAsync(c->bsit_full.p, 0, K, s));
-  uint32_t* tab = reinterpret_cast<uint32_t*>(plan.ws.as<uint8_t>() + 8192 * (size_t)m * plan.P);
-  sw.rkoff = c->bsib_pkoff.as<uint32_t>();
-  sw.tab = tab;
-  auto fill = [&](size_t k_lo, size_t k_hi, bool stats) -> int {  // every cell of the pass is written
-    HIPCHK(hipMemsetAsync(tab, 0, kTab * (k_hi - k_lo), s));
-    BsiTrSweep p = sw;
-    p.k_lo = (uint32_t)k_lo;
-    p.k_hi = (uint32_t)k_hi;
-    launch_bsitr_sweep(s, 1, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, p);
-    launch_bsitr_cells(s, tab, (uint32_t)k_lo, (uint32_t)k_hi, m, plan.ws.as<uint8_t>(), stats,
-                       reinterpret_cast<uint32_t*>(sc + 2), c->bsit_kcard.as<uint32_t>(), c->bsit_full.as<uint8_t>(),
-                       sc + 3);
-    return RBG_OK;
-  };
-  unsigned long long h3[2] = {};  // {min, max}, full keys: the first sweep's statistics
-  auto read_h3 = [&]() -> int {
-    HIPCHK(hipMemcpyAsync(h3, sc + 2, 16, hipMemcpyDeviceToHost, s));
-    return RBG_OK;
-  };
-  CHK(plan.sweep(true, fill, read_h3));
-  dbg(s, "bsi_transpose: count + plan");
-  if (h3[1] && batch_size > 4096 && card > batch_size) {  // a full key fed by several batches of bitmap size
-    const size_t n_full = (size_t)h3[1];
-    const size_t n_batches = (size_t)((card + batch_size - 1) / batch_size);
-    std::vector<uint8_t> isfull(K);
-    HIPCHK(hipMemcpyAsync(isfull.data(), c->bsit_full.p, K, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (n_full * n_batches * 8192 <= bsib_budget()) {
-      // on the device: a bitmap per (full key, batch), then a workgroup per full key over its batches
-      std::vector<uint32_t> tbl(K + n_full, 0xFFFFFFFFu);  // fidx[K], then fki[n_full]
-      size_t f = 0;
-      for (size_t ki = 0; ki < K && f < n_full; ki++)
-        if (isfull[ki]) tbl[ki] = (uint32_t)f, tbl[K + f++] = (uint32_t)ki;
-      DevBuf dt, bits;
-      CHK(pool_take(c, dt, 4 * tbl.size() + 16));
-      CHK(pool_take(c, bits, n_full * n_batches * 8192));
-      CHK(upload_words(c, dt.p, tbl.data(), tbl.size()));
-      HIPCHK(hipMemsetAsync(bits.p, 0, n_full * n_batches * 8192, s));
-      BsiTrSweep p = sw;
-      p.rank = rank;
-      p.fidx = dt.as<uint32_t>();
-      p.bits = bits.as<uint32_t>();
-      p.n_batches = (uint32_t)n_batches;
-      p.batch_size = (uint32_t)batch_size;
-      launch_bsitr_sweep(s, 4, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, p);
-      launch_bsitr_full_runs(s, bits.as<uint32_t>(), (uint32_t)f, (uint32_t)n_batches, dt.as<uint32_t>() + K,
-                             c->bsia_run.as<uint8_t>());
-      HIPCHK(hipGetLastError());
-      pool_put(c, dt);  // whatever takes them next is enqueued on this stream, after the kernels
-      pool_put(c, bits);
-      CHK(plan.sweep(false, fill));  // a flagged key is a run container of one run: sizes and kinds again
-      dbg(s, "bsi_transpose: full keys");
-    } else {
-      // the bitmaps exceed the budget: the (rank, value) pairs of the full keys go to the host
-      const size_t cap = (size_t)most;
-      DevBuf dr, dv;
-      CHK(pool_take(c, dr, 4 * cap + 16));
-      CHK(pool_take(c, dv, 4 * cap + 16));
-      BsiTrSweep p = sw;
-      p.isfull = c->bsit_full.as<uint8_t>();
-      p.rank = rank;
-      p.n_pairs = sc + 4;
-      p.out_rank = dr.as<uint32_t>();
-      p.out_val = dv.as<uint32_t>();
-      p.cap = cap;
-      launch_bsitr_sweep(s, 2, a, has_found, c->bsit_ckeys.as<uint16_t>(), sc, grid, p);
-      HIPCHK(hipGetLastError());
-      unsigned long long np = 0;
-      std::vector<uint16_t> rkeys(K);
-      std::vector<uint8_t> run(K, 0);
-      HIPCHK(hipMemcpyAsync(&np, sc + 4, 8, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipMemcpyAsync(rkeys.data(), c->bsib_pkeys.p, 2 * K, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      const size_t n = (size_t)std::min<unsigned long long>(np, cap);
-      std::vector<uint32_t> hr(n), hv(n);
-      if (n) {
-        HIPCHK(hipMemcpyAsync(hr.data(), dr.p, 4 * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipMemcpyAsync(hv.data(), dv.p, 4 * n, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-      }
-      pool_put(c, dr);
-      pool_put(c, dv);
-      std::vector<int32_t> slot(65536, -1);
-      for (size_t ki = 0; ki < K; ki++)
-        if (isfull[ki]) slot[rkeys[ki]] = (int32_t)ki;
-      bsit_full_runs(hr, hv, n, slot, (uint64_t)batch_size, run);
-      if (std::find(run.begin(), run.end(), (uint8_t)1) != run.end()) {
-        CHK(pinned_ensure(c, K));
-        std::memcpy(c->pinned, run.data(), K);
-        HIPCHK(hipMemcpyAsync(c->bsia_run.p, c->pinned, K, hipMemcpyHostToDevice, s));
-        CHK(plan.sweep(false, fill));  // the flagged keys are a run container of one run: sizes and kinds again
-        dbg(s, "bsi_transpose: full keys (host)");
-      }
-    }
-  }
-  const uint32_t mn = (uint32_t)h3[0], mx = (uint32_t)(h3[0] >> 32);
-  const int nb = mx ? 32 - __builtin_clz(mx) : 0;
-  CHK(plan.emit(1 + nb, fill, "bsi_transpose: write", out_id));
-  out3[0] = nb;
-  out3[1] = (int32_t)mn;
-  out3[2] = (int32_t)mx;
-  return RBG_OK;
 }
 
 // ImmutableRoaringBitmap.and / andNot and MutableRoaringBitmap's static and / andNot
@@ -2263,49 +1191,6 @@ static int batch_host_index(Ctx* c, Batch* b) {
 // by key, then larger cardinality first (RB/RoaringArray.java:708-713), with the heap's own
 // tie order.  The heap is replayed here over the container table (keys and cardinalities
 // only -- no payload); order[key_off[k] + j] = the j-th container of key k's chain.
-namespace {
-struct HPtr {
-  uint32_t bm, i, key, card, pos;
-};
-static int hcmp(const HPtr& x, const HPtr& y) {  // ContainerPointer.compareTo
-  if (x.key != y.key) return (int)x.key - (int)y.key;
-  return (int)y.card - (int)x.card;
-}
-struct JHeap {  // java.util.PriorityQueue siftUp / siftDown (OpenJDK)
-  std::vector<HPtr> q;
-  void add(const HPtr& x) {
-    size_t k = q.size();
-    q.push_back(x);
-    while (k > 0) {
-      const size_t p = (k - 1) >> 1;
-      if (hcmp(x, q[p]) >= 0) break;
-      q[k] = q[p];
-      k = p;
-    }
-    q[k] = x;
-  }
-  HPtr poll() {
-    const HPtr r = q[0];
-    const HPtr x = q.back();
-    q.pop_back();
-    const size_t n = q.size();
-    if (n) {
-      size_t k = 0;
-      const size_t half = n >> 1;
-      while (k < half) {
-        size_t ch = 2 * k + 1;
-        if (ch + 1 < n && hcmp(q[ch], q[ch + 1]) > 0) ch++;
-        if (hcmp(x, q[ch]) <= 0) break;
-        q[k] = q[ch];
-        k = ch;
-      }
-      q[k] = x;
-    }
-    return r;
-  }
-};
-}  // namespace
-
 // *identity: the chain order is the batch's own (no key needed sorting): no order table
 static int horizontal_order(Ctx* c, Batch* B, bool* identity) {
   *identity = B->h_chain_identity;
@@ -2790,282 +1675,6 @@ static int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const in
   });
 }
 
-// compareUsingMinMax (BSI/:515-579): 0 = run the circuit, 1 = all, 2 = empty
-static int bsi_minmax(int op, int32_t s, int32_t e, int32_t lo, int32_t hi) {
-  switch (op) {
-    case BSI_LT: return s > hi ? 1 : s <= lo ? 2 : 0;
-    case BSI_LE: return s >= hi ? 1 : s < lo ? 2 : 0;
-    case BSI_GT: return s < lo ? 1 : s >= hi ? 2 : 0;
-    case BSI_GE: return s <= lo ? 1 : s > hi ? 2 : 0;
-    case BSI_EQ:
-      if (lo == hi && lo == s) return 1;
-      return (s < lo || s > hi) ? 2 : 0;
-    case BSI_NEQ:
-      if (lo == hi) return lo == s ? 2 : 1;
-      return 0;
-    case BSI_RANGE:
-      if (s <= lo && e >= hi) return 1;
-      return (s > hi || e < lo) ? 2 : 0;
-    default: return 0;
-  }
-}
-
-// RoaringBitmapSliceIndex.compare (BSI/:482-513) and / or sum (BSI/:581-592) over a
-// key-major batch [ebM, bA[0..nbits-1], foundSet?]; the result is materialised like a
-// wide op's, the sums land in c->bsi_sums.
-static int ctx_bsi(Ctx* c, int32_t id, int op, int nbits, int has_found, int32_t start, int32_t end,
-                   int32_t min_value, int32_t max_value, int want_sum) {
-  Batch* B;
-  CHK(get_batch(c, id, &B));
-  if (!B->key_major || B->packed || nbits < 0 || nbits + 2 > kBsiMaxInputs || B->n_bm != (size_t)(1 + nbits + (has_found ? 1 : 0)) ||
-      op < 0 || op > BSI_SUM_ONLY || (op == BSI_SUM_ONLY && !has_found)) {
-    set_err("bsi: batch must hold ebM, nbits slices and the optional foundSet; bad op");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  hipStream_t s = c->stream;
-  CHK(c->bsi_sums.ensure(8 * kBsiSumAll));  // zeroed by the plan kernel
-  c->bsi_nbits = nbits;
-  int mode = op;
-  if (op != BSI_SUM_ONLY) {
-    const int mm = bsi_minmax(op, start, end, min_value, max_value);
-    if (mm == 1) mode = BSI_ALL;
-    if (mm == 2) mode = -1;  // empty result
-  }
-  const size_t ub = std::min<size_t>(kMaxKeys, std::max<size_t>(B->n_ctr, 1));
-  OutCtx oc;
-  CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser, &oc, op == BSI_SUM_ONLY));
-  c->pending_src = {id};
-  const uint32_t need = mode == -1 ? 0xFFFFFFFFu : (op == BSI_SUM_ONLY ? (uint32_t)(nbits + 1) : 0u);
-  BsiScratch sc{};
-  if (mode >= 0 && mode <= BSI_RANGE) {
-    CHK(c->bsi_defer.ensure(4 * (ub + 1)));
-    CHK(c->bsi_cnts.ensure((size_t)4 * 128 * 4 * ub));  // count rows (< 128) x 4 units
-    CHK(c->bsi_kin.ensure((size_t)16 * 34 * ub));
-    CHK(c->bsi_table.ensure((size_t)16 * 34 * ub));
-    sc = BsiScratch{c->bsi_defer.as<uint32_t>(), c->bsi_cnts.as<int>(), c->bsi_kin.p, ub, c->bsi_table.p};
-    if (!c->bsi_claims.p) {  // zeroed once here, then by k_bsi_types after every query that claims
-      CHK(c->bsi_claims.ensure(4 * kBsiClaimWords));
-      HIPCHK(hipMemsetAsync(c->bsi_claims.p, 0, 4 * kBsiClaimWords, s));
-    }
-    sc.claims = c->bsi_claims.as<unsigned int>();
-  }
-  WideArgs wa{};
-  wa.desc = B->desc.as<CDesc>();
-  wa.bm = B->bm.as<uint32_t>();
-  wa.payload = B->payload.as<uint8_t>();
-  c->mark(0);
-  Task* tasks = c->tasks.as<Task>();
-  uint32_t* nt = c->ntasks.as<uint32_t>();
-  if (sc.defer && bsi_reg_path(mode, nbits)) {
-    // The task list (keys where ebM has a container) and the input table depend on the batch
-    // only: planned once per batch, kept with it (RoaringBitmapSliceIndex queries on one index,
-    // BSI/:482-513, re-walk the same keys every time).
-    if (!B->bsi_cached) {
-      CHK(B->bsi_tasks.ensure(sizeof(Task) * kMaxKeys));
-      CHK(B->bsi_nt.ensure(64));
-      CHK(B->bsi_table.ensure((size_t)16 * 34 * ub));
-      launch_plan_bsi(s, B->key_off.as<uint32_t>(), B->bm.as<uint32_t>(), need, c->by_key.as<Task>(),
-                      c->flag.as<uint8_t>(), c->wg_count.as<uint32_t>(), nullptr, nullptr, nullptr, nullptr);
-      launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(),
-                     B->bsi_tasks.as<Task>(), B->bsi_nt.as<uint32_t>());
-      launch_bsi_table(s, B->bsi_tasks.as<Task>(), B->bsi_nt.as<uint32_t>(), wa, B->bsi_table.p, ub);
-      B->bsi_cached = true;
-    }
-    tasks = B->bsi_tasks.as<Task>();
-    nt = B->bsi_nt.as<uint32_t>();
-    sc.table = B->bsi_table.p;
-    sc.table_ready = true;
-    sc.zlb = c->zlb;
-    sc.ztile = c->ztile;
-    sc.zsums = c->bsi_sums.as<unsigned long long>();
-    sc.nt_src = nt;
-    sc.nt_dst = c->ntasks.as<uint32_t>();
-  } else {
-    launch_plan_bsi(s, B->key_off.as<uint32_t>(), B->bm.as<uint32_t>(), need, c->by_key.as<Task>(),
-                    c->flag.as<uint8_t>(), c->wg_count.as<uint32_t>(), c->zlb, c->ztile,
-                    c->bsi_sums.as<unsigned long long>(), sc.defer);
-    launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(), tasks, nt);
-  }
-  c->mark(1);
-  BsiArgs p{mode < 0 ? BSI_EQ : mode, nbits, has_found, (uint32_t)start, (uint32_t)end};
-  launch_bsi(s, grid_for(ub, 65536), tasks, nt, wa, p, oc, want_sum ? c->bsi_sums.as<unsigned long long>() : nullptr,
-             sc.defer ? &sc : nullptr, want_sum ? c->bsi_sums_dst : nullptr);
-  c->mark(2);
-  if (op == BSI_SUM_ONLY) {
-    c->last = 0;
-  } else {
-    defer_place(c);
-  }
-  c->mark(3);
-  HIPCHK(hipGetLastError());
-  return RBG_OK;
-}
-
-// ---------------------------------------------------------------------------
-// Buffer-package BSI: BitSliceIndexBase.compare (bsi/src/main/java/org/roaringbitmap/bsi/buffer/
-// BitSliceIndexBase.java, BBSI/ below), bsi.hip's k_bsi_buf
-// ---------------------------------------------------------------------------
-
-// horizontal_or's chain order for owenGreatEqual (BBSI/:266, RB/buffer/BufferFastAggregation.java:187-235):
-// the queue holds one container pointer per orInput bitmap (in orInputs order, top down,
-// BBSI/:247-264); each walks the keys where its orInput has a container, ordered by key, then
-// larger cardinality first (RB/buffer/MutableRoaringArray.java:476-481), ties in the heap's
-// order.  The poll order of a key's pointers is that key's chain: ord[t * kOwenOrder] = n,
-// then the n orInput indices.
-static int owen_order(Ctx* c, int M, uint32_t nt) {
-  hipStream_t s = c->stream;
-  std::vector<uint32_t> keys(nt);
-  std::vector<int32_t> tb((size_t)nt * 32 * 4);  // TB: kind, card, src, pad
-  if (nt) {
-    HIPCHK(hipMemcpyAsync(keys.data(), c->owen_keys.p, 4 * (size_t)nt, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipMemcpyAsync(tb.data(), c->owen_tb.p, 16 * 32 * (size_t)nt, hipMemcpyDeviceToHost, s));
-  }
-  HIPCHK(hipStreamSynchronize(s));
-  std::vector<std::vector<uint32_t>> lists(M);  // tasks (ascending keys) where orInput j has a container
-  for (uint32_t t = 0; t < nt; t++)
-    for (int j = 0; j < M; j++)
-      if (tb[((size_t)t * 32 + j) * 4 + 1] > 0) lists[j].push_back(t);
-  std::vector<uint8_t> ord((size_t)std::max<uint32_t>(nt, 1) * kOwenOrder, 0);
-  auto ptr = [&](uint32_t j, uint32_t i) {
-    const uint32_t t = lists[j][i];
-    return HPtr{j, i, keys[t], (uint32_t)tb[((size_t)t * 32 + j) * 4 + 1], t};
-  };
-  auto push = [&](const HPtr& x) {
-    uint8_t* o = ord.data() + (size_t)x.pos * kOwenOrder;
-    o[1 + o[0]++] = (uint8_t)x.bm;
-  };
-  JHeap pq;
-  for (int j = 0; j < M; j++)
-    if (!lists[j].empty()) pq.add(ptr((uint32_t)j, 0));
-  auto advance_add = [&](const HPtr& x) {
-    if (x.i + 1 < lists[x.bm].size()) pq.add(ptr(x.bm, x.i + 1));
-  };
-  while (!pq.q.empty()) {
-    const HPtr x1 = pq.poll();
-    push(x1);
-    if (pq.q.empty() || pq.q[0].key != x1.key) {
-      advance_add(x1);
-      continue;
-    }
-    const HPtr x2 = pq.poll();
-    push(x2);
-    while (!pq.q.empty() && pq.q[0].key == x1.key) {
-      const HPtr x = pq.poll();
-      push(x);
-      if (x.i + 1 < lists[x.bm].size()) pq.add(ptr(x.bm, x.i + 1));
-      else if (pq.q.empty()) break;
-    }
-    advance_add(x1);
-    advance_add(x2);
-  }
-  CHK(c->owen_ord.ensure(ord.size()));
-  HIPCHK(hipMemcpyAsync(c->owen_ord.p, ord.data(), ord.size(), hipMemcpyHostToDevice, s));
-  HIPCHK(hipStreamSynchronize(s));  // `ord` is a stack vector
-  return RBG_OK;
-}
-
-// op: RBG_BSI_* (compare) or RBG_BSI_RANGE_NEQ_DIRECT; the batch is [ebM, bA[0..nbits-1], foundSet?].
-// Synchronous: the big-run arena is checked after the op (with_big_runs).
-static int ctx_bsi_buffer(Ctx* c, int32_t id, int op, int nbits, int has_found, int32_t start, int32_t end,
-                          int32_t min_value, int32_t max_value) {
-  Batch* B;
-  CHK(get_batch(c, id, &B));
-  if (!B->key_major || B->packed || nbits < 0 || nbits + 2 > kBsiMaxInputs ||
-      B->n_bm != (size_t)(1 + nbits + (has_found ? 1 : 0)) || op < 0 || op > RBG_BSI_RANGE_NEQ_DIRECT) {
-    set_err("bsi: batch must hold ebM, nbits slices and the optional foundSet; bad op");
-    return RBG_ERR_ILLEGAL_ARGUMENT;
-  }
-  hipStream_t s = c->stream;
-  // compareUsingMinMax (BBSI/:455-519, as the heap one) and the op's own dispatch (BBSI/:422-453)
-  int mode, nb_eff = nbits, found_eff = has_found;
-  if (op == RBG_BSI_RANGE_NEQ_DIRECT || op == BSI_NEQ) {
-    const int mm = op == BSI_NEQ ? bsi_minmax(BSI_NEQ, start, end, min_value, max_value) : 0;
-    if (mm) {
-      mode = mm == 1 ? BSI_ALL : -1;
-    } else {  // andNot(ebM, rangeEQ(foundSet, value)); rangeEQ checks compareUsingMinMax(EQ) itself
-      const int em = bsi_minmax(BSI_EQ, start, 0, min_value, max_value);
-      mode = BSI_NEQ;
-      if (em == 2) {  // andNot(ebM, empty): ebM's clone
-        mode = BSI_ALL;
-        found_eff = 0;
-      } else if (em == 1) {  // andNot(ebM, ebM.clone() or and(ebM, foundSet)): the chain without slices
-        nb_eff = 0;
-      }
-    }
-  } else {
-    const int mm = bsi_minmax(op, start, end, min_value, max_value);
-    mode = mm == 1 ? BSI_ALL : mm == 2 ? -1 : op;
-  }
-  // owenGreatEqual (BBSI/:245-264): beGtrThan = start - 1, leastSignifZero =
-  // Long.numberOfTrailingZeros(~beGtrThan) (64 when start - 1 == -1: no orInput at all)
-  uint32_t zeros = 0, ones = 0;
-  if (mode == BSI_GE || mode == BSI_RANGE) {
-    const int32_t b = (int32_t)((uint32_t)start - 1u);
-    const uint32_t nbx = ~(uint32_t)b;
-    const int lsz = nbx == 0 ? 64 : __builtin_ctz(nbx);
-    for (int w = nbits - 1; w >= lsz; w--) {
-      if ((((uint32_t)b >> w) & 1u) == 0) zeros |= 1u << w;
-      else ones |= 1u << w;
-    }
-  }
-  const int M = __builtin_popcount(zeros);
-  const size_t ub = std::min<size_t>(kMaxKeys, std::max<size_t>(B->n_ctr, 1));
-  return with_big_runs(c, true, "bsi", [&](const BigRuns& big) -> int {
-    OutCtx oc;
-    CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser + big.cap, &oc, false));
-    c->pending_src = {id};
-    const uint32_t need = mode == -1 ? 0xFFFFFFFFu : 0xFFFFFFFEu;  // every key of any input
-    c->mark(0);
-    launch_plan_bsi(s, B->key_off.as<uint32_t>(), B->bm.as<uint32_t>(), need, c->by_key.as<Task>(),
-                    c->flag.as<uint8_t>(), c->wg_count.as<uint32_t>(), c->zlb, c->ztile, nullptr, nullptr);
-    launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(), c->tasks.as<Task>(),
-                   c->ntasks.as<uint32_t>());
-    c->mark(1);
-    WideArgs wa{};
-    wa.desc = B->desc.as<CDesc>();
-    wa.bm = B->bm.as<uint32_t>();
-    wa.payload = B->payload.as<uint8_t>();
-    BsiArgs p{};
-    p.op = mode < 0 ? BSI_EQ : mode;
-    p.nbits = nb_eff;
-    p.has_found = found_eff;
-    p.pred0 = (uint32_t)start;
-    p.pred1 = (uint32_t)end;
-    p.buffer = 1;
-    p.found_input = nbits + 1;
-    p.owen_zeros = zeros;
-    p.owen_ones = ones;
-    p.big = big;
-    const int grid = grid_for(ub, 65536);
-    if (mode >= 0 && M >= 3) {  // the chain order needs horizontal_or's queue: every orInput's type first
-      CHK(c->owen_tb.ensure((size_t)16 * 32 * ub));
-      CHK(c->owen_keys.ensure(4 * ub));
-      p.owen_tb = c->owen_tb.p;
-      p.task_keys = c->owen_keys.as<uint32_t>();
-      launch_bsi_owen_pre(s, grid, c->tasks.as<Task>(), c->ntasks.as<uint32_t>(), wa, p);
-      HIPCHK(hipGetLastError());
-      uint32_t nt = 0;
-      HIPCHK(hipMemcpyAsync(&nt, c->ntasks.p, 4, hipMemcpyDeviceToHost, s));
-      HIPCHK(hipStreamSynchronize(s));
-      CHK(owen_order(c, M, nt));
-      p.owen_order = c->owen_ord.as<uint8_t>();
-    }
-    if (mode >= 0) launch_bsi_buf(s, grid, c->tasks.as<Task>(), c->ntasks.as<uint32_t>(), wa, p, oc);
-    return op_end(c);
-  });
-}
-
-// (sum, count) of the last BSI call: k_bsi_sum_final's Java longs, read back
-static int ctx_bsi_sums(Ctx* c, int64_t* out2) {
-  if (!c->bsi_sums.p) {
-    out2[0] = out2[1] = 0;
-    return RBG_OK;
-  }
-  HIPCHK(hipMemcpyAsync(out2, c->bsi_sums.as<uint64_t>() + kBsiSumOut, 16, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return RBG_OK;
-}
-
 static int ctx_info(Ctx* c, ResultInfo* ri) {
   if (c->last == 1) CHK(ensure_placed(c));
   HIPCHK(hipMemcpyAsync(ri, c->info.p, sizeof(ResultInfo), hipMemcpyDeviceToHost, c->stream));
@@ -3178,7 +1787,7 @@ static uint8_t* out_alloc(size_t n) {
   return (uint8_t*)p;
 }
 
-static int ctx_fetch(Ctx* c, rbg_buffer* out) {
+int ctx_fetch(Ctx* c, rbg_buffer* out) {
   if (c->last != 1) {
     set_err("no serialized result pending");
     return RBG_ERR_ILLEGAL_ARGUMENT;
@@ -3214,7 +1823,7 @@ static int emit_empty(rbg_buffer* out) { return emit_bytes(kEmpty, sizeof(kEmpty
 
 // Download bitmaps [i0, i1) of a batch as portable serialized bytes: their slots are
 // gathered on the device into one buffer (one D2H copy), the headers built here.
-static int ctx_batch_fetch_range(Ctx* c, int32_t batch, size_t i0, size_t i1, rbg_buffer* outs) {
+int ctx_batch_fetch_range(Ctx* c, int32_t batch, size_t i0, size_t i1, rbg_buffer* outs) {
   Batch* b;
   CHK(get_batch(c, batch, &b));
   if (i0 > i1 || i1 > b->n_bm || (i1 > i0 && !outs)) return RBG_ERR_ILLEGAL_ARGUMENT;
@@ -3815,7 +2424,7 @@ struct TLCtx {
 };
 static thread_local TLCtx tl;
 
-static int tl_ctx(Ctx** out) {
+int tl_ctx(Ctx** out) {
   int dev;
   {
     std::lock_guard<std::mutex> g(g_dev_mu);
@@ -3833,57 +2442,12 @@ static int tl_ctx(Ctx** out) {
   return RBG_OK;
 }
 
-// Scope of a one-shot call: the calling thread's context and the batches the call made, dropped on
-// exit.  load / load_separate register their batches before they return, adopt those an op made.
-struct OneShot {
-  Ctx* c = nullptr;
-  BatchGuard g{nullptr, {}};
-  int open() {
-    CHK(tl_ctx(&c));
-    g.c = c;
-    return RBG_OK;
-  }
-  void adopt(int32_t id) { g.ids.push_back(id); }
-  int load(const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* id, bool pack_arrays = false,
-           bool key_major = true) {
-    CHK(ctx_load_impl(c, bufs, lens, n, key_major, id, pack_arrays));
-    adopt(*id);
-    return RBG_OK;
-  }
-  int load_separate(const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* ids) {
-    CHK(ctx_load_separate(c, bufs, lens, n, ids));
-    g.ids.insert(g.ids.end(), ids, ids + n);
-    return RBG_OK;
-  }
-};
-
-// the batch [ebM, slices, foundSet?] of a one-shot BSI call
-static int bsi_load(OneShot& os, const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* lens,
-                    size_t nbits, const uint8_t* found, size_t found_len, int32_t* id) {
-  if (!ebm || (nbits && (!slices || !lens)) || nbits + 2 > (size_t)kBsiMaxInputs) return RBG_ERR_ILLEGAL_ARGUMENT;
-  std::vector<const uint8_t*> bufs{ebm};
-  std::vector<size_t> ls{ebm_len};
-  for (size_t i = 0; i < nbits; i++) {
-    bufs.push_back(slices[i]);
-    ls.push_back(lens[i]);
-  }
-  if (found) {
-    bufs.push_back(found);
-    ls.push_back(found_len);
-  }
-  return os.load(bufs.data(), ls.data(), bufs.size(), id);
-}
-
 }  // namespace rbg
 
 using namespace rbg;
 
-struct rbg_ctx {
-  Ctx c;
-};
-
 // entry of a session call: a null handle is an illegal argument; else the context, entered
-static int session(rbg_ctx* ctx, Ctx** c) {
+int rbg::session(rbg_ctx* ctx, Ctx** c) {
   if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
   *c = &ctx->c;
   return enter(*c);
@@ -4581,265 +3145,6 @@ int rbg_synth_key_bytes(int kind, uint64_t seed, size_t n, uint64_t* out) {
     }
   }
   return RBG_OK;
-}
-int rbg_ctx_bsi(rbg_ctx* ctx, int32_t batch, int op, int nbits, int has_found, int32_t start, int32_t end,
-                int32_t min_value, int32_t max_value, int want_sum) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  return ctx_bsi(c, batch, op, nbits, has_found, start, end, min_value, max_value, want_sum);
-}
-int rbg_ctx_bsi_sums(rbg_ctx* ctx, int64_t* out2) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (!out2) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_sums(c, out2);
-}
-int rbg_ctx_bsi_sums_target(rbg_ctx* ctx, void* dst2) {
-  if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
-  ctx->c.bsi_sums_dst = dst2;
-  return RBG_OK;
-}
-int rbg_ctx_bsi_sums_device(rbg_ctx* ctx, void* dst2) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (!dst2 || !c->bsi_sums.p) return RBG_ERR_ILLEGAL_ARGUMENT;
-  launch_bsi_sums_out(c->stream, c->bsi_sums.as<unsigned long long>(), dst2);
-  HIPCHK(hipGetLastError());
-  return RBG_OK;
-}
-int rbg_bsi_compare(int op, int32_t start, int32_t end, const uint8_t* ebm, size_t ebm_len,
-                    const uint8_t* const* slices, const size_t* slice_lens, size_t nbits, int32_t min_value,
-                    int32_t max_value, const uint8_t* found, size_t found_len, rbg_buffer* out) {
-  if (!out || op < 0 || op > BSI_RANGE) return RBG_ERR_ILLEGAL_ARGUMENT;
-  OneShot os;
-  CHK(os.open());
-  Ctx* c = os.c;
-  int32_t id;
-  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
-  CHK(ctx_bsi(c, id, op, (int)nbits, found ? 1 : 0, start, end, min_value, max_value, 0));
-  return ctx_fetch(c, out);
-}
-int rbg_bsi_compare_buffer(int op, int32_t start, int32_t end, const uint8_t* ebm, size_t ebm_len,
-                           const uint8_t* const* slices, const size_t* slice_lens, size_t nbits, int32_t min_value,
-                           int32_t max_value, const uint8_t* found, size_t found_len, rbg_buffer* out) {
-  if (!out || op < 0 || op > RBG_BSI_RANGE_NEQ_DIRECT) return RBG_ERR_ILLEGAL_ARGUMENT;
-  OneShot os;
-  CHK(os.open());
-  Ctx* c = os.c;
-  int32_t id;
-  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
-  CHK(ctx_bsi_buffer(c, id, op, (int)nbits, found ? 1 : 0, start, end, min_value, max_value));
-  return ctx_fetch(c, out);
-}
-int rbg_ctx_bsi_buffer(rbg_ctx* ctx, int32_t batch, int op, int nbits, int has_found, int32_t start, int32_t end,
-                       int32_t min_value, int32_t max_value) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  return ctx_bsi_buffer(c, batch, op, nbits, has_found, start, end, min_value, max_value);
-}
-int rbg_bsi_sum(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
-                size_t nbits, const uint8_t* found, size_t found_len, int64_t* out2) {
-  if (!out2) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (!found) {  // BSI/:582: null foundSet -> (0, 0)
-    out2[0] = out2[1] = 0;
-    return RBG_OK;
-  }
-  OneShot os;
-  CHK(os.open());
-  Ctx* c = os.c;
-  int32_t id;
-  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, nbits, found, found_len, &id));
-  CHK(ctx_bsi(c, id, BSI_SUM_ONLY, (int)nbits, 1, 0, 0, 0, 0, 1));
-  return ctx_bsi_sums(c, out2);
-}
-
-/* ---- a BSI from (column, value) pairs (bsibuild.hip) and its values back (bsival.hip) ---- */
-
-int rbg_ctx_bsi_from_columns(rbg_ctx* ctx, const uint32_t* columns, const int32_t* values, size_t n, int run_optimize,
-                             int32_t* batch, int32_t* out3) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (!batch || !out3 || (n && (!columns || !values))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_from_columns_host(c, columns, values, n, run_optimize != 0, batch, out3);
-}
-
-int rbg_ctx_bsi_from_columns_device(rbg_ctx* ctx, const void* columns_dev, const void* values_dev, size_t n,
-                                    int run_optimize, int32_t* batch, int32_t* out3) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (!batch || !out3 || (n && (!columns_dev || !values_dev))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_from_columns(c, reinterpret_cast<const uint32_t*>(columns_dev),
-                              reinterpret_cast<const int32_t*>(values_dev), n, run_optimize != 0, batch, out3);
-}
-
-int rbg_ctx_bsi_get_values(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const uint32_t* columns, size_t n,
-                           int64_t* out) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (nbits < 0 || (n && (!columns || !out))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (n == 0) return RBG_OK;
-  return ctx_bsi_get_values_host(c, batch, nbits, has_found, columns, n, out);
-}
-
-int rbg_ctx_bsi_get_values_device(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const void* columns_dev,
-                                  size_t n, void* out_dev) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (nbits < 0 || (n && (!columns_dev || !out_dev))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (n == 0) return RBG_OK;
-  return ctx_bsi_get_values(c, batch, nbits, has_found, reinterpret_cast<const uint32_t*>(columns_dev), n,
-                            reinterpret_cast<long long*>(out_dev));
-}
-
-int rbg_ctx_bsi_to_pairs(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int columns64, int values64,
-                         void* columns_out, void* values_out, uint64_t* n_out) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (nbits < 0) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_to_pairs_host(c, batch, nbits, has_found, columns64 != 0, values64 != 0, columns_out, values_out,
-                               n_out);
-}
-
-int rbg_ctx_bsi_to_pairs_device(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int columns64, int values64,
-                                void* columns_dev, void* values_dev, uint64_t* n_out) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (nbits < 0) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_to_pairs(c, batch, nbits, has_found, columns64 != 0, values64 != 0, columns_dev, values_dev, n_out);
-}
-
-int rbg_bsi_from_columns(const uint32_t* columns, const int32_t* values, size_t n, int run_optimize, rbg_buffer* outs,
-                         int32_t* out3) {
-  if (!outs || !out3 || (n && (!columns || !values))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  OneShot os;
-  CHK(os.open());
-  Ctx* c = os.c;
-  int32_t id;
-  CHK(ctx_bsi_from_columns_host(c, columns, values, n, run_optimize != 0, &id, out3));
-  os.adopt(id);
-  return ctx_batch_fetch_range(c, id, 0, 1 + (size_t)out3[0], outs);
-}
-
-int rbg_ctx_bsi_add(rbg_ctx* ctx, int32_t batch_a, int nbits_a, int32_t batch_b, int nbits_b, int32_t min_a,
-                    int32_t max_a, int32_t* out_batch, int32_t* out3) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (!out_batch || !out3) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_add(c, batch_a, nbits_a, batch_b, nbits_b, min_a, max_a, out_batch, out3);
-}
-
-int rbg_bsi_add(const uint8_t* ebm_a, size_t ebm_a_len, const uint8_t* const* slices_a, const size_t* lens_a, int na,
-                int32_t min_a, int32_t max_a, const uint8_t* ebm_b, size_t ebm_b_len, const uint8_t* const* slices_b,
-                const size_t* lens_b, int nb, rbg_buffer* outs, int32_t* out3) {
-  if (!outs || !out3 || na < 0 || nb < 0 || na > 32 || nb > 32) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (!ebm_a || !ebm_b || (na && (!slices_a || !lens_a)) || (nb && (!slices_b || !lens_b))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  OneShot os;
-  CHK(os.open());
-  Ctx* c = os.c;
-  int32_t ia, ib, id;
-  CHK(bsi_load(os, ebm_a, ebm_a_len, slices_a, lens_a, (size_t)na, nullptr, 0, &ia));
-  CHK(bsi_load(os, ebm_b, ebm_b_len, slices_b, lens_b, (size_t)nb, nullptr, 0, &ib));
-  CHK(ctx_bsi_add(c, ia, na, ib, nb, min_a, max_a, &id, out3));
-  os.adopt(id);
-  return ctx_batch_fetch_range(c, id, 0, 1 + (size_t)out3[0], outs);
-}
-
-/* ---- RoaringBitmapSliceIndex.setValues (BSI/:349-357; bsiset.hip) ---- */
-
-int rbg_ctx_bsi_set_values(rbg_ctx* ctx, int32_t batch, int nbits, int32_t min_value, int32_t max_value,
-                           const uint32_t* columns, const int32_t* values, size_t n, int32_t* out_batch, int32_t* out3) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (!out_batch || !out3 || (n && (!columns || !values))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_set_values_host(c, batch, nbits, min_value, max_value, columns, values, n, out_batch, out3);
-}
-
-int rbg_ctx_bsi_set_values_device(rbg_ctx* ctx, int32_t batch, int nbits, int32_t min_value, int32_t max_value,
-                                  const void* columns_dev, const void* values_dev, size_t n, int32_t* out_batch,
-                                  int32_t* out3) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (!out_batch || !out3 || (n && (!columns_dev || !values_dev))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_set_values(c, batch, nbits, min_value, max_value, reinterpret_cast<const uint32_t*>(columns_dev),
-                            reinterpret_cast<const int32_t*>(values_dev), n, out_batch, out3);
-}
-
-int rbg_bsi_set_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
-                       int nbits, int32_t min_value, int32_t max_value, const uint32_t* columns, const int32_t* values,
-                       size_t n, rbg_buffer* outs, int32_t* out3) {
-  if (!outs || !out3 || nbits < 0 || nbits > 32 || (n && (!columns || !values))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (!ebm || (nbits && (!slices || !slice_lens))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  OneShot os;
-  CHK(os.open());
-  Ctx* c = os.c;
-  int32_t ia, id;
-  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, (size_t)nbits, nullptr, 0, &ia));
-  CHK(ctx_bsi_set_values_host(c, ia, nbits, min_value, max_value, columns, values, n, &id, out3));
-  os.adopt(id);
-  return ctx_batch_fetch_range(c, id, 0, 1 + (size_t)out3[0], outs);
-}
-
-/* ---- BitSliceIndexBase.parallelIn (BBSI/:611-639; bsiin.hip) ---- */
-
-int rbg_ctx_bsi_in(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, const int32_t* values, size_t n_values,
-                   int parallelism, int32_t* out_batch) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (!out_batch || (n_values && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_in(c, batch, nbits, has_found != 0, values, n_values, parallelism, out_batch);
-}
-
-int rbg_bsi_in(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens, int nbits,
-               const uint8_t* found, size_t found_len, const int32_t* values, size_t n_values, int parallelism,
-               rbg_buffer* out) {
-  if (!out || nbits < 0 || nbits > 32 || parallelism < 1 || (n_values && !values)) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (!ebm || (nbits && (!slices || !slice_lens))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  OneShot os;
-  CHK(os.open());
-  Ctx* c = os.c;
-  int32_t id, res;
-  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, (size_t)nbits, found, found_len, &id));
-  CHK(ctx_bsi_in(c, id, nbits, found ? 1 : 0, values, n_values, parallelism, &res));
-  os.adopt(res);
-  return ctx_batch_fetch_range(c, res, 0, 1, out);
-}
-
-/* ---- BitSliceIndexBase.parallelTransposeWithCount (BBSI/:551-597; bsitr.hip) ---- */
-
-int rbg_ctx_bsi_transpose(rbg_ctx* ctx, int32_t batch, int nbits, int has_found, int parallelism, int32_t* out_batch,
-                          int32_t* out3) {
-  Ctx* c;
-  CHK(session(ctx, &c));
-  if (!out_batch || !out3) return RBG_ERR_ILLEGAL_ARGUMENT;
-  return ctx_bsi_transpose(c, batch, nbits, has_found != 0, parallelism, out_batch, out3);
-}
-
-int rbg_bsi_transpose(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
-                      int nbits, const uint8_t* found, size_t found_len, int parallelism, rbg_buffer* outs,
-                      int32_t* out3) {
-  if (!outs || !out3 || nbits < 0 || nbits > 32 || parallelism < 1) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (!ebm || (nbits && (!slices || !slice_lens))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  OneShot os;
-  CHK(os.open());
-  Ctx* c = os.c;
-  int32_t id, res;
-  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, (size_t)nbits, found, found_len, &id));
-  CHK(ctx_bsi_transpose(c, id, nbits, found ? 1 : 0, parallelism, &res, out3));
-  os.adopt(res);
-  return ctx_batch_fetch_range(c, res, 0, 1 + (size_t)out3[0], outs);
-}
-
-int rbg_bsi_get_values(const uint8_t* ebm, size_t ebm_len, const uint8_t* const* slices, const size_t* slice_lens,
-                       int nbits, const uint32_t* columns, size_t n, int64_t* out) {
-  if (nbits < 0 || (n && (!columns || !out))) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (!ebm || (nbits && (!slices || !slice_lens)) || nbits + 2 > kBsiMaxInputs) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (n == 0) return RBG_OK;
-  OneShot os;
-  CHK(os.open());
-  Ctx* c = os.c;
-  int32_t id;
-  CHK(bsi_load(os, ebm, ebm_len, slices, slice_lens, (size_t)nbits, nullptr, 0, &id));
-  return ctx_bsi_get_values_host(c, id, nbits, 0, columns, n, out);
 }
 int rbg_ctx_pair_bytes(rbg_ctx* ctx, int32_t batch, int64_t* out2) {
   if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;

@@ -12,7 +12,7 @@ mkdir -p $OUT
 for s in $(cd $C && ls *.hip); do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -x hip -c $C/$s -o $OUT/$s.o &
 done
-for s in engine.cpp format.cpp; do
+for s in $(cd $C && ls *.cpp); do
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -c $C/$s -o $OUT/$s.o &
 done
 for j in $(jobs -p); do wait $j || { echo "compile failed"; exit 1; }; done

@@ -1,4 +1,4 @@
-"""Many-key parity of the bit-sliced index compare / sum kernels (csrc/bsi.hip, engine.cpp ctx_bsi and
+"""Many-key parity of the bit-sliced index compare / sum kernels (csrc/bsi.hip, engine_bsi.cpp ctx_bsi and
 ctx_bsi_buffer), byte for byte against the oracle (tests/_bsi.py).
 
 The small-shape files (test_gpu_bsi.py, test_gpu_bsi_buffer.py) mix every container kind on 16 keys or fewer,
