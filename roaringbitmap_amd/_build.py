@@ -15,7 +15,35 @@ LIB = os.path.join(LIBDIR, "libroaring_mi355x.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels.hip", "pairwise.hip", "wide.hip", "pq.hip", "synth.hip", "bsi.hip", "runopt.hip", "ornot.hip", "rangemut.hip", "addoffset.hip", "decode.hip", "rankdir.hip", "build.hip", "expand.hip", "bsibuild.hip", "bsival.hip", "bsiadd.hip", "bsiset.hip", "bsiin.hip", "bsitr.hip", "engine.cpp", "engine_bsi.cpp", "format.cpp"]
+SOURCES = [
+    "kernels.hip",
+    "pairwise.hip",
+    "wide.hip",
+    "pq.hip",
+    "synth.hip",
+    "bsi.hip",
+    "runopt.hip",
+    "ornot.hip",
+    "rangemut.hip",
+    "addoffset.hip",
+    "decode.hip",
+    "rankdir.hip",
+    "build.hip",
+    "expand.hip",
+    "bsibuild.hip",
+    "bsival.hip",
+    "bsiadd.hip",
+    "bsiset.hip",
+    "bsiin.hip",
+    "bsitr.hip",
+    "engine.cpp",
+    "engine_load.cpp",
+    "engine_wide.cpp",
+    "engine_bsi.cpp",
+    "engine_synth.cpp",
+    "engine_api.cpp",
+    "format.cpp",
+]
 HEADERS = ["device.hpp", "kernels.hpp", "format.hpp", "wave.hpp", "vb.hpp", "bsival.hpp", "engine.hpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result"]

@@ -1,12 +1,19 @@
-// Private to the engine's two host translation units -- engine.cpp (the core: contexts, upload and decode,
-// result output, the roaring op pipelines, the synthetic workloads, the C ABI) and engine_bsi.cpp (every
-// bit-sliced-index pipeline and its entry points): the macros, constants and types both use, and the core
-// functions the BSI unit calls.  Everything declared here is defined once, in engine.cpp.
+// The one internal interface of the engine's host translation units: the macros, constants and types they
+// share, and every function that one unit defines and another calls, grouped by the defining unit.
+//   engine.cpp        the core: contexts and pools, batches, result output and fetch, pairwise and single-bitmap ops
+//   engine_load.cpp   upload of serialized bitmaps and their decode on the device
+//   engine_wide.cpp   the aggregations (FastAggregation's dispatch, the horizontal and priority-queue forms)
+//   engine_bsi.cpp    every bit-sliced-index pipeline and its entry points
+//   engine_synth.cpp  the bench workload synthesizers
+//   engine_api.cpp    the exported C ABI
+// What is declared here is defined once; what no other unit calls stays static in its own.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
+#include <cstdlib>
+#include <cstring>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -209,25 +216,85 @@ struct BatchGuard {
   }
 };
 
-// The core functions the BSI unit (or OneShot, below) calls (engine.cpp).
+static inline uint64_t round16(uint64_t x) { return (x + 15) & ~15ULL; }
+
+// engine.cpp, contexts, pools and batches.
 void dbg(hipStream_t s, const char* what);
+int ctx_init(Ctx* c, int device);
+int enter(Ctx* c);
 int tl_ctx(Ctx** out);
+int find_batch(Ctx* c, int32_t id, Batch** out);
 int get_batch(Ctx* c, int32_t id, Batch** out);
 int32_t new_batch(Ctx* c);
+int batch_host_index(Ctx* c, Batch* b);
 void pool_put(Ctx* c, DevBuf& b);
 int pool_take(Ctx* c, DevBuf& dst, size_t bytes);
+size_t pool_clear(Ctx* c);
 int pinned_ensure(Ctx* c, size_t bytes);
 int upload_words(Ctx* c, void* dst, const void* src, size_t n);
-int ctx_empty_bitmap(Ctx* c, int32_t* out_id);
-int ctx_load_impl(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, bool key_major, int32_t* out_id,
-                  bool pack_arrays = false);
-int ctx_load_separate(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* ids);
+int ctx_profile(Ctx* c, int max_ops, bool compute_only);
+// engine.cpp, the output of an op: its bracket, placement, serialization, the result's facts and bytes.
 int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* oc, bool card_only);
 void defer_place(Ctx* c);
+int ensure_placed(Ctx* c);
 int grid_for(size_t tasks, size_t cap = 4096);
 int op_end(Ctx* c);
+int ctx_serialize(Ctx* c);
+int ctx_info(Ctx* c, ResultInfo* ri);
+uint8_t* out_alloc(size_t n);
 int ctx_fetch(Ctx* c, rbg_buffer* out);
 int ctx_batch_fetch_range(Ctx* c, int32_t batch, size_t i0, size_t i1, rbg_buffer* outs);
+int ctx_fetch_shard_device(Ctx* c, int64_t total_containers, int has_run, int64_t payload_base, void* desc_dst,
+                           void* offsets_dst, void* runflag_dst, void* payload_dst);
+// engine.cpp, the ops.
+int ctx_empty_bitmap(Ctx* c, int32_t* out_id);
+int ctx_point(Ctx* c, int op, int32_t batch, size_t i, const uint32_t* q_dev, size_t n, long long* out_dev);
+int ctx_point_host(Ctx* c, int op, int32_t batch, size_t i, const uint32_t* q, size_t n, int64_t* out);
+int ctx_to_values(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t count, bool out64, void* out_dev,
+                  uint64_t* n_out);
+int ctx_to_values_host(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t count, uint32_t* out,
+                       uint64_t* n_out);
+int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32_t* out_id);
+int ctx_from_values_host(Ctx* c, const uint32_t* v, size_t n, bool run_opt, int32_t* out_id);
+int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, bool card_only, int key_lo = 0,
+                 int key_hi = kMaxKeys);
+int ctx_ornot(Ctx* c, int32_t ia, size_t ma, int32_t ib, size_t mb, int64_t range_end, int flags);
+int check_range(int64_t start, int64_t end);
+int ctx_range_mut(Ctx* c, int op, int32_t ia, size_t ma, int64_t start, int64_t end, bool buf);
+int ctx_remove_run_compression(Ctx* c, int32_t ia, size_t ma);
+int ctx_limit(Ctx* c, int32_t ia, size_t ma, int cut_key, int leftover);
+int ctx_add_offset(Ctx* c, int32_t ia, size_t ma, int64_t offset);
+int ctx_batch_card(Ctx* c, int32_t id);
+int ctx_run_optimize(Ctx* c, int32_t id, int32_t* out_id, uint8_t* answers);
+int ctx_select_range(Ctx* c, int32_t id, int64_t start, int64_t end, int32_t* out_id, bool buf = false);
+// engine_load.cpp.
+int ctx_load_impl(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, bool key_major, int32_t* out_id,
+                  bool pack_arrays = false);
+int ctx_load(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* out_id,
+             bool pack_arrays = false);
+int ctx_load_separate(Ctx* c, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* ids);
+// engine_wide.cpp.  host_card_out / host_card_valid: a cardinality the host knows without a launch; null unless
+// card_only.
+bool wide_reads_packed(int op, size_t n);
+int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const int32_t* ids, bool card_only,
+             int* host_card_out, bool* host_card_valid, int32_t start_override = -1);
+// engine_synth.cpp.
+int synth_c2(Ctx* c, int kind, uint64_t seed, int32_t* out_id);
+int synth_c3(Ctx* c, int kind, uint64_t seed, size_t n, int key_lo, int key_hi, int32_t* out_id);
+int synth_c4(Ctx* c, uint64_t seed, size_t n_pairs, int32_t* out_id);
+int synth_c5(Ctx* c, uint64_t seed, size_t rows, int key_lo, int key_hi, int32_t* out_id);
+
+// a malloc'd copy of n bytes as a result buffer (rbg_free releases it); static like with_big_runs below: the
+// core's batch fetch and the entry points each inline it
+static int emit_bytes(const uint8_t* src, size_t n, rbg_buffer* out) {
+  uint8_t* p = (uint8_t*)std::malloc(n ? n : 1);
+  if (!p) return RBG_ERR_OUT_OF_MEMORY;
+  if (n) std::memcpy(p, src, n);
+  out->data = p;
+  out->len = n;
+  return RBG_OK;
+}
+static int emit_host(const std::vector<uint8_t>& v, rbg_buffer* out) { return emit_bytes(v.data(), v.size(), out); }
 
 // An op whose kernel may keep run containers above 2047 runs reserves them in the context's big-run
 // arena (Ctx::big; big_ctl = {bytes reserved, overflow flag}).  pass(BigRuns) enqueues one complete
@@ -255,7 +322,7 @@ static int with_big_runs(Ctx* c, bool use_arena, const char* what, Pass&& pass) 
   }
 }
 
-// The replay of java.util.PriorityQueue over container pointers: horizontal_order (engine.cpp) and owen_order
+// The replay of java.util.PriorityQueue over container pointers: horizontal_order (engine_wide.cpp) and owen_order
 // (engine_bsi.cpp).
 namespace {
 struct HPtr {
@@ -326,11 +393,13 @@ struct OneShot {
 
 }  // namespace rbg
 
-struct rbg_ctx {
+// (hidden: a std:: template the compiler instantiates over the handle, unique_ptr<rbg_ctx>'s destructor, stays
+// out of the library's dynamic symbols, whichever unit it lands in)
+struct __attribute__((visibility("hidden"))) rbg_ctx {
   rbg::Ctx c;
 };
 
 namespace rbg {
-// entry of a session call: a null handle is an illegal argument; else the context, entered
+// engine_api.cpp.  Entry of a session call: a null handle is an illegal argument; else the context, entered
 int session(rbg_ctx* ctx, Ctx** c);
 }  // namespace rbg

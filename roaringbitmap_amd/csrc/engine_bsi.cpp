@@ -1,7 +1,7 @@
 // The bit-sliced-index (BSI) host code of the MI355X Roaring engine: the batch builders and read-outs
 // (from pairs, add, setValues, values back, IN-list, transpose), the compare and sum pipelines of both
-// packages, and their exported entry points.  What it needs from the core (engine.cpp) is declared in
-// engine.hpp.
+// packages, and their exported entry points.  What it needs from the core (engine.cpp) and the loads
+// (engine_load.cpp) is declared in engine.hpp.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>

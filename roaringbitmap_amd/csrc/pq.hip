@@ -4,7 +4,7 @@
 // The reference pairs whole bitmaps in a java.util.PriorityQueue ordered by
 // getLongSizeInBytes, so every step's operands depend on the sizes of earlier
 // intermediate results over all keys.  The queue lives in device memory: the host
-// adds the inputs and plans the first step (engine.cpp: ctx_pq), then enqueues N - 1
+// adds the inputs and plans the first step (engine_wide.cpp: ctx_pq), then enqueues N - 1
 // launches of k_pq_step.  Each combines the two nodes its step record names -- an input
 // bitmap (leaf) or an intermediate (temp) -- over every union key (one workgroup per
 // key), keeps the per-key result in the output temp and adds its getSizeInBytes to the

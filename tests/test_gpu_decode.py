@@ -179,7 +179,7 @@ def test_packed_decode_for_wide_ops(gpu):
         e.release(b)
 
 
-# every wide op that reads the packed layout (wide_reads_packed, csrc/engine.cpp; `and` above 10 inputs)
+# every wide op that reads the packed layout (wide_reads_packed, csrc/engine_wide.cpp; `and` above 10 inputs)
 PACKED_WIDE_OPS = ["or", "xor", "and", "workshy_and", "parallel_or", "parallel_xor", "buffer_or_mutable",
                    "horizontal_or", "horizontal_xor", "priorityqueue_or", "priorityqueue_xor"]
 
