@@ -7,6 +7,8 @@ and every compute call returns RBG_ERR_DEVICE when no gfx950 device is present.
 import ctypes
 import os
 
+import numpy as np
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("RBG_LIB") or os.path.join(HERE, "lib", "libroaring_mi355x.so")
 
@@ -31,155 +33,135 @@ RBG_ORNOT_INPLACE, RBG_ORNOT_BUFFER = 1, 2
 RMUT_OP = {"add": 0, "remove": 1, "flip": 2, "add_inplace": 3}  # rbg_range_mut (| RBG_RMUT_BUFFER: MutableRoaringBitmap's)
 RBG_RMUT_BUFFER = 4
 PQ_OP = {"rank": 0, "select": 1, "contains": 2, "next": 3, "prev": 4}  # rbg_point_query (RBG_PQ_*)
+OPERATIONS = ("EQ", "NEQ", "LE", "LT", "GE", "GT", "RANGE")  # BitmapSliceIndex.Operation order (rbg_bsi_compare)
+
+
+def bsi_op(op):
+    """the code of a BSI compare operation given by name (OPERATIONS) or as the code itself"""
+    return OPERATIONS.index(op) if isinstance(op, str) else int(op)
 
 
 class rbg_buffer(ctypes.Structure):
     _fields_ = [("data", ctypes.POINTER(ctypes.c_uint8)), ("len", ctypes.c_size_t)]
 
 
-EXPORTED = [
-    "rbg_pairwise", "rbg_pairwise_card", "rbg_wide", "rbg_wide_card", "rbg_range_op", "rbg_ctx_select_range", "rbg_batch_and_card", "rbg_free",
-    "rbg_set_devices", "rbg_last_error", "rbg_version", "rbg_trim", "rbg_pool_evictions", "rbg_from_values", "rbg_run_optimize",
-    "rbg_to_values", "rbg_inspect", "rbg_ctx_create", "rbg_ctx_destroy", "rbg_ctx_stream", "rbg_ctx_sync",
-    "rbg_ctx_load", "rbg_ctx_synth", "rbg_ctx_release", "rbg_ctx_batch_stats", "rbg_ctx_batch_fetch",
-    "rbg_ctx_pairwise", "rbg_ctx_pairwise_serialized", "rbg_ctx_pairwise_range", "rbg_ctx_pairwise_card", "rbg_ctx_wide", "rbg_ctx_wide_card",
-    "rbg_ctx_batch_and_card", "rbg_ctx_card", "rbg_ctx_cards", "rbg_ctx_result_stats", "rbg_ctx_fetch",
-    "rbg_ctx_fetch_shard", "rbg_ctx_profile", "rbg_ctx_profile_compute", "rbg_ctx_profile_read", "rbg_ctx_profile_bytes", "rbg_ctx_serialize", "rbg_ctx_wide_start",
-    "rbg_ctx_batch_counts", "rbg_synth_key_bytes", "rbg_ctx_pair_bytes",
-    "rbg_bsi_compare", "rbg_bsi_sum", "rbg_ctx_bsi", "rbg_ctx_bsi_sums", "rbg_ctx_bsi_sums_device", "rbg_ctx_bsi_sums_target", "rbg_ctx_batch_minmax",
-    "rbg_ctx_run_optimize", "rbg_run_optimize_many", "rbg_ctx_batch_fetch_range",
-    "rbg_ctx_fetch_shard_device", "rbg_bsi_compare_buffer", "rbg_ctx_bsi_buffer",
-    "rbg_ctx_result_layout_device", "rbg_ctx_fetch_shard_device_dyn", "rbg_pairwise_inplace",
-    "rbg_ctx_load_separate", "rbg_ctx_load_packed", "rbg_ornot", "rbg_ctx_ornot", "rbg_range_mut", "rbg_ctx_range_mut", "rbg_add_offset", "rbg_ctx_add_offset", "rbg_select_range", "rbg_remove_run_compression", "rbg_limit", "rbg_bitmap_of_range",
-    "rbg_point_query", "rbg_ctx_point_query", "rbg_ctx_point_query_device",
-    "rbg_build_values", "rbg_expand_values", "rbg_ctx_from_values", "rbg_ctx_from_values_device",
-    "rbg_ctx_to_values", "rbg_ctx_to_values_device",
-    "rbg_bsi_from_columns", "rbg_bsi_get_values", "rbg_ctx_bsi_from_columns", "rbg_ctx_bsi_from_columns_device",
-    "rbg_ctx_bsi_get_values", "rbg_ctx_bsi_get_values_device", "rbg_ctx_bsi_to_pairs", "rbg_ctx_bsi_to_pairs_device",
-    "rbg_bsi_add", "rbg_ctx_bsi_add", "rbg_bsi_in", "rbg_ctx_bsi_in", "rbg_bsi_transpose", "rbg_ctx_bsi_transpose",
-    "rbg_bsi_set_values", "rbg_ctx_bsi_set_values", "rbg_ctx_bsi_set_values_device",
-]
+# the header's C types, named once: int, int32_t, int64_t, uint64_t, size_t; void*, const uint8_t*, rbg_buffer*;
+# const uint8_t* const*, size_t* and the pointers to the fixed-width integers
+P = ctypes.POINTER
+ci, i32, i64, u64, sz = ctypes.c_int, ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64, ctypes.c_size_t
+vp, u8p, buf = ctypes.c_void_p, ctypes.c_char_p, P(rbg_buffer)
+strs, szp, u32p, i32p, i64p, u64p = P(ctypes.c_char_p), P(sz), P(ctypes.c_uint32), P(i32), P(i64), P(u64)
+
+
+# Every entry point of include/roaring_mi355x.h, in the header's order: name -> (restype, argtypes).  lib()
+# applies it.  An entry point without argtypes would take a Python int as a C int, silently.
+_BSI_COMPARE = [ci, i32, i32, u8p, sz, strs, szp, sz, i32, i32, u8p, sz, buf]
+SIGNATURES = {
+    "rbg_range_op": (ci, [ci, strs, szp, sz, i64, i64, buf]),
+    "rbg_ornot": (ci, [u8p, sz, u8p, sz, i64, ci, buf]),
+    "rbg_range_mut": (ci, [ci, u8p, sz, i64, i64, buf]),
+    "rbg_add_offset": (ci, [u8p, sz, i64, buf]),
+    "rbg_remove_run_compression": (ci, [u8p, sz, buf]),
+    "rbg_limit": (ci, [u8p, sz, i32, buf]),
+    "rbg_point_query": (ci, [ci, u8p, sz, u32p, sz, i64p]),
+    "rbg_build_values": (ci, [u32p, sz, ci, buf]),
+    "rbg_expand_values": (ci, [u8p, sz, buf]),
+    "rbg_bitmap_of_range": (ci, [i64, i64, buf]),
+    "rbg_select_range": (ci, [u8p, sz, i64, i64, ci, buf]),
+    "rbg_pairwise": (ci, [ci, u8p, sz, u8p, sz, buf]),
+    "rbg_pairwise_inplace": (ci, [ci, u8p, sz, u8p, sz, ci, buf]),
+    "rbg_pairwise_card": (ci, [ci, u8p, sz, u8p, sz, i32p]),
+    "rbg_wide": (ci, [ci, strs, szp, i32p, sz, buf]),
+    "rbg_wide_card": (ci, [ci, strs, szp, sz, i32p]),
+    "rbg_batch_and_card": (ci, [sz, strs, szp, strs, szp, i32p]),
+    "rbg_bsi_compare": (ci, _BSI_COMPARE),
+    "rbg_bsi_compare_buffer": (ci, _BSI_COMPARE),
+    "rbg_bsi_sum": (ci, [u8p, sz, strs, szp, sz, u8p, sz, i64p]),
+    "rbg_bsi_from_columns": (ci, [u32p, i32p, sz, ci, vp, i32p]),
+    "rbg_bsi_get_values": (ci, [u8p, sz, strs, szp, ci, u32p, sz, i64p]),
+    "rbg_bsi_add": (ci, [u8p, sz, strs, szp, ci, i32, i32, u8p, sz, strs, szp, ci, vp, i32p]),
+    "rbg_bsi_set_values": (ci, [u8p, sz, strs, szp, ci, i32, i32, u32p, i32p, sz, vp, i32p]),
+    "rbg_bsi_in": (ci, [u8p, sz, strs, szp, ci, u8p, sz, i32p, sz, ci, buf]),
+    "rbg_bsi_transpose": (ci, [u8p, sz, strs, szp, ci, u8p, sz, ci, vp, i32p]),
+    "rbg_free": (None, [buf]),
+    "rbg_set_devices": (ci, [u64]),
+    "rbg_last_error": (u8p, []),
+    "rbg_version": (ci, []),
+    "rbg_trim": (None, []),
+    "rbg_pool_evictions": (u64, []),
+    "rbg_from_values": (ci, [u32p, sz, ci, buf]),
+    "rbg_run_optimize": (ci, [u8p, sz, buf]),
+    "rbg_to_values": (ci, [u8p, sz, buf]),
+    "rbg_inspect": (ci, [u8p, sz, szp, i64p, i64p]),
+    "rbg_ctx_create": (ci, [ci, P(vp)]),
+    "rbg_ctx_destroy": (None, [vp]),
+    "rbg_ctx_stream": (vp, [vp]),
+    "rbg_ctx_sync": (ci, [vp]),
+    "rbg_ctx_profile": (ci, [vp, ci]),
+    "rbg_ctx_profile_compute": (ci, [vp, ci]),
+    "rbg_ctx_profile_read": (ci, [vp, P(ctypes.c_double), P(ci)]),
+    "rbg_ctx_profile_bytes": (ci, [vp, i64p]),
+    "rbg_ctx_load_separate": (ci, [vp, strs, szp, sz, i32p]),
+    "rbg_ctx_load": (ci, [vp, strs, szp, sz, i32p]),
+    "rbg_ctx_load_packed": (ci, [vp, strs, szp, sz, i32p]),
+    "rbg_ctx_synth": (ci, [vp, ci, u64, sz, ci, ci, i32p]),
+    "rbg_ctx_release": (ci, [vp, i32]),
+    "rbg_ctx_select_range": (ci, [vp, i32, i64, i64, i32p]),
+    "rbg_ctx_run_optimize": (ci, [vp, i32, i32p, P(ctypes.c_uint8)]),
+    "rbg_run_optimize_many": (ci, [vp, szp, sz, vp, P(ctypes.c_uint8)]),
+    "rbg_ctx_batch_minmax": (ci, [vp, i32, i32p]),
+    "rbg_ctx_batch_stats": (ci, [vp, i32, i64p]),
+    "rbg_ctx_batch_fetch": (ci, [vp, i32, sz, buf]),
+    "rbg_ctx_batch_fetch_range": (ci, [vp, i32, sz, sz, vp]),
+    "rbg_ctx_pairwise": (ci, [vp, ci, i32, sz, i32, sz]),
+    "rbg_ctx_pairwise_serialized": (ci, [vp, ci, i32, sz, i32, sz]),
+    "rbg_ctx_pairwise_range": (ci, [vp, ci, i32, sz, i32, sz, ci, ci]),
+    "rbg_ctx_ornot": (ci, [vp, i32, sz, i32, sz, i64, ci]),
+    "rbg_ctx_range_mut": (ci, [vp, ci, i32, sz, i64, i64]),
+    "rbg_ctx_add_offset": (ci, [vp, i32, sz, i64]),
+    "rbg_ctx_pairwise_card": (ci, [vp, ci, i32, sz, i32, sz]),
+    "rbg_ctx_wide": (ci, [vp, ci, i32, ci, ci, i32p]),
+    "rbg_ctx_wide_card": (ci, [vp, ci, i32, ci, ci]),
+    "rbg_ctx_wide_start": (ci, [vp, ci, i32, ci, ci, i32p, i32]),
+    "rbg_ctx_pair_bytes": (ci, [vp, i32, i64p]),
+    "rbg_ctx_bsi": (ci, [vp, i32, ci, ci, ci, i32, i32, i32, i32, ci]),
+    "rbg_ctx_bsi_sums": (ci, [vp, i64p]),
+    "rbg_ctx_bsi_buffer": (ci, [vp, i32, ci, ci, ci, i32, i32, i32, i32]),
+    "rbg_ctx_bsi_sums_device": (ci, [vp, vp]),
+    "rbg_ctx_bsi_sums_target": (ci, [vp, vp]),
+    "rbg_ctx_point_query": (ci, [vp, ci, i32, sz, u32p, sz, i64p]),
+    "rbg_ctx_point_query_device": (ci, [vp, ci, i32, sz, vp, sz, vp]),
+    "rbg_ctx_from_values": (ci, [vp, u32p, sz, ci, i32p]),
+    "rbg_ctx_from_values_device": (ci, [vp, vp, sz, ci, i32p]),
+    "rbg_ctx_to_values": (ci, [vp, i32, sz, u64, u64, u32p, u64p]),
+    "rbg_ctx_to_values_device": (ci, [vp, i32, sz, u64, u64, ci, vp, u64p]),
+    "rbg_ctx_bsi_from_columns": (ci, [vp, u32p, i32p, sz, ci, i32p, i32p]),
+    "rbg_ctx_bsi_from_columns_device": (ci, [vp, vp, vp, sz, ci, i32p, i32p]),
+    "rbg_ctx_bsi_add": (ci, [vp, i32, ci, i32, ci, i32, i32, i32p, i32p]),
+    "rbg_ctx_bsi_set_values": (ci, [vp, i32, ci, i32, i32, u32p, i32p, sz, i32p, i32p]),
+    "rbg_ctx_bsi_set_values_device": (ci, [vp, i32, ci, i32, i32, vp, vp, sz, i32p, i32p]),
+    "rbg_ctx_bsi_in": (ci, [vp, i32, ci, ci, i32p, sz, ci, i32p]),
+    "rbg_ctx_bsi_transpose": (ci, [vp, i32, ci, ci, ci, i32p, i32p]),
+    "rbg_ctx_bsi_get_values": (ci, [vp, i32, ci, ci, u32p, sz, i64p]),
+    "rbg_ctx_bsi_get_values_device": (ci, [vp, i32, ci, ci, vp, sz, vp]),
+    "rbg_ctx_bsi_to_pairs": (ci, [vp, i32, ci, ci, ci, ci, vp, vp, u64p]),
+    "rbg_ctx_bsi_to_pairs_device": (ci, [vp, i32, ci, ci, ci, ci, vp, vp, u64p]),
+    "rbg_ctx_batch_counts": (ci, [vp, i32, u32p, sz]),
+    "rbg_synth_key_bytes": (ci, [ci, u64, sz, u64p]),
+    "rbg_ctx_batch_and_card": (ci, [vp, i32]),
+    "rbg_ctx_card": (ci, [vp, i32p]),
+    "rbg_ctx_cards": (ci, [vp, i32p, sz]),
+    "rbg_ctx_result_stats": (ci, [vp, i64p]),
+    "rbg_ctx_serialize": (ci, [vp]),
+    "rbg_ctx_fetch": (ci, [vp, buf]),
+    "rbg_ctx_fetch_shard": (ci, [vp, i64, ci, i64, i64, buf, buf, buf]),
+    "rbg_ctx_fetch_shard_device": (ci, [vp, i64, ci, i64, vp, vp, vp, vp]),
+    "rbg_ctx_result_layout_device": (ci, [vp, vp]),
+    "rbg_ctx_fetch_shard_device_dyn": (ci, [vp, vp, ci, ci, vp, vp]),
+}
+EXPORTED = list(SIGNATURES)  # the names alone
 
 _lib = None
-
-
-def _declare(L):
-    P = ctypes.POINTER
-    u8p = ctypes.c_char_p
-    sz = ctypes.c_size_t
-    buf = P(rbg_buffer)
-    i32 = ctypes.c_int32
-    vp = ctypes.c_void_p
-    L.rbg_pairwise.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, buf]
-    L.rbg_trim.argtypes = []
-    L.rbg_trim.restype = None
-    L.rbg_pool_evictions.argtypes = []
-    L.rbg_pool_evictions.restype = ctypes.c_uint64
-    L.rbg_pairwise_card.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, P(i32)]
-    L.rbg_pairwise_inplace.argtypes = [ctypes.c_int, u8p, sz, u8p, sz, ctypes.c_int, buf]
-    L.rbg_wide.argtypes = [ctypes.c_int, P(ctypes.c_char_p), P(sz), P(i32), sz, buf]
-    L.rbg_wide_card.argtypes = [ctypes.c_int, P(ctypes.c_char_p), P(sz), sz, P(i32)]
-    L.rbg_range_op.argtypes = [ctypes.c_int, P(ctypes.c_char_p), P(sz), sz, ctypes.c_int64, ctypes.c_int64, buf]
-    L.rbg_ornot.argtypes = [u8p, sz, u8p, sz, ctypes.c_int64, ctypes.c_int, buf]
-    L.rbg_ctx_ornot.argtypes = [vp, i32, sz, i32, sz, ctypes.c_int64, ctypes.c_int]
-    L.rbg_range_mut.argtypes = [ctypes.c_int, u8p, sz, ctypes.c_int64, ctypes.c_int64, buf]
-    L.rbg_ctx_range_mut.argtypes = [vp, ctypes.c_int, i32, sz, ctypes.c_int64, ctypes.c_int64]
-    L.rbg_add_offset.argtypes = [u8p, sz, ctypes.c_int64, buf]
-    L.rbg_remove_run_compression.argtypes = [u8p, sz, buf]
-    L.rbg_limit.argtypes = [u8p, sz, ctypes.c_int32, buf]
-    L.rbg_bitmap_of_range.argtypes = [ctypes.c_int64, ctypes.c_int64, buf]
-    L.rbg_point_query.argtypes = [ctypes.c_int, u8p, sz, P(ctypes.c_uint32), sz, P(ctypes.c_int64)]
-    L.rbg_ctx_point_query.argtypes = [vp, ctypes.c_int, i32, sz, P(ctypes.c_uint32), sz, P(ctypes.c_int64)]
-    L.rbg_ctx_point_query_device.argtypes = [vp, ctypes.c_int, i32, sz, vp, sz, vp]
-    u64 = ctypes.c_uint64
-    L.rbg_build_values.argtypes = [P(ctypes.c_uint32), sz, ctypes.c_int, buf]
-    L.rbg_expand_values.argtypes = [u8p, sz, buf]
-    L.rbg_ctx_from_values.argtypes = [vp, P(ctypes.c_uint32), sz, ctypes.c_int, P(i32)]
-    L.rbg_ctx_from_values_device.argtypes = [vp, vp, sz, ctypes.c_int, P(i32)]
-    L.rbg_ctx_to_values.argtypes = [vp, i32, sz, u64, u64, P(ctypes.c_uint32), P(u64)]
-    L.rbg_ctx_to_values_device.argtypes = [vp, i32, sz, u64, u64, ctypes.c_int, vp, P(u64)]
-    u32p, i32p, i64p, ci = P(ctypes.c_uint32), P(i32), P(ctypes.c_int64), ctypes.c_int
-    L.rbg_bsi_from_columns.argtypes = [u32p, i32p, sz, ci, vp, i32p]
-    L.rbg_bsi_get_values.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, u32p, sz, i64p]
-    L.rbg_ctx_bsi_from_columns.argtypes = [vp, u32p, i32p, sz, ci, i32p, i32p]
-    L.rbg_ctx_bsi_from_columns_device.argtypes = [vp, vp, vp, sz, ci, i32p, i32p]
-    L.rbg_ctx_bsi_get_values.argtypes = [vp, i32, ci, ci, u32p, sz, i64p]
-    L.rbg_ctx_bsi_get_values_device.argtypes = [vp, i32, ci, ci, vp, sz, vp]
-    L.rbg_ctx_bsi_to_pairs.argtypes = [vp, i32, ci, ci, ci, ci, vp, vp, P(u64)]
-    L.rbg_ctx_bsi_to_pairs_device.argtypes = [vp, i32, ci, ci, ci, ci, vp, vp, P(u64)]
-    L.rbg_bsi_add.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, i32, i32,
-                              u8p, sz, P(ctypes.c_char_p), P(sz), ci, vp, i32p]
-    L.rbg_ctx_bsi_add.argtypes = [vp, i32, ci, i32, ci, i32, i32, i32p, i32p]
-    L.rbg_bsi_set_values.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, i32, i32, u32p, i32p, sz, vp, i32p]
-    L.rbg_ctx_bsi_set_values.argtypes = [vp, i32, ci, i32, i32, u32p, i32p, sz, i32p, i32p]
-    L.rbg_ctx_bsi_set_values_device.argtypes = [vp, i32, ci, i32, i32, vp, vp, sz, i32p, i32p]
-    L.rbg_bsi_in.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, u8p, sz, i32p, sz, ci, buf]
-    L.rbg_ctx_bsi_in.argtypes = [vp, i32, ci, ci, i32p, sz, ci, i32p]
-    L.rbg_bsi_transpose.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), ci, u8p, sz, ci, vp, i32p]
-    L.rbg_ctx_bsi_transpose.argtypes = [vp, i32, ci, ci, ci, i32p, i32p]
-    L.rbg_select_range.argtypes = [u8p, sz, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, buf]
-    L.rbg_ctx_add_offset.argtypes = [vp, i32, sz, ctypes.c_int64]
-    L.rbg_ctx_select_range.argtypes = [vp, i32, ctypes.c_int64, ctypes.c_int64, P(i32)]
-    L.rbg_batch_and_card.argtypes = [sz, P(ctypes.c_char_p), P(sz), P(ctypes.c_char_p), P(sz), P(i32)]
-    L.rbg_free.argtypes = [buf]
-    L.rbg_free.restype = None
-    L.rbg_set_devices.argtypes = [ctypes.c_uint64]
-    L.rbg_last_error.restype = ctypes.c_char_p
-    L.rbg_from_values.argtypes = [P(ctypes.c_uint32), sz, ctypes.c_int, buf]
-    L.rbg_run_optimize.argtypes = [u8p, sz, buf]
-    L.rbg_to_values.argtypes = [u8p, sz, buf]
-    L.rbg_inspect.argtypes = [u8p, sz, P(sz), P(ctypes.c_int64), P(ctypes.c_int64)]
-    L.rbg_ctx_create.argtypes = [ctypes.c_int, P(vp)]
-    L.rbg_ctx_destroy.argtypes = [vp]
-    L.rbg_ctx_destroy.restype = None
-    L.rbg_ctx_stream.argtypes = [vp]
-    L.rbg_ctx_stream.restype = vp
-    L.rbg_ctx_sync.argtypes = [vp]
-    L.rbg_ctx_load.argtypes = [vp, P(ctypes.c_char_p), P(sz), sz, P(i32)]
-    L.rbg_ctx_load_separate.argtypes = [vp, P(ctypes.c_char_p), P(sz), sz, P(i32)]
-    L.rbg_ctx_load_packed.argtypes = [vp, P(ctypes.c_char_p), P(sz), sz, P(i32)]
-    L.rbg_ctx_synth.argtypes = [vp, ctypes.c_int, ctypes.c_uint64, sz, ctypes.c_int, ctypes.c_int, P(i32)]
-    L.rbg_ctx_release.argtypes = [vp, i32]
-    L.rbg_ctx_batch_stats.argtypes = [vp, i32, P(ctypes.c_int64)]
-    L.rbg_ctx_batch_fetch.argtypes = [vp, i32, sz, buf]
-    L.rbg_ctx_batch_fetch_range.argtypes = [vp, i32, sz, sz, vp]
-    L.rbg_ctx_pairwise.argtypes = [vp, ctypes.c_int, i32, sz, i32, sz]
-    L.rbg_ctx_pairwise_serialized.argtypes = [vp, ctypes.c_int, i32, sz, i32, sz]
-    L.rbg_ctx_pairwise_range.argtypes = [vp, ctypes.c_int, i32, sz, i32, sz, ctypes.c_int, ctypes.c_int]
-    L.rbg_ctx_pairwise_card.argtypes = [vp, ctypes.c_int, i32, sz, i32, sz]
-    L.rbg_ctx_wide.argtypes = [vp, ctypes.c_int, i32, ctypes.c_int, ctypes.c_int, P(i32)]
-    L.rbg_ctx_wide_card.argtypes = [vp, ctypes.c_int, i32, ctypes.c_int, ctypes.c_int]
-    L.rbg_ctx_wide_start.argtypes = [vp, ctypes.c_int, i32, ctypes.c_int, ctypes.c_int, P(i32), i32]
-    L.rbg_ctx_batch_counts.argtypes = [vp, i32, P(ctypes.c_uint32), sz]
-    L.rbg_bsi_compare.argtypes = [ctypes.c_int, i32, i32, u8p, sz, P(ctypes.c_char_p), P(sz), sz, i32, i32, u8p, sz,
-                                  buf]
-    L.rbg_bsi_compare_buffer.argtypes = L.rbg_bsi_compare.argtypes
-    L.rbg_ctx_bsi_buffer.argtypes = [vp, i32, ctypes.c_int, ctypes.c_int, ctypes.c_int, i32, i32, i32, i32]
-    L.rbg_bsi_sum.argtypes = [u8p, sz, P(ctypes.c_char_p), P(sz), sz, u8p, sz, P(ctypes.c_int64)]
-    L.rbg_ctx_bsi.argtypes = [vp, i32, ctypes.c_int, ctypes.c_int, ctypes.c_int, i32, i32, i32, i32, ctypes.c_int]
-    L.rbg_ctx_bsi_sums.argtypes = [vp, P(ctypes.c_int64)]
-    L.rbg_ctx_bsi_sums_device.argtypes = [vp, vp]
-    L.rbg_ctx_bsi_sums_target.argtypes = [vp, vp]
-    L.rbg_ctx_batch_minmax.argtypes = [vp, i32, P(i32)]
-    L.rbg_ctx_run_optimize.argtypes = [vp, i32, P(i32), P(ctypes.c_uint8)]
-    L.rbg_run_optimize_many.argtypes = [vp, P(sz), sz, vp, P(ctypes.c_uint8)]
-    L.rbg_ctx_pair_bytes.argtypes = [vp, i32, P(ctypes.c_int64)]
-    L.rbg_synth_key_bytes.argtypes = [ctypes.c_int, ctypes.c_uint64, sz, P(ctypes.c_uint64)]
-    L.rbg_ctx_batch_and_card.argtypes = [vp, i32]
-    L.rbg_ctx_serialize.argtypes = [vp]
-    L.rbg_ctx_card.argtypes = [vp, P(i32)]
-    L.rbg_ctx_cards.argtypes = [vp, P(i32), sz]
-    L.rbg_ctx_result_stats.argtypes = [vp, P(ctypes.c_int64)]
-    L.rbg_ctx_fetch.argtypes = [vp, buf]
-    L.rbg_ctx_profile.argtypes = [vp, ctypes.c_int]
-    L.rbg_ctx_profile_compute.argtypes = [vp, ctypes.c_int]
-    L.rbg_ctx_profile_read.argtypes = [vp, P(ctypes.c_double), P(ctypes.c_int)]
-    L.rbg_ctx_profile_bytes.argtypes = [vp, P(ctypes.c_int64)]
-    L.rbg_ctx_fetch_shard_device.argtypes = [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, vp, vp, vp, vp]
-    L.rbg_ctx_result_layout_device.argtypes = [vp, vp]
-    L.rbg_ctx_fetch_shard_device_dyn.argtypes = [vp, vp, ctypes.c_int, ctypes.c_int, vp, vp]
-    L.rbg_ctx_fetch_shard.argtypes = [vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int64, ctypes.c_int64, buf, buf,
-                                      buf]
 
 
 def lib():
@@ -191,7 +173,9 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the engine has no CPU fallback)")
         L = ctypes.CDLL(LIB_PATH)
-        _declare(L)
+        for name, (restype, argtypes) in SIGNATURES.items():
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -248,3 +232,47 @@ def buf_array(bufs):
     arr = (ctypes.c_char_p * max(n, 1))(*bufs)
     lens = (ctypes.c_size_t * max(n, 1))(*[len(b) for b in bufs])
     return arr, lens
+
+
+def call_bytes(f, *args) -> bytes:
+    """f(*args, &buffer) -> the bytes the library left in the buffer, which is freed"""
+    b = rbg_buffer()
+    check(f(*args, ctypes.byref(b)))
+    return take(b)
+
+
+def ids_array(ids):
+    """the identity ids of a wide op's inputs as int32[], or a null pointer"""
+    return None if ids is None else (ctypes.c_int32 * len(ids))(*ids)
+
+
+def is_torch(x) -> bool:
+    """a torch tensor or dtype, told without importing torch"""
+    return type(x).__module__.split(".")[0] == "torch"
+
+
+def as_u32(values) -> np.ndarray:
+    """values (Java ints or their unsigned patterns) as a flat contiguous uint32 array: the low 32 bits"""
+    return np.ascontiguousarray(np.asarray(values, dtype=np.int64).astype(np.uint32)).reshape(-1)
+
+
+def in_list(values) -> np.ndarray:
+    """the value list of an IN query as contiguous int32: Java ints, or their unsigned bit patterns"""
+    if isinstance(values, np.ndarray) and values.dtype in (np.int32, np.uint32):
+        return np.ascontiguousarray(values.reshape(-1)).view(np.int32)
+    v = np.asarray(values if isinstance(values, np.ndarray) else list(values), dtype=np.int64).reshape(-1)
+    if v.size and (v.min() < -(1 << 31) or v.max() >= 1 << 32):
+        raise IllegalArgumentException("the values of an IN list must fit 32 bits")
+    return np.ascontiguousarray(v.astype(np.uint32).view(np.int32))
+
+
+def pair_arrays(columns, values):
+    """(column, value) pairs as flat contiguous arrays of one length, uint32 columns and int32 values (Java's
+    non-negative ints): the host front of the calls that write pairs into a bit-sliced index"""
+    c = np.asarray(columns, dtype=np.int64).reshape(-1)
+    v = np.asarray(values, dtype=np.int64).reshape(-1)
+    if c.size != v.size:
+        raise IllegalArgumentException("columns and values differ in length")
+    if v.size and (v.min() < 0 or v.max() >= 1 << 31):
+        raise IllegalArgumentException("Values should be non-negative and below 2^31")
+    return np.ascontiguousarray(c.astype(np.uint32)), np.ascontiguousarray(v.astype(np.int32))

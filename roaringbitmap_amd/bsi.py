@@ -22,11 +22,19 @@ import os
 import numpy as np
 
 from . import _lib
-from ._lib import IllegalArgumentException, check, lib, take
-from .engine import _in_list
+from ._lib import OPERATIONS  # noqa: F401  (the operation names, importable from here as before)
+from ._lib import IllegalArgumentException, as_u32, call_bytes, check, lib, take
 from .roaring import RoaringBitmap, run_optimize_many
 
-OPERATIONS = ("EQ", "NEQ", "LE", "LT", "GE", "GT", "RANGE")  # BitmapSliceIndex.Operation order
+
+def _index_call(f, *args, ebm_cls=RoaringBitmap):
+    """f(*args, outs, out3): a one-shot call that makes an index -> (ebM, slices, minValue, maxValue) from the
+    1 + nbits buffers it wrote and out3 = {nbits, minValue, maxValue}"""
+    outs = (_lib.rbg_buffer * 34)()  # ebM and at most 33 slices (rbg_bsi_add's; the others write at most 33)
+    out3 = (ctypes.c_int32 * 3)()
+    check(f(*args, outs, out3))
+    return (ebm_cls(take(outs[0])), [RoaringBitmap(take(outs[1 + k])) for k in range(int(out3[0]))],
+            int(out3[1]), int(out3[2]))
 
 
 class RoaringBitmapSliceIndex:
@@ -53,15 +61,10 @@ class RoaringBitmapSliceIndex:
         if gpu:
             if values.size and int(values.max()) >= 1 << 31:
                 raise IllegalArgumentException("Values should be below 2^31")
-            c = np.ascontiguousarray(columns.reshape(-1).astype(np.uint32))
-            v = np.ascontiguousarray(values.reshape(-1).astype(np.int32))
-            outs = (_lib.rbg_buffer * 33)()
-            out3 = (ctypes.c_int32 * 3)()
-            check(lib().rbg_bsi_from_columns(c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                             v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size,
-                                             int(bool(run_optimize)), outs, out3))
-            bms = [RoaringBitmap(take(outs[k])) for k in range(1 + int(out3[0]))]
-            obj = cls(bms[0], bms[1:], int(out3[1]), int(out3[2]))
+            c, v = _lib.pair_arrays(columns, values)
+            obj = cls(*_index_call(lib().rbg_bsi_from_columns, c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                   v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size,
+                                   int(bool(run_optimize))))
             obj.runOptimized = bool(run_optimize)
             return obj
         mn = mx = 0
@@ -96,30 +99,17 @@ class RoaringBitmapSliceIndex:
         gpu=True: the one-shot device pass (rbg_bsi_set_values, csrc/bsiset.hip), which also takes an ebM
         with full run containers and new columns; it refuses a run container in a slice and one in ebM that
         is not full."""
-        c = np.asarray(columns, dtype=np.int64).reshape(-1)
-        v = np.asarray(values, dtype=np.int64).reshape(-1)
-        if c.size != v.size:
-            raise IllegalArgumentException("columns and values differ in length")
+        c, v = _lib.pair_arrays(columns, values)  # an empty list passes its range check
         if v.size == 0:
             raise IllegalArgumentException("setValues: no pair given")
-        if v.min() < 0 or v.max() >= 1 << 31:
-            raise IllegalArgumentException("Values should be non-negative and below 2^31")
         if len(self.bA) > 32:
             raise IllegalArgumentException("setValues: an index holds at most 32 slices")
-        c = np.ascontiguousarray(c.astype(np.uint32))
         ebm_cls = type(self.ebM)
         if gpu:
-            v = np.ascontiguousarray(v.astype(np.int32))
-            arr, lens = self._slices()
-            e = self.ebM.serialize()
-            outs = (_lib.rbg_buffer * 33)()
-            out3 = (ctypes.c_int32 * 3)()
-            check(lib().rbg_bsi_set_values(e, len(e), arr, lens, len(self.bA), self.minValue, self.maxValue,
-                                           c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                           v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size, outs, out3))
-            self.ebM = ebm_cls(take(outs[0]))
-            self.bA = [RoaringBitmap(take(outs[1 + k])) for k in range(int(out3[0]))]
-            self.minValue, self.maxValue = int(out3[1]), int(out3[2])
+            self.ebM, self.bA, self.minValue, self.maxValue = _index_call(
+                lib().rbg_bsi_set_values, *self._operands()[0], self.minValue, self.maxValue,
+                c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                c.size, ebm_cls=ebm_cls)
             return
         if any(b.container_stats()[2] > 0 for b in self.bA):
             raise IllegalArgumentException("setValues: a slice holds a run container")
@@ -192,17 +182,9 @@ class RoaringBitmapSliceIndex:
             return
         if len(self.bA) > 32 or len(otherBsi.bA) > 32:
             raise IllegalArgumentException("add: an index holds at most 32 slices")
-        arr_a, lens_a = self._slices()
-        arr_b, lens_b = otherBsi._slices()
-        ea, eb = self.ebM.serialize(), otherBsi.ebM.serialize()
-        outs = (_lib.rbg_buffer * 34)()
-        out3 = (ctypes.c_int32 * 3)()
-        check(lib().rbg_bsi_add(ea, len(ea), arr_a, lens_a, len(self.bA), self.minValue, self.maxValue,
-                                eb, len(eb), arr_b, lens_b, len(otherBsi.bA), outs, out3))
-        cls = type(self.ebM)
-        self.ebM = cls(take(outs[0]))
-        self.bA = [RoaringBitmap(take(outs[1 + k])) for k in range(int(out3[0]))]
-        self.minValue, self.maxValue = int(out3[1]), int(out3[2])
+        self.ebM, self.bA, self.minValue, self.maxValue = _index_call(
+            lib().rbg_bsi_add, *self._operands()[0], self.minValue, self.maxValue, *otherBsi._operands()[0],
+            ebm_cls=type(self.ebM))
 
     def _add_composed(self, otherBsi):
         """The reference's literal sequence (BSI/:71-95) over the device's pairwise ops: the in-place or of the
@@ -263,13 +245,11 @@ class RoaringBitmapSliceIndex:
         (getValue's exists == false).  The columns need not be sorted or distinct.  Host default: numpy
         membership tests against toArray() of ebM and of every slice; gpu=True: one batched lookup on the
         device (rbg_bsi_get_values, csrc/bsival.hip)."""
-        q = np.ascontiguousarray(np.asarray(columns, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        q = as_u32(columns)
         if gpu:
             out = np.empty(q.size, dtype=np.int64)
             if q.size:
-                arr, lens = self._slices()
-                e = self.ebM.serialize()
-                check(lib().rbg_bsi_get_values(e, len(e), arr, lens, len(self.bA),
+                check(lib().rbg_bsi_get_values(*self._operands()[0],
                                                q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), q.size,
                                                out.ctypes.data_as(ctypes.POINTER(ctypes.c_int64))))
             return out
@@ -305,28 +285,31 @@ class RoaringBitmapSliceIndex:
     def getLongCardinality(self):
         return self.ebM.getLongCardinality()
 
-    def _slices(self):
-        bufs = [b.serialize() for b in self.bA]
-        return _lib.buf_array(bufs)
-
-    def compare(self, operation, startOrValue, end=0, foundSet=None):
-        """BSI/:482-513 -> RoaringBitmap"""
-        op = OPERATIONS.index(operation) if isinstance(operation, str) else int(operation)
-        arr, lens = self._slices()
+    def _operands(self, foundSet=None):
+        """The argument blocks of the one-shot calls: (ebM, its length, the slices, their lengths, their count)
+        and (foundSet or null, its length)."""
+        arr, lens = _lib.buf_array([b.serialize() for b in self.bA])
         e = self.ebM.serialize()
         f = foundSet.serialize() if foundSet is not None else None
-        out = _lib.rbg_buffer()
-        check(lib().rbg_bsi_compare(op, int(startOrValue), int(end), e, len(e), arr, lens, len(self.bA),
-                                    self.minValue, self.maxValue, f, len(f) if f else 0, ctypes.byref(out)))
-        return RoaringBitmap(take(out))
+        return (e, len(e), arr, lens, len(self.bA)), (f, len(f) if f else 0)
+
+    _COMPARE = "rbg_bsi_compare"  # the class's compare circuit
+
+    def _compare(self, op, start, end, foundSet):
+        index, found = self._operands(foundSet)
+        return RoaringBitmap(call_bytes(getattr(lib(), self._COMPARE), op, int(start), int(end), *index,
+                                        self.minValue, self.maxValue, *found))
+
+    def compare(self, operation, startOrValue, end=0, foundSet=None):
+        """BSI/:482-513 -> RoaringBitmap; the buffer package's index: BBSI/:422-453 -> ImmutableRoaringBitmap (as
+        RoaringBitmap bytes)"""
+        return self._compare(_lib.bsi_op(operation), startOrValue, end, foundSet)
 
     def sum(self, foundSet):
         """BSI/:581-592 -> (sum, count) as Java longs"""
-        arr, lens = self._slices()
-        e = self.ebM.serialize()
-        f = foundSet.serialize() if foundSet is not None else None
+        index, found = self._operands(foundSet)
         out = (ctypes.c_int64 * 2)()
-        check(lib().rbg_bsi_sum(e, len(e), arr, lens, len(self.bA), f, len(f) if f else 0, out))
+        check(lib().rbg_bsi_sum(*index, *found, out))
         return int(out[0]), int(out[1])
 
 
@@ -336,6 +319,7 @@ class BitSliceIndexBase(RoaringBitmapSliceIndex):
     against ebM) and ImmutableRoaringBitmap's result types (csrc/bsi.hip, k_bsi_buf)."""
 
     RANGE_NEQ_DIRECT = 7  # RBG_BSI_RANGE_NEQ_DIRECT
+    _COMPARE = "rbg_bsi_compare_buffer"
 
     def add(self, otherBsi):
         """MutableBitSliceIndex.add (bsi/.../buffer/MutableBitSliceIndex.java:121-130, 201-262): for indexes
@@ -361,15 +345,10 @@ class BitSliceIndexBase(RoaringBitmapSliceIndex):
             raise IllegalArgumentException("parallelIn: parallelism must be positive")
         if len(self.bA) > 32:
             raise IllegalArgumentException("parallelIn: an index holds at most 32 slices")
-        v = _in_list(values)
-        arr, lens = self._slices()
-        e = self.ebM.serialize()
-        f = foundSet.serialize() if foundSet is not None else None
-        out = _lib.rbg_buffer()
-        check(lib().rbg_bsi_in(e, len(e), arr, lens, len(self.bA), f, len(f) if f else 0,
-                               v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), v.size, int(parallelism),
-                               ctypes.byref(out)))
-        return RoaringBitmap(take(out))
+        v = _lib.in_list(values)
+        index, found = self._operands(foundSet)
+        return RoaringBitmap(call_bytes(lib().rbg_bsi_in, *index, *found,
+                                        v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), v.size, int(parallelism)))
 
     def parallelTransposeWithCount(self, foundSet, parallelism, pool=None):
         """BBSI/:551-597 parallelTransposeWithCount(foundSet, parallelism, pool) -> a new index of the same
@@ -383,29 +362,8 @@ class BitSliceIndexBase(RoaringBitmapSliceIndex):
             raise IllegalArgumentException("parallelTransposeWithCount: parallelism must be positive")
         if len(self.bA) > 32:
             raise IllegalArgumentException("parallelTransposeWithCount: an index holds at most 32 slices")
-        arr, lens = self._slices()
-        e = self.ebM.serialize()
-        f = foundSet.serialize() if foundSet is not None else None
-        outs = (_lib.rbg_buffer * 33)()
-        out3 = (ctypes.c_int32 * 3)()
-        check(lib().rbg_bsi_transpose(e, len(e), arr, lens, len(self.bA), f, len(f) if f else 0, int(parallelism),
-                                      outs, out3))
-        bms = [RoaringBitmap(take(outs[k])) for k in range(1 + int(out3[0]))]
-        return type(self)(bms[0], bms[1:], int(out3[1]), int(out3[2]))
-
-    def _compare(self, op, start, end, foundSet):
-        arr, lens = self._slices()
-        e = self.ebM.serialize()
-        f = foundSet.serialize() if foundSet is not None else None
-        out = _lib.rbg_buffer()
-        check(lib().rbg_bsi_compare_buffer(op, int(start), int(end), e, len(e), arr, lens, len(self.bA),
-                                           self.minValue, self.maxValue, f, len(f) if f else 0, ctypes.byref(out)))
-        return RoaringBitmap(take(out))
-
-    def compare(self, operation, startOrValue, end=0, foundSet=None):
-        """BBSI/:422-453 -> ImmutableRoaringBitmap (as RoaringBitmap bytes)"""
-        op = OPERATIONS.index(operation) if isinstance(operation, str) else int(operation)
-        return self._compare(op, startOrValue, end, foundSet)
+        index, found = self._operands(foundSet)
+        return type(self)(*_index_call(lib().rbg_bsi_transpose, *index, *found, int(parallelism)))
 
     def rangeEQ(self, foundSet, predicate):  # BBSI/:351-375 (== compare(EQ))
         return self._compare(0, predicate, 0, foundSet)

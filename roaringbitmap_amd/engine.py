@@ -8,10 +8,23 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._lib import check, lib, take
+from ._lib import as_u32, call_bytes, check, ids_array, is_torch, lib, take
 from .roaring import RoaringBitmap
 
 SYNTH_C2, SYNTH_C3_UNIFORM, SYNTH_C3_CLUSTERED, SYNTH_C4_PAIRS, SYNTH_C5_BSI = 0, 1, 2, 3, 4
+
+
+def _dptr(t):
+    """the device pointer of a tensor, null for an empty one"""
+    return ctypes.c_void_p(t.data_ptr()) if t.numel() else None
+
+
+def _index_call(f, *args):
+    """f(*args, &batch, out3): a session call that makes a bit-sliced index -> (batch, nbits, minValue, maxValue)"""
+    out = ctypes.c_int32()
+    out3 = (ctypes.c_int32 * 3)()
+    check(f(*args, ctypes.byref(out), out3))
+    return out.value, int(out3[0]), int(out3[1]), int(out3[2])
 
 
 def synth_key_bytes(kind, seed, n) -> np.ndarray:
@@ -20,16 +33,6 @@ def synth_key_bytes(kind, seed, n) -> np.ndarray:
     check(lib().rbg_synth_key_bytes(int(kind), int(seed), int(n),
                                     out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
     return out
-
-
-def _in_list(values):
-    """the value list of an IN query as contiguous int32: Java ints, or their unsigned bit patterns"""
-    if isinstance(values, np.ndarray) and values.dtype in (np.int32, np.uint32):
-        return np.ascontiguousarray(values.reshape(-1)).view(np.int32)
-    v = np.asarray(values if isinstance(values, np.ndarray) else list(values), dtype=np.int64).reshape(-1)
-    if v.size and (v.min() < -(1 << 31) or v.max() >= 1 << 32):
-        raise _lib.IllegalArgumentException("the values of an IN list must fit 32 bits")
-    return np.ascontiguousarray(v.astype(np.uint32).view(np.int32))
 
 
 class Engine:
@@ -114,9 +117,7 @@ class Engine:
         return dict(zip(keys, list(s)))
 
     def batch_fetch(self, batch, i=0) -> RoaringBitmap:
-        b = _lib.rbg_buffer()
-        check(lib().rbg_ctx_batch_fetch(self._ctx, int(batch), int(i), ctypes.byref(b)))
-        return RoaringBitmap(take(b))
+        return RoaringBitmap(call_bytes(lib().rbg_ctx_batch_fetch, self._ctx, int(batch), int(i)))
 
     def batch_fetch_range(self, batch, first=0, count=None) -> list:
         """Bitmaps [first, first + count) of a batch (default: all), one device gather + one copy."""
@@ -161,18 +162,12 @@ class Engine:
         check(lib().rbg_ctx_pairwise_card(self._ctx, 0, int(a), int(ia), int(b), int(ib)))
 
     def wide(self, op, batch, key_lo=0, key_hi=65536, ids=None):
-        idp = None
-        if ids is not None:
-            idp = (ctypes.c_int32 * len(ids))(*ids)
-        check(lib().rbg_ctx_wide(self._ctx, _lib.WIDE_OP[op], int(batch), int(key_lo), int(key_hi), idp))
+        check(lib().rbg_ctx_wide(self._ctx, _lib.WIDE_OP[op], int(batch), int(key_lo), int(key_hi), ids_array(ids)))
 
     def wide_start(self, op, batch, key_lo, key_hi, start_bm, ids=None):
         """wide op whose naive_and chain starts from input `start_bm` (key-range shards)."""
-        idp = None
-        if ids is not None:
-            idp = (ctypes.c_int32 * len(ids))(*ids)
-        check(lib().rbg_ctx_wide_start(self._ctx, _lib.WIDE_OP[op], int(batch), int(key_lo), int(key_hi), idp,
-                                       int(start_bm)))
+        check(lib().rbg_ctx_wide_start(self._ctx, _lib.WIDE_OP[op], int(batch), int(key_lo), int(key_hi),
+                                       ids_array(ids), int(start_bm)))
 
     def pair_bytes(self, batch):
         """(matched payload + descriptors, all payload + descriptors) of a batch of pairs (C4)."""
@@ -209,16 +204,14 @@ class Engine:
     def bsi(self, batch, op, nbits, start, end=0, min_value=0, max_value=0, has_found=False, want_sum=False):
         """RoaringBitmapSliceIndex.compare (op in BitmapSliceIndex.Operation order; 8 = sum alone) over a
         key-major batch [ebM, bA[0..nbits-1], foundSet?]; want_sum fuses sum(result)."""
-        from .bsi import OPERATIONS
-        code = OPERATIONS.index(op) if isinstance(op, str) else int(op)
+        code = _lib.bsi_op(op)
         check(lib().rbg_ctx_bsi(self._ctx, int(batch), code, int(nbits), int(bool(has_found)), int(start), int(end),
                                 int(min_value), int(max_value), int(bool(want_sum))))
 
     def bsi_buffer(self, batch, op, nbits, start, end=0, min_value=0, max_value=0, has_found=False):
         """The buffer package's BitSliceIndexBase.compare (bsi/.../bsi/buffer/BitSliceIndexBase.java:422-453;
         op 7 = rangeNEQ called directly) over a key-major batch [ebM, bA[0..nbits-1], foundSet?]."""
-        from .bsi import OPERATIONS
-        code = OPERATIONS.index(op) if isinstance(op, str) else int(op)
+        code = _lib.bsi_op(op)
         check(lib().rbg_ctx_bsi_buffer(self._ctx, int(batch), code, int(nbits), int(bool(has_found)), int(start),
                                        int(end), int(min_value), int(max_value)))
 
@@ -258,38 +251,19 @@ class Engine:
         query, which builds its rank directory); torch's current stream waits for the result, so work
         enqueued there afterwards may read it."""
         code = _lib.PQ_OP[op] if isinstance(op, str) else int(op)
-        if type(queries).__module__.split(".")[0] == "torch":
+        if is_torch(queries):
             import torch
-            if queries.device.type != "cuda" or queries.device.index != self.device:
-                raise ValueError(f"point_query: the query tensor must be on device {self.device}")
-            if queries.dtype == torch.int64:  # the low 32 bits of every element (little-endian words)
-                q = queries.contiguous().reshape(-1).view(torch.int32)[::2].contiguous()
-            elif queries.dtype == torch.uint32:
-                q = queries.contiguous()
-            else:
-                raise ValueError("point_query: an int64 or uint32 tensor is required")
-            q = q.reshape(-1)
+            q = self._words("point_query", queries, ("int64", "uint32"), "query tensor")
             out = torch.empty(q.numel(), dtype=torch.int64, device=queries.device)
             if q.numel() == 0:
                 return out
-            # The conversion above ran on torch's current stream: the engine stream waits for it.  The current
-            # stream then waits for the query kernel, so torch's allocator, which orders the reuse of q's and
-            # out's memory on that stream alone, cannot hand either out while the kernel still uses it (the
-            # tensors keep no reference to the engine stream, which close() destroys), and out is ready
-            # for work enqueued on the current stream.
-            cur = torch.cuda.current_stream(queries.device)
-            es = torch.cuda.ExternalStream(self.stream_ptr, device=queries.device)
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            es.wait_event(ev)
+            done = self._handshake(queries.device)
             check(lib().rbg_ctx_point_query_device(self._ctx, code, int(batch), int(ia),
                                                    ctypes.c_void_p(q.data_ptr()), q.numel(),
                                                    ctypes.c_void_p(out.data_ptr())))
-            done = torch.cuda.Event()
-            done.record(es)
-            cur.wait_event(done)
+            done()
             return out
-        q = np.ascontiguousarray(np.asarray(queries, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        q = as_u32(queries)
         out = np.empty(q.size, dtype=np.int64)
         check(lib().rbg_ctx_point_query(self._ctx, code, int(batch), int(ia),
                                         q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), q.size,
@@ -298,10 +272,11 @@ class Engine:
 
     def _handshake(self, device):
         """Orders the engine stream after torch's current stream on `device`; returns a function that,
-        called after the engine work is enqueued, makes the current stream wait for it.  As in
-        point_query: tensors made on the current stream are ready for the engine's kernels, torch's
-        allocator (which orders reuse on the current stream alone) cannot hand their memory out while
-        those kernels run, and the outputs are ready for work enqueued on the current stream."""
+        called after the engine work is enqueued, makes the current stream wait for it.  So tensors made on
+        the current stream (a conversion of the input) are ready for the engine's kernels; torch's allocator,
+        which orders the reuse of a tensor's memory on the current stream alone, cannot hand that memory out
+        while those kernels still use it (the tensors keep no reference to the engine stream, which close()
+        destroys); and the outputs are ready for work enqueued on the current stream."""
         import torch
         cur = torch.cuda.current_stream(device)
         es = torch.cuda.ExternalStream(self.stream_ptr, device=device)
@@ -315,9 +290,41 @@ class Engine:
             cur.wait_event(d)
         return done
 
-    def _check_tensor(self, what, t):
+    def _words(self, what, t, dtypes=("int64", "uint32", "int32"), noun="tensor"):
+        """A torch tensor on this engine's GPU as flat contiguous 32-bit words: int64 (the low 32 bits of every
+        element, little-endian words) or, as it is, another of `dtypes`."""
+        import torch
         if t.device.type != "cuda" or t.device.index != self.device:
-            raise ValueError(f"{what}: the tensor must be on device {self.device}")
+            raise ValueError(f"{what}: the {noun} must be on device {self.device}")
+        if t.dtype == torch.int64:
+            w = t.contiguous().reshape(-1).view(torch.int32)[::2].contiguous()
+        elif t.dtype in [getattr(torch, d) for d in dtypes]:
+            w = t.contiguous()
+        else:
+            raise ValueError(f"{what}: an {', '.join(dtypes[:-1])} or {dtypes[-1]} tensor is required")
+        return w.reshape(-1)
+
+    def _pairs(self, what, columns, values):
+        """The shared front of the calls that take (column, value) pairs -> (done, columns pointer, values
+        pointer, n).  Tensors: both must be, of one length, int64 values in [0, 2^31); they are read in place as
+        32-bit words, and done, to be called after the device entry point, is the stream handshake's second half.
+        Arrays or sequences: checked and converted by pair_arrays, for the host entry point; done is None."""
+        if not is_torch(columns):
+            c, v = _lib.pair_arrays(columns, values)
+            return (None, c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                    v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size)
+        import torch
+        if not is_torch(values):
+            raise ValueError(f"{what}: columns and values must both be tensors or both arrays")
+        if columns.numel() != values.numel():
+            raise _lib.IllegalArgumentException("columns and values differ in length")
+        if values.dtype == torch.int64 and values.numel() and bool(((values < 0) | (values >= 1 << 31)).any()):
+            raise _lib.IllegalArgumentException("Values should be non-negative and below 2^31")
+        c = self._words(what, columns)
+        v = self._words(what, values)
+        done = self._handshake(columns.device)
+        done.words = (c, v)  # referenced for as long as the caller holds done
+        return done, _dptr(c), _dptr(v), c.numel()
 
     def from_values(self, values, run_optimize=False) -> int:
         """A resident bitmap from its values, built on the device (rbg_ctx_from_values): RoaringBitmap.bitmapOf
@@ -328,22 +335,14 @@ class Engine:
         0xFFFFFFFF) or uint32, with point_query's stream handshake.  Synchronous either way: the container
         count and the batch totals are read back."""
         out = ctypes.c_int32()
-        if type(values).__module__.split(".")[0] == "torch":
-            import torch
-            self._check_tensor("from_values", values)
-            if values.dtype == torch.int64:  # the low 32 bits of every element (little-endian words)
-                v = values.contiguous().reshape(-1).view(torch.int32)[::2].contiguous()
-            elif values.dtype == torch.uint32:
-                v = values.contiguous()
-            else:
-                raise ValueError("from_values: an int64 or uint32 tensor is required")
-            v = v.reshape(-1)
+        if is_torch(values):
+            v = self._words("from_values", values, ("int64", "uint32"))
             done = self._handshake(values.device)
-            check(lib().rbg_ctx_from_values_device(self._ctx, ctypes.c_void_p(v.data_ptr()) if v.numel() else None,
-                                                   v.numel(), int(bool(run_optimize)), ctypes.byref(out)))
+            check(lib().rbg_ctx_from_values_device(self._ctx, _dptr(v), v.numel(), int(bool(run_optimize)),
+                                                   ctypes.byref(out)))
             done()
             return out.value
-        v = np.ascontiguousarray(np.asarray(values, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        v = as_u32(values)
         check(lib().rbg_ctx_from_values(self._ctx, v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size,
                                         int(bool(run_optimize)), ctypes.byref(out)))
         return out.value
@@ -364,7 +363,7 @@ class Engine:
         check(lib().rbg_ctx_to_values_device(self._ctx, int(batch), int(ia), first, count, 0, None,
                                              ctypes.byref(n_out)))
         n = int(n_out.value)
-        if dtype is not None and type(dtype).__module__.split(".")[0] == "torch":
+        if dtype is not None and is_torch(dtype):
             import torch
             if dtype not in (torch.uint32, torch.int64):
                 raise ValueError("to_values: dtype torch.uint32 or torch.int64")
@@ -386,19 +385,6 @@ class Engine:
                                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(n_out)))
         return out
 
-    def _words(self, what, t):
-        """A torch tensor on this engine's GPU as contiguous 32-bit words: int64 (the low 32 bits of every
-        element, little-endian words), uint32 or int32, as from_values and point_query take them."""
-        import torch
-        self._check_tensor(what, t)
-        if t.dtype == torch.int64:
-            w = t.contiguous().reshape(-1).view(torch.int32)[::2].contiguous()
-        elif t.dtype in (torch.uint32, torch.int32):
-            w = t.contiguous()
-        else:
-            raise ValueError(f"{what}: an int64, uint32 or int32 tensor is required")
-        return w.reshape(-1)
-
     def bsi_from_columns(self, columns, values, run_optimize=False):
         """A resident bit-sliced index from (column, value) pairs, built on the device
         (rbg_ctx_bsi_from_columns): setValue(column, value) for every pair, with run_optimize followed by
@@ -409,37 +395,12 @@ class Engine:
         (columns below 2^32, values below 2^31) are uploaded; torch tensors on this engine's GPU are read
         in place (rbg_ctx_bsi_from_columns_device), int64 (the low 32 bits of every element are read) or
         uint32 / int32, with point_query's stream handshake.  Synchronous either way."""
-        out = ctypes.c_int32()
-        out3 = (ctypes.c_int32 * 3)()
-        if type(columns).__module__.split(".")[0] == "torch":
-            import torch
-            if type(values).__module__.split(".")[0] != "torch":
-                raise ValueError("bsi_from_columns: columns and values must both be tensors or both arrays")
-            if columns.numel() != values.numel():
-                raise _lib.IllegalArgumentException("columns and values differ in length")
-            if values.dtype == torch.int64 and values.numel() and bool(((values < 0) | (values >= 1 << 31)).any()):
-                raise _lib.IllegalArgumentException("Values should be non-negative and below 2^31")
-            c = self._words("bsi_from_columns", columns)
-            v = self._words("bsi_from_columns", values)
-            done = self._handshake(columns.device)
-            n = c.numel()
-            check(lib().rbg_ctx_bsi_from_columns_device(
-                self._ctx, ctypes.c_void_p(c.data_ptr()) if n else None, ctypes.c_void_p(v.data_ptr()) if n else None,
-                n, int(bool(run_optimize)), ctypes.byref(out), out3))
+        done, cp, vp, n = self._pairs("bsi_from_columns", columns, values)
+        f = lib().rbg_ctx_bsi_from_columns_device if done else lib().rbg_ctx_bsi_from_columns
+        got = _index_call(f, self._ctx, cp, vp, n, int(bool(run_optimize)))
+        if done:
             done()
-            return out.value, int(out3[0]), int(out3[1]), int(out3[2])
-        c = np.asarray(columns, dtype=np.int64).reshape(-1)
-        v = np.asarray(values, dtype=np.int64).reshape(-1)
-        if c.size != v.size:
-            raise _lib.IllegalArgumentException("columns and values differ in length")
-        if v.size and (v.min() < 0 or v.max() >= 1 << 31):
-            raise _lib.IllegalArgumentException("Values should be non-negative and below 2^31")
-        c = np.ascontiguousarray(c.astype(np.uint32))
-        v = np.ascontiguousarray(v.astype(np.int32))
-        check(lib().rbg_ctx_bsi_from_columns(self._ctx, c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                             v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size,
-                                             int(bool(run_optimize)), ctypes.byref(out), out3))
-        return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+        return got
 
     def bsi_add(self, a, nbits_a, b, nbits_b, min_a=0, max_a=0):
         """RoaringBitmapSliceIndex.add (BSI/:66-95) of two resident run-free indexes, the key-major batches
@@ -449,11 +410,8 @@ class Engine:
         doubles the values.  An empty ebM of b: a copy of a with (nbits_a, min_a, max_a).  A run container
         in either batch, more than 32 slices on either side or in the sum: IllegalArgumentException, no
         batch made.  Synchronous."""
-        out = ctypes.c_int32()
-        out3 = (ctypes.c_int32 * 3)()
-        check(lib().rbg_ctx_bsi_add(self._ctx, int(a), int(nbits_a), int(b), int(nbits_b), int(min_a), int(max_a),
-                                    ctypes.byref(out), out3))
-        return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+        return _index_call(lib().rbg_ctx_bsi_add, self._ctx, int(a), int(nbits_a), int(b), int(nbits_b), int(min_a),
+                           int(max_a))
 
     def bsi_set_values(self, batch, nbits, columns, values, min_value=0, max_value=0):
         """RoaringBitmapSliceIndex.setValues(List<Pair>) (BSI/:349-357; setValue, :299-313, with one pair) on a
@@ -467,39 +425,12 @@ class Engine:
         full: IllegalArgumentException, no batch made.  numpy arrays or sequences are uploaded; torch tensors
         on this engine's GPU are read in place (rbg_ctx_bsi_set_values_device), as in bsi_from_columns.
         Synchronous either way."""
-        out = ctypes.c_int32()
-        out3 = (ctypes.c_int32 * 3)()
-        if type(columns).__module__.split(".")[0] == "torch":
-            import torch
-            if type(values).__module__.split(".")[0] != "torch":
-                raise ValueError("bsi_set_values: columns and values must both be tensors or both arrays")
-            if columns.numel() != values.numel():
-                raise _lib.IllegalArgumentException("columns and values differ in length")
-            if values.dtype == torch.int64 and values.numel() and bool(((values < 0) | (values >= 1 << 31)).any()):
-                raise _lib.IllegalArgumentException("Values should be non-negative and below 2^31")
-            c = self._words("bsi_set_values", columns)
-            v = self._words("bsi_set_values", values)
-            done = self._handshake(columns.device)
-            n = c.numel()
-            check(lib().rbg_ctx_bsi_set_values_device(
-                self._ctx, int(batch), int(nbits), int(min_value), int(max_value),
-                ctypes.c_void_p(c.data_ptr()) if n else None, ctypes.c_void_p(v.data_ptr()) if n else None, n,
-                ctypes.byref(out), out3))
+        done, cp, vp, n = self._pairs("bsi_set_values", columns, values)
+        f = lib().rbg_ctx_bsi_set_values_device if done else lib().rbg_ctx_bsi_set_values
+        got = _index_call(f, self._ctx, int(batch), int(nbits), int(min_value), int(max_value), cp, vp, n)
+        if done:
             done()
-            return out.value, int(out3[0]), int(out3[1]), int(out3[2])
-        c = np.asarray(columns, dtype=np.int64).reshape(-1)
-        v = np.asarray(values, dtype=np.int64).reshape(-1)
-        if c.size != v.size:
-            raise _lib.IllegalArgumentException("columns and values differ in length")
-        if v.size and (v.min() < 0 or v.max() >= 1 << 31):
-            raise _lib.IllegalArgumentException("Values should be non-negative and below 2^31")
-        c = np.ascontiguousarray(c.astype(np.uint32))
-        v = np.ascontiguousarray(v.astype(np.int32))
-        check(lib().rbg_ctx_bsi_set_values(self._ctx, int(batch), int(nbits), int(min_value), int(max_value),
-                                           c.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
-                                           v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), c.size,
-                                           ctypes.byref(out), out3))
-        return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+        return got
 
     def bsi_in(self, batch, nbits, values, parallelism=1, has_found=False) -> int:
         """BitSliceIndexBase.parallelIn (BBSI/:611-639), WHERE value IN (values), over a resident index
@@ -510,7 +441,7 @@ class Engine:
         slices), in any order, repeats allowed.  parallelism only decides whether a full container is a
         bitmap or a run container.  parallelism < 1, nbits > 32 or a batch of another shape:
         IllegalArgumentException, no batch made.  Synchronous."""
-        v = _in_list(values)
+        v = _lib.in_list(values)
         out = ctypes.c_int32()
         check(lib().rbg_ctx_bsi_in(self._ctx, int(batch), int(nbits), int(bool(has_found)),
                                    v.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), v.size, int(parallelism),
@@ -528,11 +459,8 @@ class Engine:
         parallelism only decides whether a full container of the result's ebM is a bitmap or a run container.
         parallelism < 1, nbits > 32 or a batch of another shape: IllegalArgumentException, no batch made.
         Synchronous."""
-        out = ctypes.c_int32()
-        out3 = (ctypes.c_int32 * 3)()
-        check(lib().rbg_ctx_bsi_transpose(self._ctx, int(batch), int(nbits), int(bool(has_found)), int(parallelism),
-                                          ctypes.byref(out), out3))
-        return out.value, int(out3[0]), int(out3[1]), int(out3[2])
+        return _index_call(lib().rbg_ctx_bsi_transpose, self._ctx, int(batch), int(nbits), int(bool(has_found)),
+                           int(parallelism))
 
     def bsi_get_values(self, batch, nbits, columns, has_found=False):
         """getValue for many columns at once against a resident index [ebM, bA[0..nbits-1], foundSet?]
@@ -540,7 +468,7 @@ class Engine:
         columns need not be sorted or distinct.  numpy in -> numpy out, synchronous; a torch tensor on this
         engine's GPU (int64 low words, or uint32) -> torch int64 tensor through the device entry point with no
         host synchronisation, under point_query's stream handshake."""
-        if type(columns).__module__.split(".")[0] == "torch":
+        if is_torch(columns):
             import torch
             q = self._words("bsi_get_values", columns)
             out = torch.empty(q.numel(), dtype=torch.int64, device=columns.device)
@@ -552,7 +480,7 @@ class Engine:
                                                       ctypes.c_void_p(out.data_ptr())))
             done()
             return out
-        q = np.ascontiguousarray(np.asarray(columns, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        q = as_u32(columns)
         out = np.empty(q.size, dtype=np.int64)
         check(lib().rbg_ctx_bsi_get_values(self._ctx, int(batch), int(nbits), int(bool(has_found)),
                                            q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), q.size,
@@ -575,7 +503,7 @@ class Engine:
         them, as with point_query's result."""
         n = self.bsi_pairs_count(batch, nbits, has_found)
         n_out = ctypes.c_uint64()
-        if dtype is not None and type(dtype).__module__.split(".")[0] == "torch":
+        if dtype is not None and is_torch(dtype):
             import torch
             if dtype not in (torch.uint32, torch.int64):
                 raise ValueError("bsi_to_pairs: dtype torch.uint32 or torch.int64")
@@ -636,9 +564,7 @@ class Engine:
         check(lib().rbg_ctx_serialize(self._ctx))
 
     def fetch(self) -> RoaringBitmap:
-        b = _lib.rbg_buffer()
-        check(lib().rbg_ctx_fetch(self._ctx, ctypes.byref(b)))
-        return RoaringBitmap(take(b))
+        return RoaringBitmap(call_bytes(lib().rbg_ctx_fetch, self._ctx))
 
     def fetch_shard_device(self, total_containers, has_run, payload_base, desc, offsets, runflags, payload):
         """Enqueue the pending result as a key shard of a global bitmap, written straight into

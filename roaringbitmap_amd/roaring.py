@@ -13,14 +13,13 @@ Java names that are Python keywords are exposed with a trailing underscore and
 also registered under the Java name (getattr(RoaringBitmap, "and")).
 """
 import ctypes
-import itertools
 from collections.abc import Iterator
 
 import numpy as np
 
 from . import _lib
-from ._lib import (ArrayIndexOutOfBoundsException, IllegalArgumentException, NoSuchElementException, check, lib,
-                   take)
+from ._lib import (ArrayIndexOutOfBoundsException, IllegalArgumentException, NoSuchElementException, as_u32,
+                   call_bytes, check, lib, take)
 
 EMPTY = bytes.fromhex("3a30000000000000")
 
@@ -57,9 +56,8 @@ def _range_op(op, bitmaps, start, end, cls=None):
     ImmutableRoaringBitmap's (MutableRoaringBitmap results)."""
     bufs = [b._buf for b in bitmaps]
     arr, lens = _lib.buf_array(bufs)
-    b = _lib.rbg_buffer()
-    check(lib().rbg_range_op(_lib.RANGE_OP[op], arr, lens, len(bufs), int(start), int(end), ctypes.byref(b)))
-    return (cls or RoaringBitmap)(take(b))
+    return (cls or RoaringBitmap)(call_bytes(lib().rbg_range_op, _lib.RANGE_OP[op], arr, lens, len(bufs), int(start),
+                                             int(end)))
 
 
 def _is_range(args):
@@ -130,10 +128,8 @@ class _OrNot:
 
 
 def _ornot(x1, x2, range_end, inplace, buffer=False):
-    b = _lib.rbg_buffer()
     flags = (_lib.RBG_ORNOT_INPLACE if inplace else 0) | (_lib.RBG_ORNOT_BUFFER if buffer else 0)
-    check(lib().rbg_ornot(x1._buf, len(x1._buf), x2._buf, len(x2._buf), int(range_end), flags, ctypes.byref(b)))
-    return take(b)
+    return call_bytes(lib().rbg_ornot, x1._buf, len(x1._buf), x2._buf, len(x2._buf), int(range_end), flags)
 
 
 def _s_ornot(x1, x2, range_end):
@@ -159,10 +155,8 @@ class _RangeMut:
         self.op, self.buffer, self.cls = op, buffer, cls
 
     def _run(self, op, rb, range_start, range_end):
-        b = _lib.rbg_buffer()
         code = _lib.RMUT_OP[op] | (_lib.RBG_RMUT_BUFFER if self.buffer else 0)
-        check(lib().rbg_range_mut(code, rb._buf, len(rb._buf), int(range_start), int(range_end), ctypes.byref(b)))
-        return take(b)
+        return call_bytes(lib().rbg_range_mut, code, rb._buf, len(rb._buf), int(range_start), int(range_end))
 
     def static(self, rb, range_start, range_end):
         return (self.cls or RoaringBitmap)(self._run(self.op, rb, range_start, range_end))
@@ -202,11 +196,9 @@ class RoaringBitmap:
     def from_values(cls, values, run_optimize=False, gpu=False):
         """bitmapOf(values) [+ runOptimize()], built on the host (rbg_from_values); gpu=True: built on the
         device (rbg_build_values), the same bytes."""
-        v = np.ascontiguousarray(np.asarray(values, dtype=np.int64).astype(np.uint32)).reshape(-1)
-        b = _lib.rbg_buffer()
+        v = as_u32(values)
         f = lib().rbg_build_values if gpu else lib().rbg_from_values
-        check(f(v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, int(run_optimize), ctypes.byref(b)))
-        return cls(take(b))
+        return cls(call_bytes(f, v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size, int(run_optimize)))
 
     @classmethod
     def deserialize(cls, data: bytes):
@@ -222,26 +214,21 @@ class RoaringBitmap:
 
     def runOptimize(self) -> bool:
         """In-place runOptimize (RB/RoaringBitmap.java:2764-2774); True if a run container results."""
-        b = _lib.rbg_buffer()
-        check(lib().rbg_run_optimize(self._buf, len(self._buf), ctypes.byref(b)))
-        self._buf = take(b)
+        self._buf = call_bytes(lib().rbg_run_optimize, self._buf, len(self._buf))
         return self.container_stats()[2] > 0
 
     def limit(self, maxcardinality):
         """x.limit(maxcardinality) (RB/RoaringBitmap.java:2457-2476) on the GPU: a new bitmap of the first
         maxcardinality values (the cut container through Container.limit).  ImmutableRoaringBitmap.limit
         (RB/buffer/ImmutableRoaringBitmap.java:1658-1677, the same types) returns a MutableRoaringBitmap."""
-        b = _lib.rbg_buffer()
-        check(lib().rbg_limit(self._buf, len(self._buf), _int32(maxcardinality), ctypes.byref(b)))
-        return (MutableRoaringBitmap if isinstance(self, ImmutableRoaringBitmap) else RoaringBitmap)(take(b))
+        out = call_bytes(lib().rbg_limit, self._buf, len(self._buf), _int32(maxcardinality))
+        return (MutableRoaringBitmap if isinstance(self, ImmutableRoaringBitmap) else RoaringBitmap)(out)
 
     def removeRunCompression(self) -> bool:
         """In-place removeRunCompression (RB/RoaringBitmap.java:2738-2749; MutableRoaringBitmap's alike): every
         run container as an array or bitmap by cardinality, on the GPU; True if there was one."""
         had = self.container_stats()[2] > 0
-        b = _lib.rbg_buffer()
-        check(lib().rbg_remove_run_compression(self._buf, len(self._buf), ctypes.byref(b)))
-        self._buf = take(b)
+        self._buf = call_bytes(lib().rbg_remove_run_compression, self._buf, len(self._buf))
         return had
 
     def clone(self):
@@ -277,11 +264,8 @@ class RoaringBitmap:
     def toArray(self, gpu=False) -> np.ndarray:
         """RoaringBitmap.toArray() (RB/RoaringBitmap.java:3224) on the host (rbg_to_values); gpu=True: expanded
         on the device (rbg_expand_values), the same values."""
-        b = _lib.rbg_buffer()
         f = lib().rbg_expand_values if gpu else lib().rbg_to_values
-        check(f(self._buf, len(self._buf), ctypes.byref(b)))
-        raw = take(b)
-        return np.frombuffer(raw, dtype=np.uint32).copy()
+        return np.frombuffer(call_bytes(f, self._buf, len(self._buf)), dtype=np.uint32).copy()
 
     def contains(self, x) -> bool:
         """RoaringBitmap.contains(int) (RB/RoaringBitmap.java:1693-1701): the key's container through
@@ -308,7 +292,7 @@ class RoaringBitmap:
 
     # ---- point queries (rbg_point_query: the GPU's rank directory) -----------
     def _point(self, op, xs) -> np.ndarray:
-        q = np.ascontiguousarray(np.asarray(xs, dtype=np.int64).astype(np.uint32)).reshape(-1)
+        q = as_u32(xs)
         out = np.empty(q.size, dtype=np.int64)
         check(lib().rbg_point_query(_lib.PQ_OP[op], self._buf, len(self._buf),
                                     q.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), q.size,
@@ -393,10 +377,9 @@ class RoaringBitmap:
         (RB/buffer/ImmutableRoaringBitmap.java:701-757) keeps the buffer package's types and returns a
         MutableRoaringBitmap."""
         buffer = isinstance(self, ImmutableRoaringBitmap)
-        b = _lib.rbg_buffer()
-        check(lib().rbg_select_range(self._buf, len(self._buf), int(range_start), int(range_end), int(buffer),
-                                     ctypes.byref(b)))
-        return (MutableRoaringBitmap if buffer else RoaringBitmap)(take(b))
+        out = call_bytes(lib().rbg_select_range, self._buf, len(self._buf), int(range_start), int(range_end),
+                         int(buffer))
+        return (MutableRoaringBitmap if buffer else RoaringBitmap)(out)
 
     def isHammingSimilar(self, other, tolerance) -> bool:
         """RoaringBitmap.isHammingSimilar(other, tolerance) (RB/RoaringBitmap.java:1831-1863): the budget
@@ -430,10 +413,10 @@ class RoaringBitmap:
 
     # ---- static pairwise ops (RB/RoaringBitmap.java) --------------------------
     @staticmethod
-    def _pair(op, x1, x2):
-        b = _lib.rbg_buffer()
-        check(lib().rbg_pairwise(_lib.OP[op], x1._buf, len(x1._buf), x2._buf, len(x2._buf), ctypes.byref(b)))
-        return RoaringBitmap(take(b))
+    def _pair(op, x1, x2, cls=None):
+        """the static pairwise op (rbg_pairwise) as a RoaringBitmap, or as the buffer package's result class"""
+        return (cls or RoaringBitmap)(call_bytes(lib().rbg_pairwise, _lib.OP[op], x1._buf, len(x1._buf), x2._buf,
+                                                 len(x2._buf)))
 
     @staticmethod
     def _card(op, x1, x2):
@@ -455,9 +438,7 @@ class RoaringBitmap:
     def bitmapOfRange(cls, range_min, range_max):
         """RoaringBitmap.bitmapOfRange(min, max) (RB/RoaringBitmap.java:588-615) on the GPU: [min, max) as
         run containers (RunContainer.rangeOfOnes, even for one or two values)."""
-        b = _lib.rbg_buffer()
-        check(lib().rbg_bitmap_of_range(int(range_min), int(range_max), ctypes.byref(b)))
-        return cls(take(b))
+        return cls(call_bytes(lib().rbg_bitmap_of_range, int(range_min), int(range_max)))
 
     @classmethod
     def addOffset(cls, x, offset):
@@ -465,18 +446,14 @@ class RoaringBitmap:
         (a long in [-2^32, 2^32]; values leaving [0, 2^32) dropped).  The buffer package's
         MutableRoaringBitmap.addOffset(ImmutableRoaringBitmap, long) (RB/buffer/MutableRoaringBitmap.java
         :84-142) gives the same bytes, as a MutableRoaringBitmap."""
-        b = _lib.rbg_buffer()
-        check(lib().rbg_add_offset(x._buf, len(x._buf), int(offset), ctypes.byref(b)))
-        return cls(take(b))
+        return cls(call_bytes(lib().rbg_add_offset, x._buf, len(x._buf), int(offset)))
 
     def _inplace(self, op, x2):
         """x1.and / or / xor / andNot(x2) in place (rbg_pairwise_inplace); x2 may be x1 itself"""
         if x2 is self and op in ("and", "or"):
             return  # x1.and(x1) / x1.or(x1) return at once (RB/RoaringBitmap.java:1273, 2482)
-        b = _lib.rbg_buffer()
-        check(lib().rbg_pairwise_inplace(_lib.OP[op], self._buf, len(self._buf), x2._buf, len(x2._buf),
-                                         int(x2 is self), ctypes.byref(b)))
-        self._buf = take(b)
+        self._buf = call_bytes(lib().rbg_pairwise_inplace, _lib.OP[op], self._buf, len(self._buf), x2._buf,
+                               len(x2._buf), int(x2 is self))
         self._lcard = None
 
     @staticmethod
@@ -509,25 +486,29 @@ setattr(RoaringBitmap, "and", RoaringBitmap.__dict__["and_"])
 setattr(RoaringBitmap, "or", RoaringBitmap.__dict__["or_"])
 
 
-def _find_container(buf, key):
-    """(kind, payload view) of `key`'s container in a portable serialized bitmap (RB/RoaringArray.java
-    :547-629 layout: cookie, run flags, (key, card - 1) descriptors, offsets unless a run bitmap of
-    fewer than 4 containers), or None.  kind 0 = array (u16 values), 1 = bitmap (u64 words), 2 = run
-    (u16 start, length - 1 pairs)."""
+def _header(buf):
+    """The head of a portable serialized bitmap (RB/RoaringArray.java:547-588: cookie, run flags, (key,
+    card - 1) descriptors, offsets unless a run bitmap of fewer than 4 containers) -> (run flag bytes or None,
+    the descriptors as u16 pairs, where they end, whether an offset table follows)."""
     cookie = int.from_bytes(buf[0:4], "little")
     if (cookie & 0xFFFF) == 12347:
         size = (cookie >> 16) + 1
-        flags = buf[4:4 + (size + 7) // 8]
         dpos = 4 + (size + 7) // 8
-        has_off = size >= 4
+        flags, has_off = buf[4:dpos], size >= 4
     else:
         size = int.from_bytes(buf[4:8], "little")
-        flags = None
-        dpos = 8
-        has_off = True
+        dpos, flags, has_off = 8, None, True
+    return flags, np.frombuffer(buf, dtype="<u2", count=2 * size, offset=dpos), dpos + 4 * size, has_off
+
+
+def _find_container(buf, key):
+    """(kind, payload view) of `key`'s container in a portable serialized bitmap (RB/RoaringArray.java
+    :547-629 layout), or None.  kind 0 = array (u16 values), 1 = bitmap (u64 words), 2 = run
+    (u16 start, length - 1 pairs)."""
+    flags, desc, dend, has_off = _header(buf)
+    size = len(desc) // 2
     if size == 0:
         return None
-    desc = np.frombuffer(buf, dtype="<u2", count=2 * size, offset=dpos)
     keys = desc[0::2]
     i = int(np.searchsorted(keys, key))
     if i >= size or int(keys[i]) != key:
@@ -545,9 +526,9 @@ def _find_container(buf, key):
         return 8192 if k == 1 else 2 * (int(desc[2 * j + 1]) + 1)
 
     if has_off:
-        pos = int.from_bytes(buf[dpos + 4 * size + 4 * i:dpos + 4 * size + 4 * i + 4], "little")
+        pos = int.from_bytes(buf[dend + 4 * i:dend + 4 * i + 4], "little")
     else:  # no offset table: walk the (at most 3) payloads before it
-        pos = dpos + 4 * size
+        pos = dend
         for j in range(i):
             pos += length(j, pos)
     k = kind_of(i)
@@ -575,14 +556,7 @@ def _intersect_array_into_bitmap(words, keys) -> int:
 
 def _keys_of(buf) -> np.ndarray:
     """the container keys of a portable serialized bitmap (its descriptor table, RB/RoaringArray.java:547-588)"""
-    cookie = int.from_bytes(buf[0:4], "little")
-    if (cookie & 0xFFFF) == 12347:
-        size = (cookie >> 16) + 1
-        dpos = 4 + (size + 7) // 8
-    else:
-        size = int.from_bytes(buf[4:8], "little")
-        dpos = 8
-    return np.frombuffer(buf, dtype="<u2", count=2 * size, offset=dpos)[0::2].astype(np.int64)
+    return _header(buf)[1][0::2].astype(np.int64)
 
 
 def _full_containers(keys) -> bytes:
@@ -611,12 +585,8 @@ def _identity_ids(bitmaps):
 def _wide(op, bitmaps, ids=None):
     bufs = [b._buf for b in bitmaps]
     arr, lens = _lib.buf_array(bufs)
-    idp = None
-    if ids is not None and bitmaps:
-        idp = (ctypes.c_int32 * len(ids))(*ids)
-    b = _lib.rbg_buffer()
-    check(lib().rbg_wide(_lib.WIDE_OP[op], arr, lens, idp, len(bufs), ctypes.byref(b)))
-    return RoaringBitmap(take(b))
+    idp = _lib.ids_array(ids if bitmaps else None)
+    return RoaringBitmap(call_bytes(lib().rbg_wide, _lib.WIDE_OP[op], arr, lens, idp, len(bufs)))
 
 
 def _wide_card(op, bitmaps):
@@ -627,15 +597,18 @@ def _wide_card(op, bitmaps):
     return out.value
 
 
+def _varargs(args):
+    """Java's RoaringBitmap... parameter: the bitmaps themselves, or one list / tuple of them"""
+    return list(args[0]) if len(args) == 1 and isinstance(args[0], (list, tuple)) else list(args)
+
+
 def _split_args(args):
     """Java overloads: (Iterator) vs (RoaringBitmap...) vs (long[] buffer, RoaringBitmap...)."""
     if len(args) == 1 and isinstance(args[0], Iterator):
         return "iter", None, list(args[0])
     if args and isinstance(args[0], np.ndarray):
         return "buffer", args[0], list(args[1:])
-    if len(args) == 1 and isinstance(args[0], (list, tuple)):
-        return "varargs", None, list(args[0])
-    return "varargs", None, list(args)
+    return "varargs", None, _varargs(args)
 
 
 class FastAggregation:
@@ -689,7 +662,7 @@ class FastAggregation:
     @staticmethod
     def workShyAnd(buffer, *bitmaps):
         """workShyAnd(long[] buffer, RoaringBitmap...) :356-414"""
-        bms = list(bitmaps[0]) if len(bitmaps) == 1 and isinstance(bitmaps[0], (list, tuple)) else list(bitmaps)
+        bms = _varargs(bitmaps)
         return _wide("workshy_and", bms)
 
     @staticmethod
@@ -716,7 +689,7 @@ class FastAggregation:
         loop runs to the buffer's length, RB/BitmapContainer.java:535-538), and so it does here."""
         if buffer is None or len(buffer) < 1024:
             raise IllegalArgumentException("buffer should have at least 1024 elements.")
-        bms = list(bitmaps[0]) if len(bitmaps) == 1 and isinstance(bitmaps[0], (list, tuple)) else list(bitmaps)
+        bms = _varargs(bitmaps)
         if not isinstance(buffer, np.ndarray) or buffer.dtype.itemsize != 8 or buffer.ndim != 1:
             raise IllegalArgumentException("buffer must be a one-dimensional numpy array of 64-bit words")
         words = buffer.view(np.uint64)  # the caller's memory: the reference writes its long[] in place
@@ -781,13 +754,13 @@ class FastAggregation:
         horizontal_or(RoaringBitmap...) :185-231 run the container-pointer priority queue"""
         if len(args) == 1 and isinstance(args[0], Iterator):
             return _wide("or", list(args[0]))
-        bms = list(args[0]) if len(args) == 1 and isinstance(args[0], (list, tuple)) else list(args)
+        bms = _varargs(args)
         return _wide("horizontal_or", bms)
 
     @staticmethod
     def horizontal_xor(*bitmaps):
         """horizontal_xor(RoaringBitmap...) :243-289 (empty results are kept as empty containers)"""
-        bms = list(bitmaps[0]) if len(bitmaps) == 1 and isinstance(bitmaps[0], (list, tuple)) else list(bitmaps)
+        bms = _varargs(bitmaps)
         return _wide("horizontal_xor", bms)
 
     @staticmethod
@@ -796,13 +769,13 @@ class FastAggregation:
         queue of whole bitmaps by getLongSizeInBytes, lazy unions, repairAfterLazy at the end"""
         if len(args) == 1 and isinstance(args[0], Iterator):
             return _wide("priorityqueue_or", list(args[0]))
-        bms = list(args[0]) if len(args) == 1 and isinstance(args[0], (list, tuple)) else list(args)
+        bms = _varargs(args)
         return _wide("priorityqueue_or", bms)
 
     @staticmethod
     def priorityqueue_xor(*bitmaps):
         """priorityqueue_xor(RoaringBitmap...) :794-812: RoaringBitmap.xor of the two smallest"""
-        bms = list(bitmaps[0]) if len(bitmaps) == 1 and isinstance(bitmaps[0], (list, tuple)) else list(bitmaps)
+        bms = _varargs(bitmaps)
         return _wide("priorityqueue_xor", bms)
 
 
@@ -817,12 +790,12 @@ class ParallelAggregation:
 
     @staticmethod
     def or_(*bitmaps):
-        bms = list(bitmaps[0]) if len(bitmaps) == 1 and isinstance(bitmaps[0], (list, tuple)) else list(bitmaps)
+        bms = _varargs(bitmaps)
         return _wide("parallel_or", bms)
 
     @staticmethod
     def xor(*bitmaps):
-        bms = list(bitmaps[0]) if len(bitmaps) == 1 and isinstance(bitmaps[0], (list, tuple)) else list(bitmaps)
+        bms = _varargs(bitmaps)
         return _wide("parallel_xor", bms)
 
 
@@ -881,7 +854,7 @@ class BufferFastAggregation:
     @staticmethod
     def naive_and_mutable(*bitmaps):
         """naive_and(MutableRoaringBitmap...) :407-416: clone of the first, then the and chain"""
-        bms = list(bitmaps[0]) if len(bitmaps) == 1 and isinstance(bitmaps[0], (list, tuple)) else list(bitmaps)
+        bms = _varargs(bitmaps)
         return _wide("buffer_and_iter", bms)
 
     @staticmethod
@@ -909,7 +882,7 @@ class BufferFastAggregation:
         """or(MutableRoaringBitmap...) :896-898 -> naive_or(MutableRoaringBitmap...) :810-817:
         MutableRoaringBitmap.lazyor per input (RB/buffer/MutableRoaringBitmap.java:1309-1351),
         i.e. a lazyIOR chain per key, then repairAfterLazy"""
-        bms = list(bitmaps[0]) if len(bitmaps) == 1 and isinstance(bitmaps[0], (list, tuple)) else list(bitmaps)
+        bms = _varargs(bitmaps)
         return _wide("buffer_or_mutable", bms)
 
     naive_or_mutable = or_mutable
@@ -944,19 +917,13 @@ class ImmutableRoaringBitmap(RoaringBitmap):
     __slots__ = ()
 
     @staticmethod
-    def _bpair(op, x1, x2):
-        b = _lib.rbg_buffer()
-        check(lib().rbg_pairwise(_lib.OP[op], x1._buf, len(x1._buf), x2._buf, len(x2._buf), ctypes.byref(b)))
-        return MutableRoaringBitmap(take(b))
-
-    @staticmethod
     def _s_and(*args):
         """and(x1, x2) :299-325; and(Iterator, rangeStart, rangeEnd) :261-267 (selectRangeWithoutCopy, then
         BufferFastAggregation.and(Iterator) = workShyAnd)"""
         if _is_range(args):
             return _range_op("and_buffer", list(args[0]), args[1], args[2], MutableRoaringBitmap)
         x1, x2 = args
-        return ImmutableRoaringBitmap._bpair("and_buffer", x1, x2)
+        return RoaringBitmap._pair("and_buffer", x1, x2, MutableRoaringBitmap)
 
     @staticmethod
     def _s_andnot(*args):
@@ -964,7 +931,7 @@ class ImmutableRoaringBitmap(RoaringBitmap):
         if len(args) == 4:
             return _range_op("andnot_buffer", [args[0], args[1]], args[2], args[3], MutableRoaringBitmap)
         x1, x2 = args
-        return ImmutableRoaringBitmap._bpair("andnot_buffer", x1, x2)
+        return RoaringBitmap._pair("andnot_buffer", x1, x2, MutableRoaringBitmap)
 
     @staticmethod
     def _s_or(*args):
@@ -973,7 +940,7 @@ class ImmutableRoaringBitmap(RoaringBitmap):
         if _is_range(args):
             return _range_op("or_buffer", list(args[0]), args[1], args[2], MutableRoaringBitmap)
         if len(args) == 2 and not isinstance(args[0], Iterator):
-            return ImmutableRoaringBitmap._bpair("or", args[0], args[1])
+            return RoaringBitmap._pair("or", args[0], args[1], MutableRoaringBitmap)
         bms = list(args[0]) if len(args) == 1 and isinstance(args[0], Iterator) else list(args)
         return MutableRoaringBitmap(_wide("or", bms)._buf)
 
@@ -983,7 +950,7 @@ class ImmutableRoaringBitmap(RoaringBitmap):
         if _is_range(args):
             return _range_op("xor_buffer", list(args[0]), args[1], args[2], MutableRoaringBitmap)
         x1, x2 = args
-        return ImmutableRoaringBitmap._bpair("xor", x1, x2)
+        return RoaringBitmap._pair("xor", x1, x2, MutableRoaringBitmap)
 
     @staticmethod
     def orNot(x1, x2, range_end):
@@ -1027,7 +994,7 @@ class MutableRoaringBitmap(ImmutableRoaringBitmap):
                 self._buf = EMPTY
                 self._lcard = 0
             return
-        self._buf = ImmutableRoaringBitmap._bpair(op, self, x2)._buf
+        self._buf = RoaringBitmap._pair(op, self, x2)._buf
         self._lcard = None
 
 
@@ -1077,7 +1044,3 @@ def run_optimize_many(bitmaps):
         b._buf = take(o)
         b._lcard = None
     return [bool(x) for x in ans]
-
-
-def _chain(*its):
-    return itertools.chain(*its)

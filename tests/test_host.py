@@ -52,8 +52,46 @@ def test_python_binding_covers_header():
     assert set(_declared()) <= set(L.EXPORTED)
 
 
+def test_signature_table_is_the_header():
+    """The binding's one table names exactly the functions the header declares, and lib() gives every one of
+    them its argtypes: an entry point without them would take a Python int as a C int, silently."""
+    declared = set(re.findall(r"\b(rbg_[a-z0-9_]+)\s*\(", open(HEADER).read()))
+    assert len(declared) == 101
+    assert set(L.SIGNATURES) == declared
+    for name in L.SIGNATURES:
+        assert getattr(L.lib(), name).argtypes is not None, name
+
+
 def test_version():
     assert L.lib().rbg_version() >= 1
+
+
+_BOTH = "Values should be non-negative and below 2^31"
+
+
+@pytest.mark.parametrize("columns, values, set_text, build_text", [
+    ([1, 2], [3], "columns and values differ in length", "columns and values differ in length"),
+    ([1, 2], [3, -1], _BOTH, "Values should be non-negative"),
+    ([1, 2], [3, 1 << 31], _BOTH, "Values should be below 2^31"),
+])
+def test_pairs_are_refused_before_any_library_call(monkeypatch, columns, values, set_text, build_text):
+    """The shared front of the (column, value) calls, through setValues (host and device form) and
+    through from_columns(gpu=True), which keeps its own texts: the refusal is Python's, the library is not
+    entered."""
+    import roaringbitmap_amd as rb
+    from roaringbitmap_amd import bsi
+    x = rb.RoaringBitmapSliceIndex.from_columns([1, 70000, 3], [5, 6, 7])
+    before = [b.serialize() for b in [x.ebM] + x.bA]
+
+    def no_library():
+        raise AssertionError("the library was entered")
+    monkeypatch.setattr(bsi, "lib", no_library)
+    for call, text in ((lambda: x.setValues(columns, values), set_text),
+                       (lambda: x.setValues(columns, values, gpu=True), set_text),
+                       (lambda: rb.RoaringBitmapSliceIndex.from_columns(columns, values, gpu=True), build_text)):
+        with pytest.raises(IllegalArgumentException, match="^" + re.escape(text) + "$"):
+            call()
+    assert [b.serialize() for b in [x.ebM] + x.bA] == before
 
 
 @pytest.mark.parametrize("mode", MODES)
