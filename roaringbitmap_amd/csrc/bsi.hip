@@ -846,13 +846,6 @@ __global__ __launch_bounds__(256) void k_bsi_defer(const Task* __restrict__ task
 // order.  With two or fewer the order does not matter (lazyOR is symmetric) and the
 // orInputs are chained as the spine makes them.
 
-__device__ __forceinline__ int bsi_card(const uint64_t r[4], int* sh) {
-  int c = popc64(r[0]) + popc64(r[1]) + popc64(r[2]) + popc64(r[3]);
-  int u = 0;
-  block_sum2(c, u, sh);
-  return (int)uni((uint32_t)c);
-}
-
 // horizontal_or's per-key chain (RB/buffer/BufferFastAggregation.java:200-233): one container
 // is cloned; else x1.lazyOR(x2), lazyIOR of the rest, repairAfterLazy.  The state is the
 // container class of the running union (the machine of WIDE_LAZY_CHAIN in wide.hip):
@@ -881,11 +874,11 @@ __device__ __forceinline__ void hchain_add(HChain& h, const VB& x, uint32_t* lds
   if (h.st == DK_B) {
   } else if (h.st == DK_A && x.kind == DK_A) {
     if (h.cur + x.card > 1024) h.st = DK_B;
-    else h.cur = bsi_card(h.acc.r, sh);
+    else h.cur = block_card(h.acc.r, sh);
   } else if (x.kind == DK_B) {
     h.st = DK_B;
   } else if (h.st == DK_R && x.kind == DK_R) {
-    const int cc = bsi_card(h.acc.r, sh);
+    const int cc = block_card(h.acc.r, sh);
     h.st = eff(cc, count_runs(h.acc.r, lds, sh));
     h.cur = cc;
   } else {
@@ -900,7 +893,7 @@ __device__ __forceinline__ void hchain_finish(HChain& h, VB& out, uint32_t* lds,
   }
   out = h.acc;
   if (h.n == 1) return;  // x1.getContainer().clone()
-  const int c = bsi_card(out.r, sh);
+  const int c = block_card(out.r, sh);
   out.kind = h.st == DK_B ? (c == 65536 ? DK_R : by_card(c)) : h.st == DK_R ? eff(c, count_runs(out.r, lds, sh)) : DK_A;
   out.card = c;
   out.src = -1;

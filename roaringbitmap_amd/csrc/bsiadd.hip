@@ -37,13 +37,6 @@ __global__ __launch_bounds__(256) void k_bsia_keys(const uint16_t* __restrict__ 
     flag[i < na ? ka[i] : kb[i - na]] = 1;
 }
 
-// the container of input j in the key's segment [p, e) of a key-major batch (sorted by input): p moves
-// past the inputs below j; wave-uniform
-__device__ __forceinline__ bool bsia_find(const BsiAddSide& s, uint32_t& p, uint32_t e, uint32_t j) {
-  while (p < e && s.bm[p] < j) p++;
-  return p < e && s.bm[p] == j;
-}
-
 // cell (ki, j) of the pass at ws + 8192 ((ki - k_lo) m + j), m = 2 + max(na, nb); ebm_run[ki]: ebM' is full
 // and the reference holds it as a run container
 __global__ __launch_bounds__(256) void k_bsi_add(const BsiAddSide A, const BsiAddSide B,
@@ -66,7 +59,7 @@ __global__ __launch_bounds__(256) void k_bsi_add(const BsiAddSide A, const BsiAd
   uint8_t* cell = ws + 8192ull * ((uint64_t)(ki - k_lo) * (uint64_t)m);
   WCtr x, y, c;
   {  // ebM' = ebM_a | ebM_b (this.ebM.or(otherBsi.ebM), in place)
-    const bool ha = bsia_find(A, pa, ea, 0), hb = bsia_find(B, pb, eb, 0);
+    const bool ha = seg_find(A.bm, pa, ea, 0), hb = seg_find(B.bm, pb, eb, 0);
     int kind_b = -1;
     if (ha) w_materialize(A.desc[pa], A.payload, lds, x);
     else w_zero(x);
@@ -89,7 +82,7 @@ __global__ __launch_bounds__(256) void k_bsi_add(const BsiAddSide A, const BsiAd
   const int top = m - 2;  // max(na, nb)
   for (int i = 0; i < top; i++) {
     const uint32_t j = (uint32_t)i + 1;
-    const bool ha = i < A.n && bsia_find(A, pa, ea, j), hb = i < B.n && bsia_find(B, pb, eb, j);
+    const bool ha = i < A.n && seg_find(A.bm, pa, ea, j), hb = i < B.n && seg_find(B.bm, pb, eb, j);
     if (ha) w_materialize(A.desc[pa], A.payload, lds, x);
     else w_zero(x);
     if (hb) w_materialize(B.desc[pb], B.payload, lds, y);

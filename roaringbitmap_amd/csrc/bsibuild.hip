@@ -7,23 +7,23 @@
 //   k_bld_keys / k_bld_key_scan (build.hip) on the columns: the K present keys and the CSR key -> key index
 //   k_bsib_scatter  a zeroed workspace holds, for every key index of the pass, m = nbits + 1 bitmaps of
 //                   8 KiB: input 0 (ebM), then the slices.  Every pair ORs its column's bit into input 0
-//                   and into input 1 + i for every set bit i of its value.  As in k_bld_scatter, lanes
-//                   whose neighbours hit the same 32-bit word combine their bits first and only the last
-//                   lane of such a group issues the atomic, after reading the word.
+//                   and into input 1 + i for every set bit i of its value: one atomic per group of
+//                   neighbouring lanes that hit the same 32-bit word (wave.hpp: LaneGroup, computed once per
+//                   round since the inputs of a pair share the word), after reading the word.
 //   k_bsib_plan     one wave per (key index, input): cardinality (and run count), the container's type
 //                   and slot size; an empty bitmap is no container.  A wave keeps one input, so the
 //                   per-input totals (containers, cardinality, serialized bytes, run containers) cost
 //                   one set of atomics per wave.
 //   (one scan of [container count << 40 | slot bytes] over the (key index, input) cells: key-major order)
-//   k_bsib_write    one wave per non-empty cell: the slot, the CDesc, keys[], bm[] = input
+//   k_bsib_write    one wave per non-empty cell: the slot (wave.hpp: w_write_slot), the CDesc, keys[],
+//                   bm[] = input
 //   k_bsib_key_off  the batch's key CSR over its containers
 //
 // (bsiadd.hip fills the same workspace with the sum of two indexes and shares the plan, scan, write and key
 // CSR stages; its only extension is the plan's ebm_run flag.  bsiin.hip fills it with one cell per key, the
 // result of an IN-list query, and passes its full-container flag through the same argument.)
 //
-// Types as in build.hip: card <= 4096 -> A, else B; with run_optimize A -> R iff 2 card > 2 + 4 nruns,
-// B -> R iff 2 + 4 nruns < 8192.
+// Types: by_card, and with run_optimize runopt_kind (device.hpp).
 //
 // The workspace is K x m x 8 KiB, so the engine walks the key indices in passes [k_lo, k_hi) under a byte
 // budget; a pass scatters only the pairs whose key index it covers.
@@ -55,21 +55,6 @@ __global__ __launch_bounds__(256) void k_bsib_minmax(const int32_t* __restrict__
   }
 }
 
-// lane l receives lane l + 1's value; lane 63 receives `last`
-__device__ __forceinline__ uint32_t bsib_next_lane_or(uint32_t x, uint32_t last) {
-  return __builtin_amdgcn_update_dpp(last, x, 0x130, 0xf, 0xf, false);  // wave_shl:1
-}
-
-// One DPP step of the combining scan (k_bld_scatter's): a lane ORs in the bits of the lane `ctrl` points
-// at when both address the same word (same: computed once per round, the inputs of a pair share it).  A
-// lane without a source reads its own bits back: harmless.
-#define BSIB_SAME(ctrl, rmask) (__builtin_amdgcn_update_dpp(idx, idx, ctrl, rmask, 0xf, false) == idx)
-#define BSIB_STEP(same, ctrl, rmask)                                                      \
-  {                                                                                       \
-    const uint32_t sb = __builtin_amdgcn_update_dpp(bits, bits, ctrl, rmask, 0xf, false); \
-    bits |= same ? sb : 0u;                                                               \
-  }
-
 // Every wave runs whole rounds of 64 pairs and the loop over the m inputs is wave-uniform, so every lane
 // takes part in every scan; a lane past the end or outside the pass holds a word index no pair has and no
 // bits.  ws: (k_hi - k_lo) x m bitmaps; the word index (< 2^31: the engine bounds a pass) of input j is
@@ -92,18 +77,10 @@ __global__ __launch_bounds__(256) void k_bsib_scatter(const uint32_t* __restrict
       }
     }
     if (__ballot(mask != 0) == 0) continue;  // wave-uniform: no pair of the round belongs to the pass
-    const bool s1 = BSIB_SAME(0x111, 0xf), s2 = BSIB_SAME(0x112, 0xf), s4 = BSIB_SAME(0x114, 0xf),
-               s8 = BSIB_SAME(0x118, 0xf), s15 = BSIB_SAME(0x142, 0xa), s31 = BSIB_SAME(0x143, 0xc);
-    const bool last = bsib_next_lane_or(idx, 0xFFFFFFFFu) != idx;
+    const LaneGroup g = lane_group(idx);
     for (int j = 0; j < m; j++) {
-      uint32_t bits = (mask >> j) & 1u ? bit : 0u;
-      BSIB_STEP(s1, 0x111, 0xf)    // row_shr:1
-      BSIB_STEP(s2, 0x112, 0xf)    // row_shr:2
-      BSIB_STEP(s4, 0x114, 0xf)    // row_shr:4
-      BSIB_STEP(s8, 0x118, 0xf)    // row_shr:8
-      BSIB_STEP(s15, 0x142, 0xa)   // row_bcast:15 -> rows 1, 3
-      BSIB_STEP(s31, 0x143, 0xc)   // row_bcast:31 -> rows 2, 3
-      if (bits && last) {
+      const uint32_t bits = g.merge((mask >> j) & 1u ? bit : 0u);
+      if (bits && g.last) {
         uint32_t* w = ws + ((uint64_t)idx + 2048u * (uint32_t)j);
         const uint32_t cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((cur & bits) != bits) atomicOr(w, bits);
@@ -111,8 +88,6 @@ __global__ __launch_bounds__(256) void k_bsib_scatter(const uint32_t* __restrict
     }
   }
 }
-#undef BSIB_STEP
-#undef BSIB_SAME
 
 struct BsibInfo {
   uint32_t card;  // 0: no container
@@ -151,16 +126,16 @@ __global__ __launch_bounds__(256) void k_bsib_plan(const uint8_t* __restrict__ w
     int kind = by_card(card), nruns = 0;
     if (run_optimize) {
       nruns = w_runs(x);
-      if (kind == DK_A ? 2 * card > 2 + 4 * nruns : 2 + 4 * nruns < 8192) kind = DK_R;
+      kind = runopt_kind(kind, card, nruns);
     }
     if (ebm_run && j == 0 && ebm_run[ki]) {  // the full ebM' of bsiadd.hip (wave-uniform)
       kind = DK_R;
       nruns = 1;
     }
-    const uint32_t len = kind == DK_A ? 2u * card : kind == DK_B ? 8192u : 2u + 4u * nruns;
+    const uint32_t len = ser_len_of(kind, (uint32_t)card, (uint32_t)nruns);
     if (lane == 0) {
       info[cell] = BsibInfo{(uint32_t)card, (uint16_t)nruns, (uint8_t)kind, 0};
-      size[cell] = (1ull << kBsibCountShift) | (uint64_t)((len + (kind == DK_R ? 2u : 0u) + 15u) & ~15u);
+      size[cell] = (1ull << kBsibCountShift) | slot_bytes(kind, len);
     }
     cnt[kind]++;
     ser += len;
@@ -196,27 +171,10 @@ __global__ __launch_bounds__(256, 4) void k_bsib_write(const uint8_t* __restrict
     if (in.card == 0) continue;  // wave-uniform
     const uint64_t sc = scan[cell];
     const uint64_t o = sc & ((1ull << kBsibCountShift) - 1), ci = sc >> kBsibCountShift;
-    uint8_t* dst = payload + o;
-    const int kind = in.kind, card = (int)in.card;
+    const int kind = in.kind;
     WCtr x;
     w_load_bitmap(ws + 8192ull * i, x);
-    if (kind == DK_B) {
-      w_store_bitmap(dst, x);
-    } else {
-      uint32_t copy = w_stage(kind, x, card, lds);
-      if (kind == DK_A) {  // pad the slot to 16 B with the last value (batch layout)
-        uint16_t* st = reinterpret_cast<uint16_t*>(lds);
-        const uint32_t c = in.card, padded = (2u * c + 15) & ~15u;
-        const uint16_t last = st[c - 1];
-        for (uint32_t q = c + lane; q < padded / 2; q += 64) st[q] = last;
-        wsync();
-        copy = padded;
-      } else if (lane == 0) {
-        *reinterpret_cast<uint16_t*>(dst) = 0;  // the u16 in front of the run count
-      }
-      copy_lds_to_global<64>(dst + (kind == DK_R ? 2 : 0), lds, copy, lane);
-      wsync();
-    }
+    w_write_slot(kind, x, (int)in.card, lds, payload + o);
     if (lane == 0) {
       const uint16_t key = pkeys[k_lo + i / (uint64_t)m];
       desc[ci] = CDesc{o, in.card, key, (uint8_t)kind, 0};
@@ -236,19 +194,15 @@ __global__ __launch_bounds__(256) void k_bsib_key_off(const uint32_t* __restrict
   key_off[k] = (uint32_t)(scan[(uint64_t)pkey_off[k] * m] >> kBsibCountShift);
 }
 
-static unsigned bsib_grid(uint64_t items, uint64_t per_block, uint64_t cap) {
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + per_block - 1) / per_block, cap));
-}
-
 void launch_bsib_minmax(hipStream_t s, const int32_t* v, uint64_t n, int* mm) {
   if (!n) return;
-  hipLaunchKernelGGL(k_bsib_minmax, dim3(bsib_grid(n, 1024, 2048)), dim3(256), 0, s, v, n, mm);
+  hipLaunchKernelGGL(k_bsib_minmax, dim3(grid_for(n, 1024, 2048)), dim3(256), 0, s, v, n, mm);
 }
 
 void launch_bsib_scatter(hipStream_t s, const uint32_t* col, const int32_t* val, uint64_t n, const uint32_t* pkey_off,
                          uint32_t k_lo, uint32_t k_hi, int m, uint32_t* ws) {
   if (!n || k_hi <= k_lo) return;
-  const dim3 grid(bsib_grid(n, 256, 256 * 16)), block(256);
+  const dim3 grid(grid_for(n, 256, 256 * 16)), block(256);
   hipLaunchKernelGGL(k_bsib_scatter, grid, block, 0, s, col, val, n, pkey_off, k_lo, k_hi, m, ws);
 }
 
@@ -265,7 +219,7 @@ void launch_bsib_write(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t
                        const uint64_t* scan, const uint16_t* pkeys, CDesc* desc, uint16_t* keys, uint32_t* bm,
                        uint8_t* payload) {
   if (k_hi <= k_lo) return;
-  hipLaunchKernelGGL(k_bsib_write, dim3(bsib_grid((uint64_t)(k_hi - k_lo) * m, 4, 4096)), dim3(256), 0, s, ws, k_lo,
+  hipLaunchKernelGGL(k_bsib_write, dim3(grid_for((uint64_t)(k_hi - k_lo) * m, 4, 4096)), dim3(256), 0, s, ws, k_lo,
                      k_hi, m, reinterpret_cast<const BsibInfo*>(info), scan, pkeys, desc, keys, bm, payload);
 }
 

@@ -17,9 +17,10 @@
 //   k_bsis_apply    one pair per lane; the pair that holds its column's table entry ORs the column's bit into
 //                   ebM's cell and, per slice i < d', ORs it in where bit i of the value is set and ANDs it
 //                   out otherwise (BSI/:304-313).  One pair per column applies, so a bit is never set and
-//                   cleared in one pass; different columns of a word meet in atomics.  As in k_bsib_scatter,
-//                   lanes whose neighbours hit the same 32-bit word combine their bits first, and the last
-//                   lane of such a group reads the word and issues an atomic only for what would change.
+//                   cleared in one pass; different columns of a word meet in atomics.  Lanes whose neighbours
+//                   hit the same 32-bit word combine their bits first (wave.hpp: LaneGroup, over two words:
+//                   the bits to set and the bits to clear), and the last lane of such a group reads the word
+//                   and issues an atomic only for what would change.
 //
 // Types: ArrayContainer.add turns into a bitmap container above 4,096 values (RB/ArrayContainer.java:143-171),
 // BitmapContainer.remove into an array container at 4,096 (RB/BitmapContainer.java:1184-1202),
@@ -32,12 +33,6 @@
 #include "wave.hpp"
 
 namespace rbg {
-
-// the container of input j in the key's segment [p, e) of a key-major batch (sorted by input); wave-uniform
-__device__ __forceinline__ bool bsis_find(const BsiAddSide& s, uint32_t& p, uint32_t e, uint32_t j) {
-  while (p < e && s.bm[p] < j) p++;
-  return p < e && s.bm[p] == j;
-}
 
 // cell (ki, j) of the pass at ws + 8192 ((ki - k_lo) m + j), m = 1 + d' >= 1 + A.n
 __global__ __launch_bounds__(256) void k_bsis_expand(const BsiAddSide A, const uint16_t* __restrict__ pkeys,
@@ -55,7 +50,7 @@ __global__ __launch_bounds__(256) void k_bsis_expand(const BsiAddSide A, const u
   bool run = false, refused = false;
   for (int j = 0; j < m; j++) {
     w_zero(x);
-    if (j <= A.n && bsis_find(A, p, e, (uint32_t)j)) {
+    if (j <= A.n && seg_find(A.bm, p, e, (uint32_t)j)) {
       const CDesc d = A.desc[p];
       if (d.kind != DK_R) {
         w_materialize(d, A.payload, lds, x);
@@ -89,21 +84,6 @@ __global__ __launch_bounds__(256) void k_bsis_last(const uint32_t* __restrict__ 
   }
 }
 
-// lane l receives lane l + 1's value; lane 63 receives `last`
-__device__ __forceinline__ uint32_t bsis_next_lane_or(uint32_t x, uint32_t last) {
-  return __builtin_amdgcn_update_dpp(last, x, 0x130, 0xf, 0xf, false);  // wave_shl:1
-}
-
-// One DPP step of k_bsib_scatter's combining scan over two words: the bits to set and the bits to clear
-#define BSIS_SAME(ctrl, rmask) (__builtin_amdgcn_update_dpp(idx, idx, ctrl, rmask, 0xf, false) == idx)
-#define BSIS_STEP(same, ctrl, rmask)                                                          \
-  {                                                                                           \
-    const uint32_t sb = __builtin_amdgcn_update_dpp(sbits, sbits, ctrl, rmask, 0xf, false);   \
-    const uint32_t cb = __builtin_amdgcn_update_dpp(cbits, cbits, ctrl, rmask, 0xf, false);   \
-    sbits |= same ? sb : 0u;                                                                  \
-    cbits |= same ? cb : 0u;                                                                  \
-  }
-
 // Every wave runs whole rounds of 64 pairs and the loop over the m cells is wave-uniform, so every lane takes
 // part in every scan; a lane past the end, outside the pass or overruled by a later pair holds a word index no
 // pair has and no bits.  tab: k_bsis_last's.
@@ -128,19 +108,11 @@ __global__ __launch_bounds__(256) void k_bsis_apply(const uint32_t* __restrict__
       }
     }
     if (__ballot(mask != 0) == 0) continue;  // wave-uniform: no pair of the round applies in the pass
-    const bool s1 = BSIS_SAME(0x111, 0xf), s2 = BSIS_SAME(0x112, 0xf), s4 = BSIS_SAME(0x114, 0xf),
-               s8 = BSIS_SAME(0x118, 0xf), s15 = BSIS_SAME(0x142, 0xa), s31 = BSIS_SAME(0x143, 0xc);
-    const bool last = bsis_next_lane_or(idx, 0xFFFFFFFFu) != idx;
+    const LaneGroup g = lane_group(idx);
     for (int j = 0; j < m; j++) {
       const bool on = (mask >> j) & 1u;
-      uint32_t sbits = on ? bit : 0u, cbits = on ? 0u : bit;
-      BSIS_STEP(s1, 0x111, 0xf)    // row_shr:1
-      BSIS_STEP(s2, 0x112, 0xf)    // row_shr:2
-      BSIS_STEP(s4, 0x114, 0xf)    // row_shr:4
-      BSIS_STEP(s8, 0x118, 0xf)    // row_shr:8
-      BSIS_STEP(s15, 0x142, 0xa)   // row_bcast:15 -> rows 1, 3
-      BSIS_STEP(s31, 0x143, 0xc)   // row_bcast:31 -> rows 2, 3
-      if (last && idx != 0xFFFFFFFFu) {
+      const uint32_t sbits = g.merge(on ? bit : 0u), cbits = g.merge(on ? 0u : bit);
+      if (g.last && idx != 0xFFFFFFFFu) {
         uint32_t* w = ws + ((uint64_t)idx + 2048u * (uint32_t)j);
         const uint32_t cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if ((cur & sbits) != sbits) atomicOr(w, sbits);
@@ -148,12 +120,6 @@ __global__ __launch_bounds__(256) void k_bsis_apply(const uint32_t* __restrict__
       }
     }
   }
-}
-#undef BSIS_STEP
-#undef BSIS_SAME
-
-static unsigned bsis_grid(uint64_t items, uint64_t per_block, uint64_t cap) {
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + per_block - 1) / per_block, cap));
 }
 
 void launch_bsis_expand(hipStream_t s, BsiAddSide a, const uint16_t* pkeys, uint32_t k_lo, uint32_t k_hi, int m,
@@ -166,13 +132,13 @@ void launch_bsis_expand(hipStream_t s, BsiAddSide a, const uint16_t* pkeys, uint
 void launch_bsis_last(hipStream_t s, const uint32_t* col, uint64_t n, const uint32_t* pkey_off, uint32_t k_lo,
                       uint32_t k_hi, uint32_t* tab) {
   if (!n || k_hi <= k_lo) return;
-  hipLaunchKernelGGL(k_bsis_last, dim3(bsis_grid(n, 1024, 4096)), dim3(256), 0, s, col, n, pkey_off, k_lo, k_hi, tab);
+  hipLaunchKernelGGL(k_bsis_last, dim3(grid_for(n, 1024, 4096)), dim3(256), 0, s, col, n, pkey_off, k_lo, k_hi, tab);
 }
 
 void launch_bsis_apply(hipStream_t s, const uint32_t* col, const int32_t* val, uint64_t n, const uint32_t* pkey_off,
                        uint32_t k_lo, uint32_t k_hi, int m, const uint32_t* tab, uint32_t* ws) {
   if (!n || k_hi <= k_lo) return;
-  hipLaunchKernelGGL(k_bsis_apply, dim3(bsis_grid(n, 256, 256 * 16)), dim3(256), 0, s, col, val, n, pkey_off, k_lo,
+  hipLaunchKernelGGL(k_bsis_apply, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, col, val, n, pkey_off, k_lo,
                      k_hi, m, tab, ws);
 }
 

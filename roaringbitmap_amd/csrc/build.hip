@@ -8,22 +8,16 @@
 //   k_bld_key_scan scans the 65,536 flags (256 workgroups of 256 keys): keys[], the key CSR
 //                  key_off[65537] (key_off[k] is also key k's container index), the container count C
 //   k_bld_scatter  ORs every value's bit into its container's 8 KiB bitmap of a zeroed workspace
-//                  (C bitmaps).  Lanes of a wave whose neighbours hit the same 32-bit word
-//                  combine their bits first (a DPP scan over the lanes); only the last lane of
-//                  each group of equal neighbours issues the atomic, so sorted, clustered or
-//                  repeated input does not serialise 64 atomics at one address.
+//                  (C bitmaps), one atomic per group of neighbouring lanes that hit the same
+//                  32-bit word (wave.hpp: LaneGroup)
 //   k_bld_plan     one wave per container: cardinality (and run count) from registers, the
 //                  container's type and slot size, the batch totals
 //   (scan of the slot sizes)
-//   k_bld_write    one wave per container: the slot (A padded to 16 B with its last value,
-//                  R = [u16 pad][u16 nruns][u32 (start, len - 1)]), the CDesc, keys[], bm[] = 0
+//   k_bld_write    one wave per container: the slot (wave.hpp: w_write_slot), the CDesc, keys[],
+//                  bm[] = 0
 //
-// Types (format.cpp: make_ctr with kind_hint -1): card <= 4096 -> A, else B; with run_optimize
-// A -> R iff 2 card > 2 + 4 nruns (RB/ArrayContainer.java:1085-1099), B -> R iff
-// 2 + 4 nruns < 8192 (RB/BitmapContainer.java:1218-1237).  Either way a run result has at most
-// 2,047 runs, so it fits the wave's 8 KiB stage.
-#include <algorithm>
-
+// Types (format.cpp: make_ctr with kind_hint -1): by_card, and with run_optimize runopt_kind
+// (device.hpp).
 #include "kernels.hpp"
 #include "wave.hpp"
 
@@ -70,21 +64,6 @@ __global__ __launch_bounds__(256) void k_bld_key_scan(const uint8_t* __restrict_
   }
 }
 
-// lane l receives lane l + 1's value; lane 63 receives `last`
-__device__ __forceinline__ uint32_t next_lane_or(uint32_t x, uint32_t last) {
-  return __builtin_amdgcn_update_dpp(last, x, 0x130, 0xf, 0xf, false);  // wave_shl:1
-}
-
-// One DPP step of the combining scan: a lane ORs in the bits of the lane `ctrl` points at when both
-// address the same word.  A lane without a source keeps its own word index as the source's (old =
-// its own values), which ORs its own bits again: harmless.
-#define BLD_STEP(ctrl, rmask)                                                                         \
-  {                                                                                                   \
-    const uint32_t si = __builtin_amdgcn_update_dpp(idx, idx, ctrl, rmask, 0xf, false);               \
-    const uint32_t sb = __builtin_amdgcn_update_dpp(bits, bits, ctrl, rmask, 0xf, false);             \
-    bits |= si == idx ? sb : 0u;                                                                      \
-  }
-
 // Every wave runs whole rounds of 64 values (the trip count is wave-uniform, so every lane takes
 // part in every scan); a lane past the end holds a word index no value has and no bits.
 // The word is read first (from L2, where the atomics execute) and the atomic skipped when its bits
@@ -105,23 +84,14 @@ __global__ __launch_bounds__(256) void k_bld_scatter(const uint32_t* __restrict_
       idx = key_off[x >> 16] * 2048u + ((x & 0xFFFFu) >> 5);
       bits = 1u << (x & 31);
     }
-    // After the scan a lane holds the bits of every lane before it in its group of equal
-    // neighbours (a lane may also pick up bits of the same word from further away: they belong
-    // to the word too).
-    BLD_STEP(0x111, 0xf)  // row_shr:1
-    BLD_STEP(0x112, 0xf)  // row_shr:2
-    BLD_STEP(0x114, 0xf)  // row_shr:4
-    BLD_STEP(0x118, 0xf)  // row_shr:8
-    BLD_STEP(0x142, 0xa)  // row_bcast:15 -> rows 1, 3
-    BLD_STEP(0x143, 0xc)  // row_bcast:31 -> rows 2, 3
-    const uint32_t nxt = next_lane_or(idx, 0xFFFFFFFFu);
-    if (bits && nxt != idx) {
+    bits = merge_same_word(idx, bits);
+    const bool last = from_next_lane(idx, 0xFFFFFFFFu) != idx;
+    if (bits && last) {
       const uint32_t cur = __hip_atomic_load(&ws[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if ((cur & bits) != bits) atomicOr(&ws[idx], bits);
     }
   }
 }
-#undef BLD_STEP
 
 struct BldInfo {
   uint32_t card;
@@ -130,10 +100,6 @@ struct BldInfo {
   uint8_t pad;
 };
 static_assert(sizeof(BldInfo) == kBldInfoBytes, "the engine sizes the plan's table by kBldInfoBytes");
-
-__device__ __forceinline__ uint64_t bld_slot_size(int kind, uint32_t ser_len) {
-  return kind == DK_R ? (uint64_t)((ser_len + 2 + 15) & ~15u) : (uint64_t)((ser_len + 15) & ~15u);
-}
 
 // totals (u64, zeroed by the caller): [0..2] containers of kind A / B / R, [3] serialized payload
 // bytes, [4] cardinality
@@ -150,12 +116,12 @@ __global__ __launch_bounds__(256) void k_bld_plan(const uint8_t* __restrict__ ws
     int kind = by_card(card), nruns = 0;
     if (run_optimize) {
       nruns = w_runs(x);
-      if (kind == DK_A ? 2 * card > 2 + 4 * nruns : 2 + 4 * nruns < 8192) kind = DK_R;
+      kind = runopt_kind(kind, card, nruns);
     }
-    const uint32_t len = kind == DK_A ? 2u * card : kind == DK_B ? 8192u : 2u + 4u * nruns;
+    const uint32_t len = ser_len_of(kind, (uint32_t)card, (uint32_t)nruns);
     if (lane == 0) {
       info[i] = BldInfo{(uint32_t)card, (uint16_t)nruns, (uint8_t)kind, 0};
-      size[i] = bld_slot_size(kind, len);
+      size[i] = slot_bytes(kind, len);
     }
     cnt[kind]++;
     ser += len;
@@ -186,27 +152,10 @@ __global__ __launch_bounds__(256, 4) void k_bld_write(const uint8_t* __restrict_
   for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += nw) {
     const BldInfo in = info[i];
     const uint64_t o = off[i];
-    uint8_t* dst = payload + o;
-    const int kind = in.kind, card = (int)in.card;
+    const int kind = in.kind;
     WCtr x;
     w_load_bitmap(ws + 8192 * i, x);
-    if (kind == DK_B) {
-      w_store_bitmap(dst, x);
-    } else {
-      uint32_t copy = w_stage(kind, x, card, lds);
-      if (kind == DK_A) {  // pad the slot to 16 B with the last value (batch layout)
-        uint16_t* st = reinterpret_cast<uint16_t*>(lds);
-        const uint32_t c = in.card, padded = (2u * c + 15) & ~15u;
-        const uint16_t last = st[c - 1];
-        for (uint32_t q = c + lane; q < padded / 2; q += 64) st[q] = last;
-        wsync();
-        copy = padded;
-      } else if (lane == 0) {
-        *reinterpret_cast<uint16_t*>(dst) = 0;  // the u16 in front of the run count
-      }
-      copy_lds_to_global<64>(dst + (kind == DK_R ? 2 : 0), lds, copy, lane);
-      wsync();
-    }
+    w_write_slot(kind, x, (int)in.card, lds, payload + o);
     if (lane == 0) {
       desc[i] = CDesc{o, in.card, keys[i], (uint8_t)kind, 0};
       bm[i] = 0;
@@ -214,33 +163,29 @@ __global__ __launch_bounds__(256, 4) void k_bld_write(const uint8_t* __restrict_
   }
 }
 
-static unsigned bld_grid(uint64_t items, uint64_t per_block, uint64_t cap) {
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + per_block - 1) / per_block, cap));
-}
-
 void launch_bld_keys(hipStream_t s, const uint32_t* v, uint64_t n, uint8_t* flag, uint16_t* keys, uint32_t* key_off,
                      unsigned long long* n_ctr) {
-  if (n) hipLaunchKernelGGL(k_bld_keys, dim3(bld_grid(n, 256, 256 * 16)), dim3(256), 0, s, v, n, flag);
+  if (n) hipLaunchKernelGGL(k_bld_keys, dim3(grid_for(n, 256, 256 * 16)), dim3(256), 0, s, v, n, flag);
   hipLaunchKernelGGL(k_bld_key_scan, dim3(256), dim3(256), 0, s, (const uint8_t*)flag, keys, key_off, n_ctr);
 }
 
 void launch_bld_scatter(hipStream_t s, const uint32_t* v, uint64_t n, const uint32_t* key_off, uint32_t* ws) {
   if (!n) return;
-  const dim3 grid(bld_grid(n, 256, 256 * 16)), block(256);
+  const dim3 grid(grid_for(n, 256, 256 * 16)), block(256);
   hipLaunchKernelGGL(k_bld_scatter, grid, block, 0, s, v, n, key_off, ws);
 }
 
 void launch_bld_plan(hipStream_t s, const uint8_t* ws, uint64_t n_ctr, int run_optimize, void* info, uint64_t* size,
                      unsigned long long* totals) {
   if (!n_ctr) return;
-  hipLaunchKernelGGL(k_bld_plan, dim3(bld_grid(n_ctr, 4, 4096)), dim3(256), 0, s, ws, n_ctr, run_optimize,
+  hipLaunchKernelGGL(k_bld_plan, dim3(grid_for(n_ctr, 4, 4096)), dim3(256), 0, s, ws, n_ctr, run_optimize,
                      reinterpret_cast<BldInfo*>(info), size, totals);
 }
 
 void launch_bld_write(hipStream_t s, const uint8_t* ws, uint64_t n_ctr, const void* info, const uint64_t* off,
                       const uint16_t* keys, CDesc* desc, uint32_t* bm, uint32_t* bm_off, uint8_t* payload) {
   if (!n_ctr) return;
-  hipLaunchKernelGGL(k_bld_write, dim3(bld_grid(n_ctr, 4, 4096)), dim3(256), 0, s, ws, n_ctr,
+  hipLaunchKernelGGL(k_bld_write, dim3(grid_for(n_ctr, 4, 4096)), dim3(256), 0, s, ws, n_ctr,
                      reinterpret_cast<const BldInfo*>(info), off, keys, desc, bm, bm_off, payload);
 }
 

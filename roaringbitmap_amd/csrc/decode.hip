@@ -278,17 +278,13 @@ __global__ __launch_bounds__(256) void k_dec_key_off(const uint16_t* __restrict_
   key_off[k] = (uint32_t)lo;
 }
 
-__device__ __forceinline__ uint64_t dec_slot_bytes(uint32_t kind, uint32_t len) {
-  return kind == DK_R ? (uint64_t)((len + 2 + 15) & ~15u) : (uint64_t)((len + 15) & ~15u);
-}
-
 __global__ __launch_bounds__(256) void k_dec_sizes(const DecCtr* __restrict__ q, const uint32_t* __restrict__ perm,
                                                    uint64_t C, uint64_t* __restrict__ size,
                                                    unsigned long long* __restrict__ totals, int packed) {
   uint64_t cnt[3] = {0, 0, 0}, big = 0;
   for (uint64_t p = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; p < C; p += (uint64_t)gridDim.x * blockDim.x) {
     const DecCtr c = q[perm ? perm[p] : p];
-    size[p] = packed && c.kind == DK_A ? (uint64_t)c.len : dec_slot_bytes(c.kind, c.len);
+    size[p] = packed && c.kind == DK_A ? (uint64_t)c.len : slot_bytes(c.kind, c.len);
     cnt[c.kind]++;
     if (c.len > 8194) big += c.len;
   }
@@ -329,7 +325,7 @@ __global__ __launch_bounds__(256) void k_dec_fill(const uint8_t* __restrict__ ra
     if (c.kind == DK_A && !packed) {  // pad the slot to 16 B with the last value
       const uint16_t last = (uint16_t)rd16b(raw + c.src + c.len - 2);
       uint16_t* d16 = reinterpret_cast<uint16_t*>(payload + off);
-      for (uint32_t v = c.len / 2 + lane; v < ((c.len + 15) & ~15u) / 2; v += 64) d16[v] = last;
+      for (uint32_t v = c.len / 2 + lane; v < (uint32_t)slot_bytes(DK_A, c.len) / 2; v += 64) d16[v] = last;
     }
     uint32_t card = c.card;
     if (c.kind == DK_R) {
@@ -357,14 +353,10 @@ __global__ __launch_bounds__(256) void k_iota(uint32_t* __restrict__ v, uint64_t
     v[i] = (uint32_t)i;
 }
 
-static unsigned grid_of(uint64_t n, uint64_t per, uint64_t cap) {
-  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((n + per - 1) / per, cap));
-}
-
 void launch_dec_head(hipStream_t s, const uint8_t* raw, const uint64_t* in_off, const uint64_t* in_len, uint64_t n,
                      DecHead* hd, uint64_t* nctr, uint64_t* nch, uint32_t* err, uint32_t* any_err) {
   if (!n) return;
-  hipLaunchKernelGGL(k_dec_head, dim3(grid_of(n, 256, 1u << 30)), dim3(256), 0, s, raw, in_off, in_len, n, hd, nctr,
+  hipLaunchKernelGGL(k_dec_head, dim3(grid_for(n, 256, 1u << 30)), dim3(256), 0, s, raw, in_off, in_len, n, hd, nctr,
                      nch, err, any_err);
 }
 
@@ -373,11 +365,11 @@ void launch_dec_ctrs(hipStream_t s, const uint8_t* raw, const uint64_t* in_off, 
                      const uint64_t* n_chunks, uint64_t max_chunks, uint32_t* map, DecCtr* q, uint16_t* qkey,
                      uint64_t* bm_card, uint32_t* bm_flag, uint64_t* consumed, uint32_t* err, uint32_t* any_err) {
   if (!n) return;
-  hipLaunchKernelGGL(k_dec_chunk_map, dim3(grid_of(n, 256, 1u << 30)), dim3(256), 0, s, nch, ch_base, n, map);
+  hipLaunchKernelGGL(k_dec_chunk_map, dim3(grid_for(n, 256, 1u << 30)), dim3(256), 0, s, nch, ch_base, n, map);
   if (max_chunks)
-    hipLaunchKernelGGL(k_dec_ctrs, dim3(grid_of(max_chunks, 4, 8192)), dim3(256), 0, s, raw, in_off, in_len,
+    hipLaunchKernelGGL(k_dec_ctrs, dim3(grid_for(max_chunks, 4, 8192)), dim3(256), 0, s, raw, in_off, in_len,
                        (const uint32_t*)map, ch_base, n_chunks, hd, ctr_base, q, qkey, bm_card, bm_flag, consumed);
-  hipLaunchKernelGGL(k_dec_finish, dim3(grid_of(n, 256, 1u << 30)), dim3(256), 0, s, raw, in_off, in_len, n, hd,
+  hipLaunchKernelGGL(k_dec_finish, dim3(grid_for(n, 256, 1u << 30)), dim3(256), 0, s, raw, in_off, in_len, n, hd,
                      ctr_base, (const uint32_t*)bm_flag, q, consumed, err, any_err);
 }
 
@@ -390,7 +382,7 @@ size_t dec_sort_temp_bytes(uint64_t C) {
 
 int launch_dec_sort(hipStream_t s, void* temp, size_t temp_bytes, const uint16_t* qkey, uint16_t* skey,
                     uint32_t* iota, uint32_t* perm, uint64_t C) {
-  hipLaunchKernelGGL(k_iota, dim3(grid_of(C, 256, 4096)), dim3(256), 0, s, iota, C);
+  hipLaunchKernelGGL(k_iota, dim3(grid_for(C, 256, 4096)), dim3(256), 0, s, iota, C);
   return (int)hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, qkey, skey, (const uint32_t*)iota, perm, (int)C, 0,
                                                  16, s);
 }
@@ -402,7 +394,7 @@ void launch_dec_key_off(hipStream_t s, const uint16_t* skey, uint64_t C, uint32_
 void launch_dec_sizes(hipStream_t s, const DecCtr* q, const uint32_t* perm, uint64_t C, uint64_t* size,
                       unsigned long long* totals, bool packed) {
   if (!C) return;
-  hipLaunchKernelGGL(k_dec_sizes, dim3(grid_of(C, 256, 1024)), dim3(256), 0, s, q, perm, C, size, totals,
+  hipLaunchKernelGGL(k_dec_sizes, dim3(grid_for(C, 256, 1024)), dim3(256), 0, s, q, perm, C, size, totals,
                      packed ? 1 : 0);
 }
 
@@ -410,7 +402,7 @@ void launch_dec_fill(hipStream_t s, const uint8_t* raw, const DecCtr* q, const u
                      const uint64_t* slot, uint64_t C, CDesc* desc, uint16_t* keys, uint32_t* bm, uint8_t* payload,
                      uint64_t* bm_card, bool packed) {
   if (!C) return;
-  hipLaunchKernelGGL(k_dec_fill, dim3(grid_of(C, 4, 8192)), dim3(256), 0, s, raw, q, qkey, perm, slot, C, desc, keys,
+  hipLaunchKernelGGL(k_dec_fill, dim3(grid_for(C, 4, 8192)), dim3(256), 0, s, raw, q, qkey, perm, slot, C, desc, keys,
                      bm, payload, bm_card, packed ? 1 : 0);
 }
 

@@ -33,6 +33,14 @@ struct __align__(16) CDesc {
   uint8_t kind;
   uint8_t flags;
 };
+// Serialized payload bytes of a container, and the bytes of its slot: 16 B aligned, a run slot with
+// the u16 in front of its run count.  Every kernel that sizes or places a slot goes through these two.
+__host__ __device__ __forceinline__ uint32_t ser_len_of(int kind, uint32_t card, uint32_t nruns) {
+  return kind == DK_A ? 2u * card : kind == DK_B ? 8192u : 2u + 4u * nruns;
+}
+__host__ __device__ __forceinline__ uint64_t slot_bytes(int kind, uint32_t ser_len) {
+  return kind == DK_R ? (uint64_t)((ser_len + 2 + 15) & ~15u) : (uint64_t)((ser_len + 15) & ~15u);
+}
 
 // Output container descriptor (32 B) produced by an op, consumed by the emitter.
 struct __align__(16) ODesc {
@@ -199,6 +207,13 @@ __device__ __forceinline__ int eff(int c, int r) {
   const int arr_sz = 2 + 2 * c;
   return run_sz <= min(8192, arr_sz) ? DK_R : by_card(c);
 }
+// Container.runOptimize of an array or bitmap container of c values in r runs: A -> R iff
+// 2 c > 2 + 4 r (RB/ArrayContainer.java:1085-1099), B -> R iff 2 + 4 r < 8192
+// (RB/BitmapContainer.java:1218-1237).  Either way a run result has at most 2,047 runs, so it fits a
+// wave's 8 KiB stage.  (A run container goes through eff, RB/RunContainer.java:2083-2085.)
+__device__ __forceinline__ int runopt_kind(int kind, int c, int r) {
+  return (kind == DK_A ? 2 * c > 2 + 4 * r : 2 + 4 * r < 8192) ? DK_R : kind;
+}
 
 enum PairOp : int { OPR_AND = 0, OPR_OR = 1, OPR_XOR = 2, OPR_ANDNOT = 3 };  // == OpCode (kernels.hpp)
 
@@ -246,12 +261,12 @@ __device__ __forceinline__ int dpp_incl_scan(int x) {
 __device__ __forceinline__ int lane63(int x) { return __builtin_amdgcn_readlane(x, 63); }
 __device__ __forceinline__ uint32_t lane63u(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)x, 63); }
 __device__ __forceinline__ uint32_t lane0u(uint32_t x) { return (uint32_t)__builtin_amdgcn_readlane((int)x, 0); }
-// lane l receives lane l-1's / l+1's value; lane 0 / lane 63 receive 0
+// lane l receives lane l-1's / l+1's value; lane 0 receives 0, lane 63 `last`
 __device__ __forceinline__ uint32_t from_prev_lane(uint32_t x) {
   return __builtin_amdgcn_update_dpp(0u, x, 0x138, 0xf, 0xf, false);  // wave_shr:1
 }
-__device__ __forceinline__ uint32_t from_next_lane(uint32_t x) {
-  return __builtin_amdgcn_update_dpp(0u, x, 0x130, 0xf, 0xf, false);  // wave_shl:1
+__device__ __forceinline__ uint32_t from_next_lane(uint32_t x, uint32_t last = 0u) {
+  return __builtin_amdgcn_update_dpp(last, x, 0x130, 0xf, 0xf, false);  // wave_shl:1
 }
 
 __device__ __forceinline__ int wave_sum(int v) { return lane63(dpp_incl_scan(v)); }
@@ -281,6 +296,13 @@ __device__ __forceinline__ void block_sum2(int& a, int& b, int* sh) {
   a = sh[0] + sh[1] + sh[2] + sh[3];
   b = sh[4] + sh[5] + sh[6] + sh[7];
   lds_barrier();
+}
+// Cardinality of the workgroup's container from its owned words (wave-uniform); `sh` as above.
+__device__ __forceinline__ int block_card(const uint64_t r[4], int* sh) {
+  int c = __popcll(r[0]) + __popcll(r[1]) + __popcll(r[2]) + __popcll(r[3]);
+  int u = 0;
+  block_sum2(c, u, sh);
+  return __builtin_amdgcn_readfirstlane(c);
 }
 
 // Exclusive scan in word order (first halves of threads 0..255, then second

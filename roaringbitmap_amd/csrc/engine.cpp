@@ -187,10 +187,6 @@ int pinned_ensure(Ctx* c, size_t bytes) {
   return RBG_OK;
 }
 
-static inline uint64_t slot_bytes(uint8_t kind, uint32_t ser_len) {
-  return kind == KR ? round16(ser_len + 2) : round16(ser_len);
-}
-
 // epoch of the next pairwise plan (never 0, the value the tags start from)
 static uint32_t next_epoch(Ctx* c) {
   if (++c->epoch == 0) ++c->epoch;

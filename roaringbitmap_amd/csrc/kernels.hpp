@@ -2,9 +2,16 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+
 #include "device.hpp"
 
 namespace rbg {
+
+// workgroups of a grid-stride launch over `items` at `per_block` each: at least one, at most `cap`
+static inline unsigned grid_for(uint64_t items, uint64_t per_block, uint64_t cap) {
+  return (unsigned)std::max<uint64_t>(1, std::min<uint64_t>((items + per_block - 1) / per_block, cap));
+}
 
 enum OpCode : int { OP_AND = 0, OP_OR = 1, OP_XOR = 2, OP_ANDNOT = 3 };
 

@@ -3,15 +3,13 @@
 // the header decode) places slots with.
 //
 //   k_runopt : one wave per container decides the container's new type
-//                A -> R iff 2 card > 2 + 4 nruns  (RB/ArrayContainer.java:1085-1099),
-//                     nruns counted on the sorted values themselves;
-//                B -> R iff 2 + 4 nruns < 8192    (RB/BitmapContainer.java:1218-1237);
-//                R -> toEfficientContainer        (RB/RunContainer.java:2083-2085, 2326-2335)
-//                     on the stored run count, as the reference does;
+//                A, B -> runopt_kind (device.hpp), an array's runs counted on the sorted
+//                     values themselves;
+//                R -> eff (toEfficientContainer) on the stored run count, as the reference does;
 //              and writes it at its own slot offset in the new batch: an unchanged
 //              container's slot is copied verbatim (R kept as R is the reference's
 //              `return this`), a converted one is materialised in registers and
-//              staged through the wave's LDS.
+//              written by w_write_slot (wave.hpp).
 #include <algorithm>
 
 #include "kernels.hpp"
@@ -148,10 +146,6 @@ void launch_exclusive_scan(hipStream_t s, const uint64_t* in, uint64_t* out, uin
 // ---------------------------------------------------------------------------
 // runOptimize
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint64_t slot_size_of(int kind, uint32_t ser_len) {
-  return kind == DK_R ? (uint64_t)((ser_len + 2 + 15) & ~15u) : (uint64_t)((ser_len + 15) & ~15u);
-}
-
 // number of runs of a sorted array (<= 4096 values): 16 B vectors, all requested
 // at once; a value starts a run unless it follows its predecessor (the predecessor
 // of a vector's first value is the last value of the previous vector: the previous
@@ -222,22 +216,22 @@ __global__ __launch_bounds__(256, 4) void k_runopt(const CDesc* __restrict__ des
     WCtr x;
     if (d.kind == DK_A) {
       nruns = array_runs(slot, card);
-      kind = 2 * card > 2 + 4 * nruns ? DK_R : DK_A;
+      kind = runopt_kind(DK_A, card, nruns);
     } else if (d.kind == DK_B) {
       w_load_bitmap(slot, x);
       nruns = w_runs(x);
-      kind = 2 + 4 * nruns < 8192 ? DK_R : DK_B;
+      kind = runopt_kind(DK_B, card, nruns);
     } else {
       nruns = *reinterpret_cast<const uint16_t*>(slot + 2);
       kind = eff(card, nruns);
     }
-    const uint32_t len = kind == DK_A ? 2u * card : kind == DK_B ? 8192u : 2u + 4u * nruns;
+    const uint32_t len = ser_len_of(kind, (uint32_t)card, (uint32_t)nruns);
     if (kind == DK_B) {  // B kept, or R -> B
       if (d.kind != DK_B) w_materialize(d, payload, lds, x);
       w_store_bitmap(dst, x);
       wsync();
     } else if (kind == d.kind) {  // A or R kept: the slot as it is (A padding included)
-      const uint32_t nvec = (uint32_t)(slot_size_of(kind, len) >> 4);
+      const uint32_t nvec = (uint32_t)(slot_bytes(kind, len) >> 4);
       const uint4* sv = reinterpret_cast<const uint4*>(slot);
       uint4* dv = reinterpret_cast<uint4*>(dst);
       uint32_t j = lane;
@@ -249,19 +243,9 @@ __global__ __launch_bounds__(256, 4) void k_runopt(const CDesc* __restrict__ des
         dv[j + 192] = a3;
       }
       for (; j < nvec; j += 64) dv[j] = sv[j];
-    } else {  // A -> R, B -> R, R -> A: staged through the wave's LDS
+    } else {  // A -> R, B -> R, R -> A
       if (d.kind != DK_B) w_materialize(d, payload, lds, x);
-      uint32_t copy = w_stage(kind, x, card, lds);
-      if (kind == DK_A) {  // pad the slot to 16 B with the last value (batch layout)
-        uint16_t* st = reinterpret_cast<uint16_t*>(lds);
-        const uint32_t c = d.card, padded = (2u * c + 15) & ~15u;
-        const uint16_t last = st[c - 1];
-        for (uint32_t q = c + lane; q < padded / 2; q += 64) st[q] = last;
-        wsync();
-        copy = padded;
-      }
-      copy_lds_to_global<64>(dst + (kind == DK_R ? 2 : 0), lds, copy, lane);
-      wsync();
+      w_write_slot(kind, x, card, lds, dst);
     }
     if (lane == 0) out_desc[i] = CDesc{d.slot, d.card, d.key, (uint8_t)kind, d.flags};
     cnt[kind]++;
@@ -382,7 +366,7 @@ __global__ __launch_bounds__(256) void k_rsel_plan(const CDesc* __restrict__ des
     int kind = d.kind, card = keep_key ? (int)d.card : 0;
     uint32_t len = 0;
     if (keep_key && !cut) {
-      len = kind == DK_A ? 2u * card : kind == DK_B ? 8192u : 2u + 4u * *reinterpret_cast<const uint16_t*>(slot + 2);
+      len = ser_len_of(kind, (uint32_t)card, kind == DK_R ? *reinterpret_cast<const uint16_t*>(slot + 2) : 0u);
     } else if (cut && kind == DK_A) {
       int first;
       array_window(reinterpret_cast<const uint16_t*>(slot), card, lo, hi, &first, &card);
@@ -397,7 +381,7 @@ __global__ __launch_bounds__(256) void k_rsel_plan(const CDesc* __restrict__ des
       // buffer package's MappeableBitmapContainer.remove below 4096 (RB/buffer/MappeableBitmapContainer.java
       // :1597-1612), so a 4096-value bitmap stays one
       kind = (ra.buf ? card < 4096 : card <= 4096) ? DK_A : DK_B;
-      len = kind == DK_A ? 2u * card : 8192u;
+      len = ser_len_of(kind, (uint32_t)card, 0u);
     } else if (cut) {  // R
       int nr;
       run_window(slot, lo, hi, &nr, &card);
@@ -407,7 +391,7 @@ __global__ __launch_bounds__(256) void k_rsel_plan(const CDesc* __restrict__ des
     if (lane_id() == 0) {
       info[i] = (uint32_t)kind | (keep ? 4u : 0u) | (cut ? 8u : 0u);
       ncard[i] = (uint32_t)card;
-      size[i] = keep ? slot_size_of(kind, len) : 0;
+      size[i] = keep ? slot_bytes(kind, len) : 0;
       keepv[i] = keep ? 1 : 0;
       if (keep) {
         atomicAdd(&bm_cnt[bm[i]], 1ull);
@@ -456,10 +440,8 @@ __global__ __launch_bounds__(256, 4) void k_rsel_write(const CDesc* __restrict__
     const uint8_t* slot = payload + d.slot;
     uint8_t* dst = out_payload + o;
     if (!(inf & 8)) {  // inside the range: the slot as it is
-      const uint32_t len = kind == DK_A   ? 2u * card
-                           : kind == DK_B ? 8192u
-                                          : 2u + 4u * *reinterpret_cast<const uint16_t*>(slot + 2);
-      const uint32_t nvec = (uint32_t)(slot_size_of(kind, len) >> 4);
+      const uint32_t len = ser_len_of(kind, card, kind == DK_R ? *reinterpret_cast<const uint16_t*>(slot + 2) : 0u);
+      const uint32_t nvec = (uint32_t)(slot_bytes(kind, len) >> 4);
       const uint4* sv = reinterpret_cast<const uint4*>(slot);
       uint4* dv = reinterpret_cast<uint4*>(dst);
       for (uint32_t q = lane; q < nvec; q += 64) dv[q] = sv[q];
@@ -472,25 +454,14 @@ __global__ __launch_bounds__(256, 4) void k_rsel_write(const CDesc* __restrict__
         array_window(reinterpret_cast<const uint16_t*>(slot), (int)d.card, lo, hi, &first, &cnt);
         const uint16_t* v = reinterpret_cast<const uint16_t*>(slot) + first;
         uint16_t* w = reinterpret_cast<uint16_t*>(dst);
-        const int padded = (int)((2u * card + 15) & ~15u) / 2;
+        const int padded = (int)slot_bytes(DK_A, 2u * card) / 2;
         for (int x = lane; x < padded; x += 64) w[x] = v[min(x, (int)card - 1)];
       } else if (d.kind == DK_B) {
         WCtr x;
         w_load_bitmap(slot, x);
 #pragma unroll
         for (int k = 0; k < 16; k++) x.w[k] &= range_mask_word(k >> 1, k & 1, lo, hi);
-        if (kind == DK_B) {
-          w_store_bitmap(dst, x);
-        } else {
-          w_stage(DK_A, x, (int)card, lds);
-          uint16_t* st = reinterpret_cast<uint16_t*>(lds);
-          const uint32_t padded = (2u * card + 15) & ~15u;
-          const uint16_t last = st[card - 1];
-          for (uint32_t q = card + lane; q < padded / 2; q += 64) st[q] = last;
-          wsync();
-          copy_lds_to_global<64>(dst, lds, padded, lane);
-          wsync();
-        }
+        w_write_slot(kind == DK_B ? DK_B : DK_A, x, (int)card, lds, dst);  // the cut leaves B, or A at <= 4096 values
       } else {  // R: the overlapping runs, clipped, in order
         const int nr = *reinterpret_cast<const uint16_t*>(slot + 2);
         const uint32_t* pr = reinterpret_cast<const uint32_t*>(slot + 4);

@@ -70,6 +70,64 @@ __device__ __forceinline__ int wave_excl(int v, int* tot) {
   return s - v;
 }
 
+// The combining scan of the scatter kernels (k_bld_scatter, k_bsib_scatter, k_bsis_apply).  Every lane holds
+// a 32-bit word index and bits for that word; lanes whose neighbours hit the same word combine their bits
+// first and only the last lane of such a group issues the atomic, so sorted, clustered or repeated input
+// does not serialise 64 atomics at one address.  lane_group(idx) records, per step of a DPP inclusive scan
+// (dpp_incl_scan's), whether the lane the step points at addresses this lane's word; merge(bits) is that
+// scan with OR over the lanes that do.  After it a lane holds the bits of every lane before it in its
+// group of equal neighbours (it may also pick up bits of the same word from further away: they belong to
+// the word too).  A lane without a source reads its own values (old = its own), so it compares equal and
+// ORs its own bits again: harmless.  Every lane of the wave must take part.
+template <int CTRL, int ROWS>
+__device__ __forceinline__ uint32_t dpp_self(uint32_t x) {
+  return __builtin_amdgcn_update_dpp(x, x, CTRL, ROWS, 0xf, false);
+}
+struct LaneGroup {
+  bool s1, s2, s4, s8, s15, s31;  // same word as the lane row_shr:1 / 2 / 4 / 8, row_bcast:15 / 31 points at
+  bool last;                      // the next lane addresses another word (lane 63: always)
+  // one step: the DPP move is made by every lane (a lane that skipped it would not be there to be read)
+  // and only its result is selected
+  template <int CTRL, int ROWS>
+  static __device__ __forceinline__ uint32_t step(uint32_t bits, bool same) {
+    const uint32_t src = dpp_self<CTRL, ROWS>(bits);
+    return bits | (same ? src : 0u);
+  }
+  __device__ __forceinline__ uint32_t merge(uint32_t bits) const {
+    bits = step<0x111, 0xf>(bits, s1);
+    bits = step<0x112, 0xf>(bits, s2);
+    bits = step<0x114, 0xf>(bits, s4);
+    bits = step<0x118, 0xf>(bits, s8);
+    bits = step<0x142, 0xa>(bits, s15);  // rows 1, 3
+    bits = step<0x143, 0xc>(bits, s31);  // rows 2, 3
+    return bits;
+  }
+};
+// idx: below 0xFFFFFFFF for a lane with bits; a lane with nothing to write passes 0xFFFFFFFF and no bits
+__device__ __forceinline__ LaneGroup lane_group(uint32_t idx) {
+  LaneGroup g;
+  g.s1 = dpp_self<0x111, 0xf>(idx) == idx;
+  g.s2 = dpp_self<0x112, 0xf>(idx) == idx;
+  g.s4 = dpp_self<0x114, 0xf>(idx) == idx;
+  g.s8 = dpp_self<0x118, 0xf>(idx) == idx;
+  g.s15 = dpp_self<0x142, 0xa>(idx) == idx;
+  g.s31 = dpp_self<0x143, 0xc>(idx) == idx;
+  g.last = from_next_lane(idx, 0xFFFFFFFFu) != idx;
+  return g;
+}
+// The same scan for a kernel that merges one word per round (k_bld_scatter): every step fetches the source's
+// word index together with its bits, and no flag is kept.  (Through lane_group the kernel measured 10 %
+// slower on sorted input: profiles/device_helpers/README.md.)
+__device__ __forceinline__ uint32_t merge_same_word(uint32_t idx, uint32_t bits) {
+  bits = LaneGroup::step<0x111, 0xf>(bits, dpp_self<0x111, 0xf>(idx) == idx);
+  bits = LaneGroup::step<0x112, 0xf>(bits, dpp_self<0x112, 0xf>(idx) == idx);
+  bits = LaneGroup::step<0x114, 0xf>(bits, dpp_self<0x114, 0xf>(idx) == idx);
+  bits = LaneGroup::step<0x118, 0xf>(bits, dpp_self<0x118, 0xf>(idx) == idx);
+  bits = LaneGroup::step<0x142, 0xa>(bits, dpp_self<0x142, 0xa>(idx) == idx);  // rows 1, 3
+  bits = LaneGroup::step<0x143, 0xc>(bits, dpp_self<0x143, 0xc>(idx) == idx);  // rows 2, 3
+  return bits;
+}
+
 struct WCtr {
   uint64_t w[16];  // w[2*i + j] = container word 128*i + 2*lane + j
 };
@@ -398,7 +456,7 @@ __device__ __forceinline__ int w_stage_runs(const WCtr& x, uint32_t* lds);
 
 // Serialized payload of the owned container, staged in the wave's LDS
 // (A: u16 values; B: 1024 u64 words; R: u16 nruns + (start, len-1) pairs).
-// Returns the serialized length.
+// Returns the serialized length.  (w_write_slot, below copy_lds_to_global, writes it as a batch slot.)
 __device__ __forceinline__ uint32_t w_stage(int kind, const WCtr& x, int card, uint32_t* lds) {
   const int l = lane_id();
   if (kind == DK_B) {
@@ -449,6 +507,13 @@ __device__ __forceinline__ int lower_bound_u16(const uint16_t* keys, int n, uint
     else hi = mid;
   }
   return lo;
+}
+
+// The container of input j in a key's segment [p, e) of a key-major batch (bm: input per container, sorted
+// within a key): p moves past the inputs below j.  Wave-uniform.
+__device__ __forceinline__ bool seg_find(const uint32_t* bm, uint32_t& p, uint32_t e, uint32_t j) {
+  while (p < e && bm[p] < j) p++;
+  return p < e && bm[p] == j;
 }
 
 // Zeroes the output look-back state of the op about to run (block 0 of a plan
@@ -918,6 +983,32 @@ __device__ __forceinline__ void copy_lds_to_global(uint8_t* dst, const uint32_t*
   }
   const uint32_t done = head + body;
   for (uint32_t i = done / 2 + lane; i < n / 2; i += G) d16[i] = l16[i];
+}
+
+// The owned container as a slot of a batch (layout at CDesc) at dst, 16 B aligned: the one writer of a
+// computed slot (build.hip, bsibuild.hip, runopt.hip).  B goes from registers.  A is staged (w_stage) and
+// padded to 16 B with copies of its last value: ops read whole 16 B vectors of an array slot and rely on
+// the pad repeating a value of the set.  R (at most 2,047 runs) is staged behind a zeroed u16, which nothing
+// reads: a slot's bytes then do not depend on what its buffer held before.  `lds` is the wave's 8 KiB.
+__device__ __forceinline__ void w_write_slot(int kind, const WCtr& x, int card, uint32_t* lds, uint8_t* dst) {
+  if (kind == DK_B) {
+    w_store_bitmap(dst, x);
+    return;
+  }
+  const int lane = lane_id();
+  uint32_t copy = w_stage(kind, x, card, lds);
+  if (kind == DK_A) {
+    uint16_t* st = reinterpret_cast<uint16_t*>(lds);
+    const uint32_t c = (uint32_t)card, padded = (uint32_t)slot_bytes(DK_A, copy);
+    const uint16_t last = st[c - 1];
+    for (uint32_t q = c + lane; q < padded / 2; q += 64) st[q] = last;
+    wsync();
+    copy = padded;
+  } else if (lane == 0) {
+    *reinterpret_cast<uint16_t*>(dst) = 0;
+  }
+  copy_lds_to_global<64>(dst + (kind == DK_R ? 2 : 0), lds, copy, lane);
+  wsync();
 }
 
 // ---------------------------------------------------------------------------

@@ -128,13 +128,6 @@ __device__ __forceinline__ void stream_or_values(uint32_t* acc, const uint8_t* b
   }
 }
 
-__device__ __forceinline__ int block_card(const uint64_t r[4], int* sh) {
-  int c = popc64(r[0]) + popc64(r[1]) + popc64(r[2]) + popc64(r[3]);
-  int u = 0;
-  block_sum2(c, u, sh);
-  return (int)uni((uint32_t)c);
-}
-
 // FastAggregation result types (DESIGN.md §Type contract):
 //   naive_or  (RB/FastAggregation.java:603-610): n == 1 -> clone + repairAfterLazy
 //             (A, B unchanged; R -> toEfficientContainer); n >= 2 -> lazy bitmap

@@ -231,3 +231,21 @@ def sparse_bsi(rng, n_keys=6000, nbits=20):
 
 def random_values(rng, n, universe=1 << 32):
     return rng.integers(0, universe, size=n, dtype=np.int64).astype(np.uint32)
+
+
+# Cardinalities around the 8 values of a 16 B vector: an array slot is padded to 16 B with copies of its last
+# value, and ops read whole vectors of it.  One container per cardinality, keys 0..7.
+PAD_CARDS = (1, 2, 7, 8, 9, 15, 16, 17)
+
+
+def pad_lows(rng, shifted=False):
+    """-> per key of PAD_CARDS, that many sorted low halves in [100, 60100), at least 3 apart (away from 0 and
+    65535, never adjacent: such a set is an array container under every type rule); shifted: every second
+    value of a key moved up by one, which keeps them at least 2 apart"""
+    out = []
+    for c in PAD_CARDS:
+        lows = np.sort(rng.choice(20000, c, replace=False)).astype(np.int64) * 3 + 100
+        if shifted:
+            lows[1::2] += 1
+        out.append(lows)
+    return out

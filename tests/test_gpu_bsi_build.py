@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import _bsi
+import _gen
 import _oracle as O
 from _bsi import BSI
 
@@ -232,6 +233,51 @@ def test_as_bsi_operand(eng, ro):
     assert _fetch(eng, sb_) == _fetch(eng, sl_)
     for b in (built, loaded, sb_, sl_):
         eng.release(b)
+
+
+def _pad_pairs(values):
+    """PAD_CARDS[k] columns under key k (never adjacent); every value 3, or values drawn from {1, 2, 3}"""
+    rng = np.random.default_rng(62)
+    cols = np.concatenate([(k << 16) | lows for k, lows in enumerate(_gen.pad_lows(rng))])
+    vals = np.full(cols.size, 3) if values == "all_3" else rng.integers(1, 4, size=cols.size)
+    p = rng.permutation(cols.size)
+    return cols[p], vals[p]
+
+
+@pytest.mark.parametrize("ro", [False, True])
+@pytest.mark.parametrize("values", ["all_3", "of_1_2_3"])
+def test_array_slot_padding(eng, values, ro):
+    """k_bsib_write's array slots are padded to 16 B with copies of their last value: small array containers of
+    ebM and both slices, read by the BSI ops in whole 16 B vectors, against the loaded batch of the oracle's
+    bitmaps and the oracle's own answers"""
+    cols, vals = _pad_pairs(values)
+    o = BSI.from_columns(cols, vals, ro)
+    assert o.bit_count() == 2
+    for x in [o.ebm] + o.ba:  # arrays only: the non-adjacent columns keep them under run_optimize
+        ka, kb, kr = _kinds(x)
+        assert ka >= 1 and (kb, kr) == (0, 0)
+        if values == "all_3":  # ebM and both slices hold PAD_CARDS[k] values under key k
+            assert ka == len(_gen.PAD_CARDS) and O.stats(x)["card"] == sum(_gen.PAD_CARDS)
+    built, nbits, mn, mx = eng.bsi_from_columns(cols, vals, ro)
+    loaded = eng.load([o.ebm] + o.ba)
+    assert (nbits, mn, mx) == (2, o.min, o.max) and _fetch(eng, built) == [o.ebm] + o.ba
+    for op in _bsi.OPS:
+        for a, e in ((3, 3), (1, 2), (2, 5), (0, 1)):
+            res = []
+            for b in (built, loaded):
+                eng.bsi(b, op, nbits, a, e, mn, mx, want_sum=True)
+                res.append((eng.fetch().serialize(), eng.bsi_sums()))
+            assert res[0] == res[1] and res[0][0] == o.compare(op, a, e), (op, a, e)
+            assert res[0][1] == o.sum(res[0][0])
+    for op in list(range(7)) + [7]:  # 7: rangeNEQ called directly
+        for a, e in ((3, 3), (1, 2), (2, 5)):
+            res = []
+            for b in (built, loaded):
+                eng.bsi_buffer(b, op, nbits, a, e, mn, mx)
+                res.append(eng.fetch().serialize())
+            assert res[0] == res[1], (op, a, e)
+    eng.release(built)
+    eng.release(loaded)
 
 
 def test_refusals_leave_no_batch(eng):

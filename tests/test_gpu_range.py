@@ -83,6 +83,35 @@ def test_range_ops_runs_and_many_inputs(gpu):
         assert _gpu("andnot", bufs[:2], st, en) == O.range_op("andnot", bufs[:2], st, en)
 
 
+def test_bitmap_cut_to_array_slot_padding(gpu):
+    """A bitmap container cut to c values (every c of _gen.PAD_CARDS) becomes an array slot, padded to 16 B with
+    copies of its last value: the selection's bytes, and the selection as both operands of ops that read whole
+    16 B vectors of a slot"""
+    from roaringbitmap_amd import Engine
+    x = encode([(5, B, np.arange(0, 65536, 2))])
+    e = Engine(0)
+    try:
+        b = e.load([x])
+        for c in _gen.PAD_CARDS:
+            st = (5 << 16) + 2 * (500 + 37 * c)  # even: [st, st + 2 c) keeps st, st + 2, ..., st + 2 c - 2
+            wins = [(st, st + 2 * c), (st + 2, st + 2 * c + 2)]
+            want = [O.range_op("select", [x], s, t) for s, t in wins]
+            for w in want:
+                s = O.stats(w)
+                assert (s["array"], s["bitmap"], s["run"], s["card"]) == (1, 0, 0, c), c
+            sel = [e.select_range(b, s, t) for s, t in wins]
+            assert [e.batch_fetch(s).serialize() for s in sel] == want, c
+            for op in ("or", "xor", "and", "andnot"):
+                e.pairwise(op, sel[0], sel[1])
+                assert e.fetch().serialize() == O.pairwise(op, want[0], want[1]), (c, op)
+                e.pairwise(op, sel[1], sel[0])
+                assert e.fetch().serialize() == O.pairwise(op, want[1], want[0]), (c, op)
+            for s in sel:
+                e.release(s)
+    finally:
+        e.close()
+
+
 def test_range_sanity(gpu):
     rb = _rb()
     x = rb.RoaringBitmap.bitmapOf(1, 2, 3)

@@ -179,3 +179,42 @@ def test_all_array_result_with_holes(gpu):
         assert [g.serialize() for g in got] == opt
     finally:
         e.close()
+
+
+def test_run_to_array_slot_padding(gpu):
+    """R -> A writes an array slot, padded to 16 B with copies of its last value: run containers of c one-value
+    runs (every c of _gen.PAD_CARDS, keys 0..7) become arrays, and the optimized batches then serve ops that
+    read whole 16 B vectors of a slot, and point queries at each container's last value"""
+    from _fmt import R, encode
+    from roaringbitmap_amd import Engine
+    la, lb = _gen.pad_lows(np.random.default_rng(61)), _gen.pad_lows(np.random.default_rng(61), shifted=True)
+    src_a, src_b = (encode([(k, R, lows) for k, lows in enumerate(ls)]) for ls in (la, lb))
+    n = len(_gen.PAD_CARDS)
+    assert O.stats(src_a)["run"] == n and O.stats(src_b)["run"] == n
+    ba, bb = O.run_optimize(src_a), O.run_optimize(src_b)
+    for x in (ba, bb):  # eff() makes every one of them an array
+        st = O.stats(x)
+        assert (st["array"], st["bitmap"], st["run"]) == (n, 0, 0)
+    e = Engine(0)
+    try:
+        a, _ = e.run_optimize(e.load([src_a]))
+        b, _ = e.run_optimize(e.load([src_b]))
+        assert e.batch_fetch(a).serialize() == ba and e.batch_fetch(b).serialize() == bb
+        for op in ("or", "xor", "and", "andnot"):
+            e.pairwise(op, a, b)
+            assert e.fetch().serialize() == O.pairwise(op, ba, bb), op
+            e.pairwise(op, b, a)
+            assert e.fetch().serialize() == O.pairwise(op, bb, ba), op
+        e.wide("or", a)
+        assert e.fetch().serialize() == O.wide("or", [ba])
+        sv = O.to_values(ba).astype(np.int64)
+        ends = np.cumsum(_gen.PAD_CARDS)
+        last = sv[ends - 1]  # the last value of every container
+        assert (last == np.array([(k << 16) | lows[-1] for k, lows in enumerate(la)])).all()
+        assert (e.point_query("select", a, ends - 1) == last).all()
+        assert (e.point_query("rank", a, last) == ends).all()
+        assert (e.point_query("next", a, last) == last).all()
+        assert (e.point_query("prev", a, last) == last).all()
+        assert (e.point_query("next", a, last[:-1] + 1) == sv[ends[:-1]]).all()  # past the padding: the next key's first
+    finally:
+        e.close()
