@@ -29,33 +29,17 @@
 
 namespace rbg {
 
-__global__ __launch_bounds__(256) void k_plan_aoff(const uint32_t* __restrict__ koa, const CDesc* __restrict__ da,
-                                                   const uint8_t* __restrict__ pa, AoffArgs aa,
-                                                   uint64_t* __restrict__ wg_epoch, uint32_t epoch,
-                                                   PTask* __restrict__ tasks, uint32_t* __restrict__ n_tasks,
-                                                   uint64_t* zlb, uint64_t* ztile, uint32_t* err) {
-  plan_zero(zlb, ztile);
+__global__ __launch_bounds__(256) void k_plan_aoff(BmView A, AoffArgs aa, PlanOut po, uint32_t* err) {
+  plan_zero(po.zlb, po.ztile);
   const int k = (int)(blockIdx.x * blockDim.x + threadIdx.x);
   PTask t;
   t.key = (uint16_t)k;
   const int q = k - aa.co, p = q - 1;
-  if (!aa.none && q >= 0 && q <= 65535) {
-    resolve(koa, da, pa, (uint32_t)q, t.slot_a, t.card_a, t.kind_a, t.nruns_a);
-  } else {
-    t.slot_a = 0;
-    t.card_a = 0;
-    t.kind_a = kAbsent;
-    t.nruns_a = 0;
-  }
-  if (!aa.none && aa.off != 0 && p >= 0 && p <= 65535) {
-    resolve(koa, da, pa, (uint32_t)p, t.slot_b, t.card_b, t.kind_b, t.nruns_b);
-  } else {
-    t.slot_b = 0;
-    t.card_b = 0;
-    t.kind_b = kAbsent;
-    t.nruns_b = 0;
-  }
-  plan_emit(t.kind_a != kAbsent || t.kind_b != kAbsent, t, wg_epoch, epoch, tasks, n_tasks, err);
+  if (!aa.none && q >= 0 && q <= 65535) resolve<0>(A, (uint32_t)q, t);
+  else ptask_absent<0>(t);
+  if (!aa.none && aa.off != 0 && p >= 0 && p <= 65535) resolve<1>(A, (uint32_t)p, t);
+  else ptask_absent<1>(t);
+  plan_emit(t.kind_a != kAbsent || t.kind_b != kAbsent, t, po, err);
 }
 
 // the kind of a nonempty part of an input container of kind `kind` holding `pc` values
@@ -77,9 +61,7 @@ __device__ __forceinline__ void aoff_task(uint32_t t, const PTask& tk, const uin
                                           const OutCtx& oc, uint32_t* lds, AoffCarry& cy) {
   const int key = tk.key;
   if (aa.off == 0) {  // a clone under the shifted key
-    const uint32_t len = tk.kind_a == DK_A ? 2u * tk.card_a : tk.kind_a == DK_B ? 8192u : 2u + 4u * tk.nruns_a;
-    w_place(t, true, pa + tk.slot_a + (tk.kind_a == DK_R ? 2 : 0), false, lds, len, tk.card_a, (uint32_t)key,
-            tk.kind_a, oc);
+    w_clone(t, tk, pa, oc, lds);
     return;
   }
   const int s = 65536 - aa.off;  // P's part is its bits [s, 65535], Q's its bits [0, s - 1]
@@ -136,7 +118,7 @@ __device__ __forceinline__ void aoff_task(uint32_t t, const PTask& tk, const uin
   }
   const int c = w_card(x);
   if (c == 0) {  // both parts empty
-    w_place(t, false, nullptr, true, lds, 0, 0, (uint32_t)key, DK_A, oc);
+    w_drop(t, (uint32_t)key, oc, lds);
     return;
   }
   int kind;
@@ -149,57 +131,29 @@ __device__ __forceinline__ void aoff_task(uint32_t t, const PTask& tk, const uin
     else if (tp == DK_R || tq == DK_R) kind = eff(c, w_runs(x));
     else kind = by_card(c);
   }
-  if (kind == DK_B) {  // registers straight to the task's slot
-    uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
-    w_store_bitmap(slot, x);
-    w_place(t, true, slot, false, lds, 8192, (uint32_t)c, (uint32_t)key, DK_B, oc);
-    return;
-  }
   // a run result here holds <= 2047 runs (toEfficientContainer, or the full container)
-  const uint32_t len = w_stage(kind, x, c, lds);
-  w_place(t, true, nullptr, true, lds, len, (uint32_t)c, (uint32_t)key, kind, oc);
+  w_emit(t, (uint32_t)key, x, c, kind, oc, lds);
 }
 
 constexpr int kAoWaves = 4;
 constexpr int kAoLds = 2064;  // u32 per wave: the 8 KiB scratch / staging area and the window's 1025th word
 
-// one wave per contiguous chunk of tasks (consecutive keys share an input container), the next record
-// fetched while a task runs
+// one wave per contiguous chunk of tasks (consecutive keys share an input container)
 __global__ __launch_bounds__(256) void k_aoff(const PTask* __restrict__ tasks, const uint32_t* __restrict__ n_tasks,
                                               const uint8_t* pa, AoffArgs aa, OutCtx oc) {
   __shared__ __align__(16) uint32_t lds_all[kAoWaves][kAoLds];
-  const int w = threadIdx.x >> 6;
-  uint32_t* lds = lds_all[w];
-  const uint32_t nt = uni(*n_tasks);
-  const uint32_t nw = gridDim.x * kAoWaves;
-  const uint32_t per = (nt + nw - 1) / nw;
-  uint32_t t = uni((blockIdx.x * kAoWaves + w) * per);
-  const uint32_t tend = min(nt, t + per);
-  if (t >= tend) return;
   AoffCarry cy;
   cy.prev_key = -2;
   cy.prev_q = 0;
   cy.prev_high = 0;
-  PTask cur = load_task(tasks, t);
-  for (;;) {
-    const uint32_t tn = t + 1;
-    PTask nxt;
-    if (tn < tend) nxt = load_task(tasks, tn);
-    aoff_task(t, cur, pa, aa, oc, lds, cy);
-    if (tn >= tend) break;
-    t = tn;
-    cur = nxt;
-  }
+  for_each_wave_task<kChunked>(tasks, n_tasks, lds_all, [&](uint32_t t, const PTask& tk, uint32_t* lds) {
+    aoff_task(t, tk, pa, aa, oc, lds, cy);
+  });
 }
 
-void launch_aoff(hipStream_t s, const uint32_t* koa, const CDesc* da, const uint8_t* pa, AoffArgs aa,
-                 uint64_t* wg_epoch, uint32_t epoch, PTask* tasks, uint32_t* n_tasks, OutCtx oc, uint64_t* zlb,
-                 uint64_t* ztile, int grid) {
-  hipLaunchKernelGGL(k_plan_aoff, dim3(256), dim3(256), 0, s, koa, da, pa, aa, wg_epoch, epoch, tasks, n_tasks, zlb,
-                     ztile, oc.err);
-  const int g0 = std::max(1, (grid + kAoWaves - 1) / kAoWaves);
-  hipLaunchKernelGGL(k_aoff, dim3(std::min(g0, resident_grid((const void*)&k_aoff))), dim3(256), 0, s, tasks,
-                     n_tasks, pa, aa, oc);
+void launch_aoff(hipStream_t s, BmView A, AoffArgs aa, PlanOut po, OutCtx oc, int grid) {
+  hipLaunchKernelGGL(k_plan_aoff, dim3(256), dim3(256), 0, s, A, aa, po, oc.err);
+  launch_resident<k_aoff>(s, grid, kAoWaves, po.tasks, po.n_tasks, A.payload, aa, oc);
 }
 
 }  // namespace rbg

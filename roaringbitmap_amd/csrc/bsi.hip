@@ -1137,8 +1137,7 @@ __device__ __forceinline__ void pair_buf_task(uint32_t t, const PTask& tk, const
                                               const OutCtx& oc, const BigRuns& big, uint32_t* lds) {
   const int ka = tk.kind_a, kb = tk.kind_b;
   if (OP == OPR_ANDNOT && kb == kAbsent) {  // x1's container alone: appendCopy (:460-469)
-    const uint32_t len = ka == DK_A ? 2u * tk.card_a : ka == DK_B ? 8192u : 2u + 4u * tk.nruns_a;
-    w_place(t, true, pa + tk.slot_a + (ka == DK_R ? 2 : 0), false, lds, len, tk.card_a, tk.key, ka, oc);
+    w_clone(t, tk, pa, oc, lds);
     return;
   }
   WCtr x;
@@ -1146,7 +1145,7 @@ __device__ __forceinline__ void pair_buf_task(uint32_t t, const PTask& tk, const
   w_combine<OP>(CDesc{tk.slot_b, tk.card_b, tk.key, (uint8_t)kb, 0}, pb, lds, x);
   const int c = w_card(x);
   if (c == 0) {  // empty results are dropped
-    w_place(t, false, nullptr, true, lds, 0, 0, tk.key, DK_A, oc);
+    w_drop(t, tk.key, oc, lds);
     return;
   }
   const bool raw_run = ka == DK_R && kb == DK_R;  // the merged run container, no toEfficientContainer
@@ -1154,21 +1153,7 @@ __device__ __forceinline__ void pair_buf_task(uint32_t t, const PTask& tk, const
   if (raw_run) kind = DK_R;
   else if (pairwise_needs_runs(OP, ka, (int)tk.card_a, kb, (int)tk.card_b)) kind = eff(c, w_runs(x));
   else kind = pairwise_kind(OP, ka, kb, c);
-  if (kind == DK_B) {
-    uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
-    w_store_bitmap(slot, x);
-    w_place(t, true, slot, false, lds, 8192, (uint32_t)c, tk.key, DK_B, oc);
-    return;
-  }
-  if (raw_run) {
-    const int nr = w_runs(x);
-    if (nr > 2047) {
-      w_place_big_runs(t, tk.key, x, c, nr, oc, big, lds);
-      return;
-    }
-  }
-  const uint32_t len = w_stage(kind, x, c, lds);
-  w_place(t, true, nullptr, true, lds, len, (uint32_t)c, tk.key, kind, oc);
+  w_emit(t, tk.key, x, c, kind, oc, lds, &big, raw_run);
 }
 
 constexpr int kPbWaves = 4;
@@ -1177,30 +1162,15 @@ template <int OP>
 __global__ __launch_bounds__(256, 4) void k_pair_buf(const PTask* __restrict__ tasks, const uint32_t* __restrict__ n_tasks,
                                                   const uint8_t* pa, const uint8_t* pb, OutCtx oc, BigRuns big) {
   __shared__ __align__(16) uint32_t lds_all[kPbWaves][2048];
-  const int w = threadIdx.x >> 6;
-  uint32_t* lds = lds_all[w];
-  const uint32_t nt = uni(*n_tasks);
-  const uint32_t stride = gridDim.x * kPbWaves;
-  uint32_t t = uni(blockIdx.x * kPbWaves + w);
-  if (t >= nt) return;
-  PTask cur = load_task(tasks, t);
-  for (;;) {
-    const uint32_t tn = t + stride;
-    PTask nxt;
-    if (tn < nt) nxt = load_task(tasks, tn);
-    pair_buf_task<OP>(t, cur, pa, pb, oc, big, lds);
-    if (tn >= nt) break;
-    t = tn;
-    cur = nxt;
-  }
+  for_each_wave_task(tasks, n_tasks, lds_all, [&](uint32_t t, const PTask& tk, uint32_t* lds) {
+    pair_buf_task<OP>(t, tk, pa, pb, oc, big, lds);
+  });
 }
 
 void launch_pair_buf(hipStream_t s, int op, int grid, const PTask* tasks, const uint32_t* nt, const uint8_t* pa,
                      const uint8_t* pb, OutCtx oc, BigRuns big) {
-  const void* k = op == OPR_AND ? (const void*)&k_pair_buf<OPR_AND> : (const void*)&k_pair_buf<OPR_ANDNOT>;
-  const int g = std::max(1, std::min((grid + kPbWaves - 1) / kPbWaves, resident_grid(k)));
-  if (op == OPR_AND) hipLaunchKernelGGL(k_pair_buf<OPR_AND>, dim3(g), dim3(256), 0, s, tasks, nt, pa, pb, oc, big);
-  else hipLaunchKernelGGL(k_pair_buf<OPR_ANDNOT>, dim3(g), dim3(256), 0, s, tasks, nt, pa, pb, oc, big);
+  if (op == OPR_AND) launch_resident<k_pair_buf<OPR_AND>>(s, grid, kPbWaves, tasks, nt, pa, pb, oc, big);
+  else launch_resident<k_pair_buf<OPR_ANDNOT>>(s, grid, kPbWaves, tasks, nt, pa, pb, oc, big);
 }
 
 void launch_plan_bsi(hipStream_t s, const uint32_t* key_off, const uint32_t* bm, uint32_t need, Task* by_key,

@@ -172,9 +172,24 @@ __host__ __device__ inline uint64_t header_bytes(uint32_t size, uint32_t has_run
   return 8 + 8ull * size;
 }
 
-struct OperandView {
+// One operand of a per-key op as its kernels see it: a single-bitmap key-major batch (key CSR of 65,537
+// offsets into the container table, the table, the payload arena, the container count)
+struct BmView {
+  const uint32_t* key_off;
   const CDesc* desc;
   const uint8_t* payload;
+  int n;
+};
+// What a plan kernel writes: the dense task list and its count, compacted over the workgroups through
+// wg_epoch (256 u64, `epoch` unique per op of the context); it also zeroes the op's look-back header
+// (zlb, 32 u64) and tile statuses (ztile), either may be null
+struct PlanOut {
+  uint64_t* wg_epoch;
+  uint32_t epoch;
+  PTask* tasks;
+  uint32_t* n_tasks;
+  uint64_t* zlb;
+  uint64_t* ztile;
 };
 
 __device__ __forceinline__ int popc64(uint64_t x) { return __popcll(x); }

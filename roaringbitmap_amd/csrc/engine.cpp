@@ -54,7 +54,7 @@ void dbg(hipStream_t s, const char* what) {
                std::chrono::duration<double, std::milli>(now - last).count());
   last = now;
   std::fflush(stderr);
-}  // look-back state: ticket @0, error word @64, statuses @256
+}
 
 // runOptimize's device statistics (Batch::ro_stats): from byte 64 the k_runopt workgroups' partial
 // counts (4 u64 each), from ro_flags_off(groups) the per-bitmap run flags, computed only when the host
@@ -192,6 +192,12 @@ static uint32_t next_epoch(Ctx* c) {
   if (++c->epoch == 0) ++c->epoch;
   return c->epoch;
 }
+// Where the plan kernel of the op being enqueued writes (after prepare_output, which decides what it
+// zeroes); one new epoch per plan that compacts its tasks (k_plan_balanced does not: compacts = false)
+static PlanOut plan_out(Ctx* c, bool compacts = true) {
+  return PlanOut{c->wg_epoch.as<uint64_t>(), compacts ? next_epoch(c) : 0, c->tasks.as<PTask>(),
+                 c->ntasks.as<uint32_t>(), c->zlb, c->ztile};
+}
 
 int find_batch(Ctx* c, int32_t id, Batch** out) {
   if (id < 0 || (size_t)id >= c->batches.size() || !c->batches[id] || !c->batches[id]->live) {
@@ -307,7 +313,7 @@ int grid_for(size_t tasks, size_t cap) {
 // device-resident result), and the portable-format buffer the serialization
 // writes into on fetch.  Card-only ops need no output state.
 int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* oc, bool card_only) {
-  uint8_t* lb = c->lb.as<uint8_t>();
+  uint8_t* lb = c->lb.as<uint8_t>();  // look-back state: ticket @0, error word @64, statuses @256
   *oc = OutCtx{};
   oc->err = reinterpret_cast<uint32_t*>(lb + 64);
   oc->status = reinterpret_cast<uint64_t*>(lb + kLbHeader);
@@ -381,12 +387,11 @@ int ctx_serialize(Ctx* c) {
 }
 
 
-// Bitmap i of a batch as the operand of a per-key op: the batch (statistics read), its container table
-// and container count.  The range must be contiguous: a one-bitmap key-major batch.
-struct Operand {
+// Bitmap i of a batch as the operand of a per-key op: what the kernels see of it (BmView: key CSR, container
+// table, payload, container count) and the batch (statistics read).  The range must be contiguous: a
+// one-bitmap key-major batch.
+struct Operand : BmView {
   Batch* b;
-  const CDesc* desc;
-  int n;
 };
 static int resolve(Ctx* c, int32_t id, size_t i, Operand* op) {
   Batch* b;
@@ -399,7 +404,7 @@ static int resolve(Ctx* c, int32_t id, size_t i, Operand* op) {
     set_err("pairwise operands must be single-bitmap key-major batches with slot-aligned payloads");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  *op = Operand{b, b->desc.as<CDesc>(), (int)b->n_ctr};
+  *op = Operand{{b->key_off.as<uint32_t>(), b->desc.as<CDesc>(), b->payload.as<uint8_t>(), (int)b->n_ctr}, b};
   return RBG_OK;
 }
 
@@ -649,12 +654,10 @@ static int ctx_pairwise_buffer(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib
     CHK(prepare_output(c, ub, A.b->payload_bytes + B.b->payload_bytes + kStagedMax * ub + big.cap, &oc, false));
     c->pending_src = {ia, ib};
     c->mark(0);
-    launch_plan_pairwise(s, op, key_lo, key_hi, A.b->key_off.as<uint32_t>(), A.desc, A.b->payload.as<uint8_t>(),
-                         B.b->key_off.as<uint32_t>(), B.desc, B.b->payload.as<uint8_t>(), c->wg_epoch.as<uint64_t>(),
-                         next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), c->zlb, c->ztile, oc.err);
+    const PlanOut po = plan_out(c);
+    launch_plan_pairwise(s, op, key_lo, key_hi, A, B, po, oc.err);
     c->mark(1);
-    launch_pair_buf(s, op, grid_for(ub, 65536), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(),
-                    A.b->payload.as<uint8_t>(), B.b->payload.as<uint8_t>(), oc, big);
+    launch_pair_buf(s, op, grid_for(ub, 65536), po.tasks, po.n_tasks, A.payload, B.payload, oc, big);
     return op_end(c);
   });
 }
@@ -679,10 +682,8 @@ int ctx_ornot(Ctx* c, int32_t ia, size_t ma, int32_t ib, size_t mb, int64_t rang
   OutCtx oc;
   CHK(prepare_output(c, ub, A.b->payload_bytes + B.b->payload_bytes + kStagedMax * ub, &oc, false));
   op_begin(c, {ia, ib});
-  launch_ornot(s, A.b->key_off.as<uint32_t>(), A.desc, A.b->payload.as<uint8_t>(), A.n, B.b->key_off.as<uint32_t>(),
-               B.desc, B.b->payload.as<uint8_t>(), B.n, max_key, last_run, flags, c->ornot_plan.as<OrNotPlan>(),
-               c->wg_epoch.as<uint64_t>(), next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb,
-               c->ztile, grid_for(ub, 65536));
+  launch_ornot(s, A, B, max_key, last_run, flags, c->ornot_plan.as<OrNotPlan>(), plan_out(c), oc,
+               grid_for(ub, 65536));
   CHK(op_end(c));
   if (max_key < 0 && A.n == 0 && B.n > 0) {
     OrNotPlan pl;
@@ -719,9 +720,7 @@ static int run_rmut(Ctx* c, int32_t ia, const Operand& A, RmutArgs ra, bool buf,
     OutCtx oc;
     CHK(prepare_output(c, ub, A.b->payload_bytes + kStagedMax * ub + big.cap, &oc, false));
     op_begin(c, {ia});
-    launch_rmut(c->stream, A.b->key_off.as<uint32_t>(), A.desc, A.b->payload.as<uint8_t>(), ra, buf,
-                c->wg_epoch.as<uint64_t>(), next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb,
-                c->ztile, big, grid_for(ub, 65536));
+    launch_rmut(c->stream, A, ra, buf, plan_out(c), oc, big, grid_for(ub, 65536));
     return op_end(c);
   });
 }
@@ -781,9 +780,7 @@ int ctx_add_offset(Ctx* c, int32_t ia, size_t ma, int64_t offset) {
   OutCtx oc;
   CHK(prepare_output(c, ub, A.b->payload_bytes + kStagedMax * ub, &oc, false));
   op_begin(c, {ia});
-  launch_aoff(c->stream, A.b->key_off.as<uint32_t>(), A.desc, A.b->payload.as<uint8_t>(), aa,
-              c->wg_epoch.as<uint64_t>(), next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->zlb,
-              c->ztile, grid_for(ub, 65536));
+  launch_aoff(c->stream, A, aa, plan_out(c), oc, grid_for(ub, 65536));
   return op_end(c);
 }
 
@@ -801,11 +798,10 @@ int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, b
       CHK(c->ones.ensure(8192));
       HIPCHK(hipMemsetAsync(c->ones.p, 0xFF, 8192, c->stream));
     }
-    Batch *A, *B;
-    CHK(get_batch(c, ia, &A));
-    CHK(get_batch(c, ib, &B));
-    launch_ior_fix(c->stream, c->ntasks.as<uint32_t>(), c->recs.as<ORec>(), A->key_off.as<uint32_t>(),
-                   A->desc.as<CDesc>(), B->key_off.as<uint32_t>(), B->desc.as<CDesc>(), c->ones.as<uint8_t>());
+    Operand A, B;
+    CHK(resolve(c, ia, ma, &A));
+    CHK(resolve(c, ib, mb, &B));
+    launch_ior_fix(c->stream, c->ntasks.as<uint32_t>(), c->recs.as<ORec>(), A, B, c->ones.as<uint8_t>());
     HIPCHK(hipGetLastError());
     c->agg_ok = false;  // k_ior_fix changed records after the compute kernel summed them
     return RBG_OK;
@@ -813,19 +809,16 @@ int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, b
   if (op < 0 || op > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
   key_lo = std::max(0, key_lo);
   key_hi = std::min(kMaxKeys, key_hi);
-  Operand oa, ob;
-  CHK(resolve(c, ia, ma, &oa));
-  CHK(resolve(c, ib, mb, &ob));
-  Batch *A = oa.b, *B = ob.b;
-  const CDesc *da = oa.desc, *db = ob.desc;
-  const int na = oa.n, nb = ob.n;
+  Operand A, B;
+  CHK(resolve(c, ia, ma, &A));
+  CHK(resolve(c, ib, mb, &B));
   hipStream_t s = c->stream;
   const int plan_op = card_only ? OP_AND : op;
   size_t ub;
   switch (plan_op) {
-    case OP_AND: ub = std::min(na, nb); break;
-    case OP_ANDNOT: ub = na; break;
-    default: ub = std::min<size_t>((size_t)na + nb, kMaxKeys); break;
+    case OP_AND: ub = std::min(A.n, B.n); break;
+    case OP_ANDNOT: ub = A.n; break;
+    default: ub = std::min<size_t>((size_t)A.n + B.n, kMaxKeys); break;
   }
   // Dense key ranges (the op's task bound covers at least half of the range) take every key of the
   // range as a task (one record and scratch slot per key, key key_lo + t at position t).  Sparse ones
@@ -833,22 +826,19 @@ int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, b
   const size_t nkeys = key_hi > key_lo ? (size_t)(key_hi - key_lo) : 0;
   const bool dense = nkeys > 0 && 2 * ub >= nkeys;
   OutCtx oc;
-  CHK(prepare_output(c, dense ? std::max(ub, nkeys) : ub, A->payload_bytes + B->payload_bytes + kStagedMax * ub,
+  CHK(prepare_output(c, dense ? std::max(ub, nkeys) : ub, A.b->payload_bytes + B.b->payload_bytes + kStagedMax * ub,
                      &oc, card_only));
   c->pending_src = {ia, ib};
   c->mark(0);
   const PwDirect pd{key_lo};
+  const PlanOut po = plan_out(c, !dense);
   if (dense) {
     // tasks binned by estimated cost so every wave draws the same mix (k_plan_balanced)
     // ... run by one 16-wave workgroup per CU that claims the CU's tasks through LDS (k_pair_cu)
-    launch_plan_balanced(s, plan_op, card_only ? 1 : 0, key_lo, (uint32_t)nkeys, A->key_off.as<uint32_t>(), da,
-                         A->payload.as<uint8_t>(), B->key_off.as<uint32_t>(), db, B->payload.as<uint8_t>(),
-                         c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), oc, c->task_card.as<uint32_t>(), c->zlb,
-                         c->ztile);
+    launch_plan_balanced(s, plan_op, card_only ? 1 : 0, key_lo, (uint32_t)nkeys, A, B, po, oc,
+                         c->task_card.as<uint32_t>());
   } else {
-    launch_plan_pairwise(s, plan_op, key_lo, key_hi, A->key_off.as<uint32_t>(), da, A->payload.as<uint8_t>(),
-                         B->key_off.as<uint32_t>(), db, B->payload.as<uint8_t>(), c->wg_epoch.as<uint64_t>(),
-                         next_epoch(c), c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(), c->zlb, c->ztile, oc.err);
+    launch_plan_pairwise(s, plan_op, key_lo, key_hi, A, B, po, oc.err);
     dbg(s, "plan");
   }
   c->mark(1);
@@ -861,9 +851,8 @@ int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, b
   }
   // 4 waves (tasks) per workgroup, clamped to the resident grid
   const int grid = grid_for(((dense ? nkeys : ub) + 3) / 4, 16384);
-  launch_pairwise(s, op, card_only ? 1 : 0, grid, c->tasks.as<PTask>(), c->ntasks.as<uint32_t>(),
-                  A->payload.as<uint8_t>(), B->payload.as<uint8_t>(), oc, c->task_card.as<uint32_t>(),
-                  dense ? &pd : nullptr);
+  launch_pairwise(s, op, card_only ? 1 : 0, grid, po.tasks, po.n_tasks, A.payload, B.payload, oc,
+                  c->task_card.as<uint32_t>(), dense ? &pd : nullptr);
   dbg(s, "pairwise");
   c->mark(2);
   if (card_only) {

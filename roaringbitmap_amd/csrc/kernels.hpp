@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "device.hpp"
 
@@ -234,6 +235,16 @@ struct BsiArgs {
 // stride over their tasks, so no workgroup waits for a dispatch slot and no
 // wave pays a launch per task (cached per kernel).
 int resident_grid(const void* kernel, int block = 256);  // workgroups of `block` threads resident at once
+// A task kernel K (256 threads, `per_block` tasks per workgroup at a time) over a list of at most `tasks`
+// tasks: one workgroup per `per_block` of them, at least one, at most the resident grid
+template <auto K, class... A>
+static inline void launch_resident(hipStream_t s, int tasks, int per_block, A... args) {
+  const int g = std::max(1, std::min((tasks + per_block - 1) / per_block, resident_grid((const void*)K)));
+  hipLaunchKernelGGL(K, dim3(g), dim3(256), 0, s, args...);
+}
+// a run-time op / mode / flag as a type, to pick a kernel's template instance: f(Int<OP_AND>{}) ...
+template <int V>
+using Int = std::integral_constant<int, V>;
 
 // plan kernels also zero the op's look-back header (zlb, 32 u64) and tile statuses (ztile, 128 u64)
 void launch_plan_wide(hipStream_t s, int mode, const uint32_t* key_off, uint32_t n_req, int key_lo, int key_hi,
@@ -241,12 +252,9 @@ void launch_plan_wide(hipStream_t s, int mode, const uint32_t* key_off, uint32_t
 void launch_compact(hipStream_t s, const uint8_t* flag, const Task* by_key, const uint32_t* wg_count, Task* tasks,
                     uint32_t* n_tasks);
 // pairwise.hip: plan (key alignment + descriptor resolution) and the wave-per-key compute
-// plan + compaction in one launch: tasks[] in key order, *n_tasks.  wg_epoch: 256 u64
-// (zeroed once per context), epoch: unique per op of the context; only keys in [key_lo, key_hi).
-void launch_plan_pairwise(hipStream_t s, int op, int key_lo, int key_hi, const uint32_t* koa, const CDesc* da,
-                          const uint8_t* pa, const uint32_t* kob, const CDesc* db, const uint8_t* pb,
-                          uint64_t* wg_epoch, uint32_t epoch, PTask* tasks, uint32_t* n_tasks, uint64_t* zlb,
-                          uint64_t* ztile, uint32_t* err);
+// plan + compaction in one launch: tasks[] in key order, *n_tasks (PlanOut, device.hpp; wg_epoch zeroed
+// once per context); only keys in [key_lo, key_hi).
+void launch_plan_pairwise(hipStream_t s, int op, int key_lo, int key_hi, BmView A, BmView B, PlanOut po, uint32_t* err);
 // mode 0: materialise results (task slots + records); mode 1: andCardinality into task_card
 // A dense key range of the pairwise compute kernel: the record of key k is at position k - key_lo.
 struct PwDirect {
@@ -260,10 +268,9 @@ void launch_pairwise(hipStream_t s, int op, int mode, int grid, const PTask* tas
 // dense key ranges: every key's task resolved and ordered by estimated cost within its 256-key segment
 // (heaviest first, rotated by the segment index) into tasks[]; n_tasks[0] = n_tasks[1] = nkeys (records
 // and list positions, one per key: keys without a task are marked, with an empty record / a zero count)
-void launch_plan_balanced(hipStream_t s, int op, int mode, int key_lo, uint32_t nkeys, const uint32_t* koa,
-                          const CDesc* da, const uint8_t* pa, const uint32_t* kob, const CDesc* db, const uint8_t* pb,
-                          PTask* tasks, uint32_t* n_tasks, OutCtx oc, uint32_t* task_card, uint64_t* zlb,
-                          uint64_t* ztile);
+// (no compaction: po.wg_epoch / po.epoch are not used)
+void launch_plan_balanced(hipStream_t s, int op, int mode, int key_lo, uint32_t nkeys, BmView A, BmView B, PlanOut po,
+                          OutCtx oc, uint32_t* task_card);
 void launch_wide(hipStream_t s, int mode, int grid, const Task* tasks, const uint32_t* nt, WideArgs args, OutCtx oc,
                  uint32_t* task_card);
 // result materialisation: k_place = compaction scan over the task records
@@ -288,8 +295,7 @@ void launch_serialize_shard_dyn(hipStream_t s, int grid, const uint32_t* nt, Out
                                 int world, uint8_t* out, uint8_t* runb, bool emit);
 // in-place OR's types after an OR (x1.or(x2), RB/RoaringBitmap.java:2481-2523): a full result of
 // bitmap x1 | array x2 stays a bitmap (ones: 8192 bytes of 0xFF)
-void launch_ior_fix(hipStream_t s, const uint32_t* nt, ORec* recs, const uint32_t* koa, const CDesc* da,
-                    const uint32_t* kob, const CDesc* db, const uint8_t* ones);
+void launch_ior_fix(hipStream_t s, const uint32_t* nt, ORec* recs, BmView A, BmView B, const uint8_t* ones);
 // dst[0..2] = the pending result's (containers, payload bytes, has_run) from k_place's ResultInfo
 void launch_layout_out(hipStream_t s, const ResultInfo* info, int64_t* dst);
 void launch_reduce_card(hipStream_t s, const uint32_t* task_card, const uint32_t* nt, ResultInfo* info,
@@ -370,12 +376,9 @@ struct RmutArgs {
 struct AoffArgs {
   int co, off, none;
 };
-void launch_aoff(hipStream_t s, const uint32_t* koa, const CDesc* da, const uint8_t* pa, AoffArgs aa,
-                 uint64_t* wg_epoch, uint32_t epoch, PTask* tasks, uint32_t* n_tasks, OutCtx oc, uint64_t* zlb,
-                 uint64_t* ztile, int grid);
-void launch_rmut(hipStream_t s, const uint32_t* koa, const CDesc* da, const uint8_t* pa, RmutArgs ra, bool buf,
-                 uint64_t* wg_epoch, uint32_t epoch, PTask* tasks, uint32_t* n_tasks, OutCtx oc, uint64_t* zlb,
-                 uint64_t* ztile, BigRuns big, int grid);
+// plan + compute over operand A; grid: an upper bound of the task count
+void launch_aoff(hipStream_t s, BmView A, AoffArgs aa, PlanOut po, OutCtx oc, int grid);
+void launch_rmut(hipStream_t s, BmView A, RmutArgs ra, bool buf, PlanOut po, OutCtx oc, BigRuns big, int grid);
 
 // RoaringBitmap.orNot (ornot.hip): the reference's key-loop bound, computed on the device
 struct OrNotPlan {
@@ -386,10 +389,8 @@ struct OrNotPlan {
 };
 // k_ornot_scan -> k_plan_ornot -> k_ornot over single-bitmap batches A (x1) and B (x2); flags: 1 in place,
 // 2 the buffer package's types (RBG_ORNOT_INPLACE / RBG_ORNOT_BUFFER)
-void launch_ornot(hipStream_t s, const uint32_t* koa, const CDesc* da, const uint8_t* pa, int na, const uint32_t* kob,
-                  const CDesc* db, const uint8_t* pb, int nb, int max_key, int last_run, int flags, OrNotPlan* plan,
-                  uint64_t* wg_epoch, uint32_t epoch, PTask* tasks, uint32_t* n_tasks, OutCtx oc, uint64_t* zlb,
-                  uint64_t* ztile, int grid);
+void launch_ornot(hipStream_t s, BmView A, BmView B, int max_key, int last_run, int flags, OrNotPlan* plan, PlanOut po,
+                  OutCtx oc, int grid);
 
 // batched andCardinality over pairs (2i, 2i+1) of a bitmap-major batch: per-pair key
 // alignment (count, scan, emit), then one wave per matched key; pairs of more than 64

@@ -28,10 +28,6 @@
 
 namespace rbg {
 
-// serialized payload of RunContainer.full() (RB/RunContainer.java:1663-1665): nruns = 1, (0, 65535);
-// slack after it for the serializer's 16 B over-read
-__device__ uint16_t g_full_run[16] = {1, 0, 0xFFFF};
-
 // 1024-thread block sum / inclusive scan (LDS `red` of 17 ints)
 __device__ __forceinline__ int ornot_block_sum(int v, int* red) {
   v = wave_sum_i(v);
@@ -106,23 +102,18 @@ __global__ __launch_bounds__(1024) void k_ornot_scan(const uint32_t* __restrict_
 }
 
 // one thread per key: tasks for the keys the loop reaches and for x1's keys above maxKey
-__global__ __launch_bounds__(256) void k_plan_ornot(const uint32_t* __restrict__ koa, const CDesc* __restrict__ da,
-                                                    const uint8_t* __restrict__ pa, const uint32_t* __restrict__ kob,
-                                                    const CDesc* __restrict__ db, const uint8_t* __restrict__ pb,
-                                                    int max_key, const OrNotPlan* __restrict__ plan,
-                                                    uint64_t* __restrict__ wg_epoch, uint32_t epoch,
-                                                    PTask* __restrict__ tasks, uint32_t* __restrict__ n_tasks,
-                                                    uint64_t* zlb, uint64_t* ztile, uint32_t* err) {
-  plan_zero(zlb, ztile);
+__global__ __launch_bounds__(256) void k_plan_ornot(BmView A, BmView B, int max_key,
+                                                    const OrNotPlan* __restrict__ plan, PlanOut po, uint32_t* err) {
+  plan_zero(po.zlb, po.ztile);
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   PTask t;
-  resolve(koa, da, pa, k, t.slot_a, t.card_a, t.kind_a, t.nruns_a);
-  resolve(kob, db, pb, k, t.slot_b, t.card_b, t.kind_b, t.nruns_b);
+  resolve<0>(A, k, t);
+  resolve<1>(B, k, t);
   t.key = (uint16_t)k;
   const int k_end = plan->k_end;
   int f = (int)k < k_end || ((int)k > max_key && t.kind_a != kAbsent);
   if (plan->neg) f = 0;
-  plan_emit(f, t, wg_epoch, epoch, tasks, n_tasks, err);
+  plan_emit(f, t, po, err);
 }
 
 // bits [0, e) of container word w
@@ -157,9 +148,7 @@ __device__ __forceinline__ void ornot_task(uint32_t t, const PTask& tk, const ui
   const int key = tk.key;
   const bool ia = tk.kind_a != kAbsent, ib = tk.kind_b != kAbsent;
   if (key > max_key) {  // x1's containers above the range, appended as they are (:1493-1500 / :1588-1596)
-    const uint32_t len = tk.kind_a == DK_A ? 2u * tk.card_a : tk.kind_a == DK_B ? 8192u : 2u + 4u * tk.nruns_a;
-    w_place(t, true, pa + tk.slot_a + (tk.kind_a == DK_R ? 2 : 0), false, lds, len, tk.card_a, (uint32_t)key,
-            tk.kind_a, oc);
+    w_clone(t, tk, pa, oc, lds);
     return;
   }
   const int e = key == max_key ? last_run : 65536;
@@ -167,25 +156,11 @@ __device__ __forceinline__ void ornot_task(uint32_t t, const PTask& tk, const ui
     // RunContainer.full(); at maxKey with lastRun = 0x10000, x1's c1.ior(full run) and the full
     // rangeOfOnes are full run containers as well (RunContainer.or / BitmapContainer.ior(RunContainer) /
     // RunContainer.ior return full() on a full union)
-    w_place(t, true, reinterpret_cast<const uint8_t*>(g_full_run), false, lds, 6, 65536, (uint32_t)key, DK_R, oc);
+    w_full_run(t, (uint32_t)key, oc, lds);
     return;
   }
-  if (!ia && !ib) {  // rangeOfOnes(0, lastRun) at maxKey, written by lane 0
-    uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
-    const bool arr = e <= 2;
-    uint16_t* p = reinterpret_cast<uint16_t*>(arr ? slot : slot + 2);
-    if (lane_id() == 0) {
-      if (arr) {
-        p[0] = 0;
-        p[1] = 1;
-      } else {
-        p[0] = 1;
-        p[1] = 0;
-        p[2] = (uint16_t)(e - 1);
-      }
-    }
-    w_place(t, true, reinterpret_cast<const uint8_t*>(p), false, lds, arr ? 2u * e : 6u, (uint32_t)e, (uint32_t)key,
-            arr ? DK_A : DK_R, oc);
+  if (!ia && !ib) {  // rangeOfOnes(0, lastRun) at maxKey
+    w_range_of_ones(t, (uint32_t)key, 0, e - 1, true, oc, lds);
     return;
   }
   WCtr x, y;
@@ -219,7 +194,7 @@ __device__ __forceinline__ void ornot_task(uint32_t t, const PTask& tk, const ui
     if ((INPLACE || !ib) && kx == DK_B && ky == DK_A) kz = DK_B;
   } else {  // x2 only: its complement, dropped when empty
     if (cy == 0) {
-      w_place(t, false, nullptr, true, lds, 0, 0, (uint32_t)key, DK_A, oc);
+      w_drop(t, (uint32_t)key, oc, lds);
       return;
     }
 #pragma unroll
@@ -227,62 +202,38 @@ __device__ __forceinline__ void ornot_task(uint32_t t, const PTask& tk, const ui
     cz = cy;
     kz = ky;
   }
-  if (kz == DK_B) {  // registers straight to the task's slot
-    uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
-    w_store_bitmap(slot, x);
-    w_place(t, true, slot, false, lds, 8192, (uint32_t)cz, (uint32_t)key, DK_B, oc);
-    return;
-  }
-  const uint32_t len = w_stage(kz, x, cz, lds);
-  w_place(t, true, nullptr, true, lds, len, (uint32_t)cz, (uint32_t)key, kz, oc);
+  w_emit(t, (uint32_t)key, x, cz, kz, oc, lds);
 }
 
 constexpr int kOrnWaves = 4;
 
 // INPLACE: x1.orNot (iorNot, ior); BUF: the buffer package's ImmutableRoaringBitmap.orNot /
 // MutableRoaringBitmap.orNot (RB/buffer/ImmutableRoaringBitmap.java:484-548, MutableRoaringBitmap.java
-// :962-1030).  Static wave stride over the task list; the next record is fetched while a task runs.
+// :962-1030).
 template <bool INPLACE, bool BUF>
 __global__ __launch_bounds__(256, 3) void k_ornot(const PTask* __restrict__ tasks, const uint32_t* __restrict__ n_tasks,
                                                const uint8_t* pa, const uint8_t* pb, int max_key, int last_run,
                                                OutCtx oc) {
   __shared__ __align__(16) uint32_t lds_all[kOrnWaves][2048];
-  const int w = threadIdx.x >> 6;
-  uint32_t* lds = lds_all[w];
-  const uint32_t nt = uni(*n_tasks);
-  const uint32_t stride = gridDim.x * kOrnWaves;
-  uint32_t t = uni(blockIdx.x * kOrnWaves + w);
-  if (t >= nt) return;
-  PTask cur = load_task(tasks, t);
-  for (;;) {
-    const uint32_t tn = t + stride;
-    PTask nxt;
-    if (tn < nt) nxt = load_task(tasks, tn);  // in flight while this task runs
-    ornot_task<INPLACE, BUF>(t, cur, pa, pb, max_key, last_run, oc, lds);
-    if (tn >= nt) break;
-    t = tn;
-    cur = nxt;
-  }
+  for_each_wave_task(tasks, n_tasks, lds_all, [&](uint32_t t, const PTask& tk, uint32_t* lds) {
+    ornot_task<INPLACE, BUF>(t, tk, pa, pb, max_key, last_run, oc, lds);
+  });
 }
 
-void launch_ornot(hipStream_t s, const uint32_t* koa, const CDesc* da, const uint8_t* pa, int na, const uint32_t* kob,
-                  const CDesc* db, const uint8_t* pb, int nb, int max_key, int last_run, int flags, OrNotPlan* plan,
-                  uint64_t* wg_epoch, uint32_t epoch, PTask* tasks, uint32_t* n_tasks, OutCtx oc, uint64_t* zlb,
-                  uint64_t* ztile, int grid) {
-  hipLaunchKernelGGL(k_ornot_scan, dim3(1), dim3(1024), 0, s, koa, na, kob, db, nb, max_key, plan);
-  hipLaunchKernelGGL(k_plan_ornot, dim3(256), dim3(256), 0, s, koa, da, pa, kob, db, pb, max_key, plan, wg_epoch,
-                     epoch, tasks, n_tasks, zlb, ztile, oc.err);
-  const int g0 = std::max(1, (grid + kOrnWaves - 1) / kOrnWaves);
-#define RBG_ORNOT_LAUNCH(I, B)                                                                            \
-  hipLaunchKernelGGL((k_ornot<I, B>), dim3(std::min(g0, resident_grid((const void*)&k_ornot<I, B>))), dim3(256), 0, \
-                     s, tasks, n_tasks, pa, pb, max_key, last_run, oc)
+void launch_ornot(hipStream_t s, BmView A, BmView B, int max_key, int last_run, int flags, OrNotPlan* plan, PlanOut po,
+                  OutCtx oc, int grid) {
+  hipLaunchKernelGGL(k_ornot_scan, dim3(1), dim3(1024), 0, s, A.key_off, A.n, B.key_off, B.desc, B.n, max_key, plan);
+  hipLaunchKernelGGL(k_plan_ornot, dim3(256), dim3(256), 0, s, A, B, max_key, plan, po, oc.err);
+  auto run = [&](auto inplace, auto buf) {
+    launch_resident<k_ornot<decltype(inplace)::value != 0, decltype(buf)::value != 0>>(
+        s, grid, kOrnWaves, po.tasks, po.n_tasks, A.payload, B.payload, max_key, last_run, oc);
+  };
   switch (flags & 3) {
-    case 0: RBG_ORNOT_LAUNCH(false, false); break;
-    case 1: RBG_ORNOT_LAUNCH(true, false); break;
-    case 2: RBG_ORNOT_LAUNCH(false, true); break;
-    default: RBG_ORNOT_LAUNCH(true, true); break;
+    case 0: run(Int<0>{}, Int<0>{}); break;
+    case 1: run(Int<1>{}, Int<0>{}); break;
+    case 2: run(Int<0>{}, Int<1>{}); break;
+    default: run(Int<1>{}, Int<1>{}); break;
   }
-#undef RBG_ORNOT_LAUNCH
 }
 
 }  // namespace rbg

@@ -36,18 +36,13 @@ __device__ __forceinline__ int pair_class(int op, int ka, int kb) {
 // tasks straight into the dense task list -- plan and compaction in one launch.  Keys
 // outside [key_lo, key_hi) give no task (a key-range shard of the op: every key's result
 // depends on that key's containers only, RB/RoaringBitmap.java:382-399).
-__global__ __launch_bounds__(256) void k_plan_pairwise(int op, int key_lo, int key_hi, const uint32_t* __restrict__ koa,
-                                                       const CDesc* __restrict__ da, const uint8_t* __restrict__ pa,
-                                                       const uint32_t* __restrict__ kob,
-                                                       const CDesc* __restrict__ db, const uint8_t* __restrict__ pb,
-                                                       uint64_t* __restrict__ wg_epoch, uint32_t epoch,
-                                                       PTask* __restrict__ tasks, uint32_t* __restrict__ n_tasks,
-                                                       uint64_t* zlb, uint64_t* ztile, uint32_t* err) {
-  plan_zero(zlb, ztile);
+__global__ __launch_bounds__(256) void k_plan_pairwise(int op, int key_lo, int key_hi, BmView A, BmView B, PlanOut po,
+                                                       uint32_t* err) {
+  plan_zero(po.zlb, po.ztile);
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   PTask t;
-  resolve(koa, da, pa, k, t.slot_a, t.card_a, t.kind_a, t.nruns_a);
-  resolve(kob, db, pb, k, t.slot_b, t.card_b, t.kind_b, t.nruns_b);
+  resolve<0>(A, k, t);
+  resolve<1>(B, k, t);
   t.key = (uint16_t)k;
   const bool ia = t.kind_a != kAbsent, ib = t.kind_b != kAbsent;
   int f;
@@ -58,7 +53,7 @@ __global__ __launch_bounds__(256) void k_plan_pairwise(int op, int key_lo, int k
     default: f = ia && ib; break;  // AND and andCardinality
   }
   if ((int)k < key_lo || (int)k >= key_hi) f = 0;
-  plan_emit(f, t, wg_epoch, epoch, tasks, n_tasks, err);
+  plan_emit(f, t, po, err);
 }
 
 // ---------------------------------------------------------------------------
@@ -103,16 +98,11 @@ __device__ __forceinline__ int bal_bin(const PTask& t) {
 }
 
 template <int OP, int MODE>
-__global__ __launch_bounds__(256) void k_plan_balanced(int key_lo, uint32_t nkeys, const uint32_t* __restrict__ koa,
-                                                       const CDesc* __restrict__ da, const uint8_t* __restrict__ pa,
-                                                       const uint32_t* __restrict__ kob,
-                                                       const CDesc* __restrict__ db, const uint8_t* __restrict__ pb,
-                                                       PTask* __restrict__ tasks, uint32_t* __restrict__ n_tasks,
-                                                       OutCtx oc, uint32_t* __restrict__ task_card, uint64_t* zlb,
-                                                       uint64_t* ztile) {
+__global__ __launch_bounds__(256) void k_plan_balanced(int key_lo, uint32_t nkeys, BmView A, BmView B, PlanOut po,
+                                                       OutCtx oc, uint32_t* __restrict__ task_card) {
   __shared__ int hist[kBalBins];
   __shared__ int off[kBalBins];
-  plan_zero(zlb, ztile);
+  plan_zero(po.zlb, po.ztile);
   if (threadIdx.x < kBalBins) hist[threadIdx.x] = 0;
   __syncthreads();
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;  // key position in the range
@@ -120,8 +110,8 @@ __global__ __launch_bounds__(256) void k_plan_balanced(int key_lo, uint32_t nkey
   int bin = kBalBins - 1, rank = 0;
   if (i < nkeys) {
     const uint32_t k = (uint32_t)key_lo + i;
-    resolve(koa, da, pa, k, t.slot_a, t.card_a, t.kind_a, t.nruns_a);
-    resolve(kob, db, pb, k, t.slot_b, t.card_b, t.kind_b, t.nruns_b);
+    resolve<0>(A, k, t);
+    resolve<1>(B, k, t);
     t.key = (uint16_t)k;
     const bool ia = t.kind_a != kAbsent, ib = t.kind_b != kAbsent;
     const bool has = (OP == OP_OR || OP == OP_XOR) ? (ia || ib) : OP == OP_ANDNOT ? ia : (ia && ib);
@@ -161,11 +151,11 @@ __global__ __launch_bounds__(256) void k_plan_balanced(int key_lo, uint32_t nkey
     // spaced 16 apart (every cost band of the segments) rather than one rank over and over
     const uint32_t m = min(256u, nkeys - blockIdx.x * 256u);
     const uint32_t r = (uint32_t)(off[bin] + rank);
-    tasks[blockIdx.x * 256u + (r + blockIdx.x) % m] = t;
+    po.tasks[blockIdx.x * 256u + (r + blockIdx.x) % m] = t;
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
-    n_tasks[0] = nkeys;  // records: one per key of the range
-    n_tasks[1] = nkeys;  // list positions (keys without a task are marked)
+    po.n_tasks[0] = nkeys;  // records: one per key of the range
+    po.n_tasks[1] = nkeys;  // list positions (keys without a task are marked)
   }
 }
 
@@ -292,13 +282,13 @@ __device__ __forceinline__ void filter_class_task(uint32_t t, const PTask& tk, c
   const int ka = tk.kind_a, kb = tk.kind_b;
   if (ka == kAbsent || kb == kAbsent) {  // unmatched key: clone (appendCopy), RB/RoaringArray.java:184-205
     if (MODE == 0) {
+      // w_clone (wave.hpp) written out: through the helper this kernel's assembly changes
       const bool from_a = ka != kAbsent;
       const int kind = from_a ? ka : kb;
       const uint32_t card = from_a ? tk.card_a : tk.card_b;
       const uint32_t nr = from_a ? tk.nruns_a : tk.nruns_b;
       const uint8_t* src = (from_a ? pa + tk.slot_a : pb + tk.slot_b) + (kind == DK_R ? 2 : 0);
-      const uint32_t len = kind == DK_A ? 2 * card : kind == DK_B ? 8192u : 2 + 4 * nr;
-      w_place(t, true, src, false, lds, len, card, tk.key, kind, oc);
+      w_place(t, true, src, false, lds, ser_len_of(kind, card, nr), card, tk.key, kind, oc);
     }
     return;
   }
@@ -426,7 +416,7 @@ __device__ __forceinline__ bool rr_and_task(uint32_t t, const PTask& tk, const u
     return true;
   }
   if (c == 0) {  // empty results are dropped (RB/RoaringBitmap.java:389)
-    w_place(t, false, nullptr, true, lds, 0, 0, tk.key, DK_A, oc);
+    w_drop(t, tk.key, oc, lds);
     return true;
   }
   int nr;
@@ -460,11 +450,12 @@ __device__ __forceinline__ void bitmap_class_task(uint32_t t, const PTask& tk, c
     return;
   }
   if (c == 0) {  // empty results are dropped (RB/RoaringBitmap.java:389,456,1084)
-    w_place(t, false, nullptr, true, lds, 0, 0, tk.key, DK_A, oc);
+    w_drop(t, tk.key, oc, lds);
     return;
   }
   const bool use_eff = pairwise_needs_runs(OP, ka, ca, kb, cb);
   const int kind = use_eff ? eff(c, w_runs(x)) : pairwise_kind(OP, ka, kb, c);
+  // w_emit (wave.hpp) written out: through the helper this kernel's assembly changes
   if (kind == DK_B) {
     uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
     w_store_bitmap(slot, x);
@@ -499,6 +490,7 @@ __global__ __launch_bounds__(256, 4) void k_pair_wave(const PTask* __restrict__ 
                                                       const uint32_t* __restrict__ n_tasks, const uint8_t* pa,
                                                       const uint8_t* pb, OutCtx oc, uint32_t* __restrict__ task_card) {
   __shared__ __align__(16) uint32_t lds_all[kWaves][kWaveLds];
+  // for_each_wave_task (wave.hpp) written out: through the helper the compiler orders this kernel differently
   const uint32_t nt = uni(*n_tasks);
   const int w = threadIdx.x >> 6;
   uint32_t* lds = lds_all[w];
@@ -582,55 +574,38 @@ static void launch_pw(hipStream_t s, int grid, const PTask* tasks, const uint32_
     hipLaunchKernelGGL((k_pair_cu<OP, MODE>), dim3(g), dim3(1024), 0, s, tasks, nt, pa, pb, oc, task_card, *dense);
     return;
   }
-  const int g = std::max(1, std::min(grid, resident_grid((const void*)&k_pair_wave<OP, MODE>)));
-  hipLaunchKernelGGL((k_pair_wave<OP, MODE>), dim3(g), dim3(256), 0, s, tasks, nt, pa, pb, oc, task_card);
+  launch_resident<k_pair_wave<OP, MODE>>(s, grid, 1, tasks, nt, pa, pb, oc, task_card);  // grid: workgroups
 }
 
-template <int OP, int MODE>
-static void launch_pb(hipStream_t s, int key_lo, uint32_t nkeys, const uint32_t* koa, const CDesc* da,
-                      const uint8_t* pa, const uint32_t* kob, const CDesc* db, const uint8_t* pb, PTask* tasks,
-                      uint32_t* n_tasks, OutCtx oc, uint32_t* task_card, uint64_t* zlb, uint64_t* ztile) {
-  hipLaunchKernelGGL((k_plan_balanced<OP, MODE>), dim3((nkeys + 255) / 256), dim3(256), 0, s, key_lo, nkeys, koa, da,
-                     pa, kob, db, pb, tasks, n_tasks, oc, task_card, zlb, ztile);
-}
-void launch_plan_balanced(hipStream_t s, int op, int mode, int key_lo, uint32_t nkeys, const uint32_t* koa,
-                          const CDesc* da, const uint8_t* pa, const uint32_t* kob, const CDesc* db, const uint8_t* pb,
-                          PTask* tasks, uint32_t* n_tasks, OutCtx oc, uint32_t* task_card, uint64_t* zlb,
-                          uint64_t* ztile) {
-#define RBG_LPB(O)                                                                                                  \
-  if (mode == 0)                                                                                                    \
-    launch_pb<O, 0>(s, key_lo, nkeys, koa, da, pa, kob, db, pb, tasks, n_tasks, oc, task_card, zlb, ztile); \
-  else                                                                                                              \
-    launch_pb<O, 1>(s, key_lo, nkeys, koa, da, pa, kob, db, pb, tasks, n_tasks, oc, task_card, zlb, ztile);
+// f(Int<OP>{}, Int<MODE>{}) for a run-time op (OP_AND .. OP_ANDNOT) and mode (0 / 1)
+template <class F>
+static void with_op_mode(int op, int mode, F f) {
+  auto with_mode = [&](auto o) { mode == 0 ? f(o, Int<0>{}) : f(o, Int<1>{}); };
   switch (op) {
-    case OP_AND: RBG_LPB(OP_AND) break;
-    case OP_OR: RBG_LPB(OP_OR) break;
-    case OP_XOR: RBG_LPB(OP_XOR) break;
-    default: RBG_LPB(OP_ANDNOT) break;
+    case OP_AND: with_mode(Int<OP_AND>{}); break;
+    case OP_OR: with_mode(Int<OP_OR>{}); break;
+    case OP_XOR: with_mode(Int<OP_XOR>{}); break;
+    default: with_mode(Int<OP_ANDNOT>{}); break;
   }
-#undef RBG_LPB
 }
 
-void launch_plan_pairwise(hipStream_t s, int op, int key_lo, int key_hi, const uint32_t* koa, const CDesc* da,
-                          const uint8_t* pa, const uint32_t* kob, const CDesc* db, const uint8_t* pb,
-                          uint64_t* wg_epoch, uint32_t epoch, PTask* tasks, uint32_t* n_tasks, uint64_t* zlb,
-                          uint64_t* ztile, uint32_t* err) {
-  hipLaunchKernelGGL(k_plan_pairwise, dim3(256), dim3(256), 0, s, op, key_lo, key_hi, koa, da, pa, kob, db, pb, wg_epoch,
-                     epoch, tasks, n_tasks, zlb, ztile, err);
+void launch_plan_balanced(hipStream_t s, int op, int mode, int key_lo, uint32_t nkeys, BmView A, BmView B, PlanOut po,
+                          OutCtx oc, uint32_t* task_card) {
+  with_op_mode(op, mode, [&](auto o, auto m) {
+    hipLaunchKernelGGL((k_plan_balanced<decltype(o)::value, decltype(m)::value>), dim3((nkeys + 255) / 256), dim3(256),
+                       0, s, key_lo, nkeys, A, B, po, oc, task_card);
+  });
+}
+
+void launch_plan_pairwise(hipStream_t s, int op, int key_lo, int key_hi, BmView A, BmView B, PlanOut po, uint32_t* err) {
+  hipLaunchKernelGGL(k_plan_pairwise, dim3(256), dim3(256), 0, s, op, key_lo, key_hi, A, B, po, err);
 }
 
 void launch_pairwise(hipStream_t s, int op, int mode, int grid, const PTask* tasks, const uint32_t* nt, const uint8_t* pa,
                      const uint8_t* pb, OutCtx oc, uint32_t* task_card, const PwDirect* dense) {
-#define RBG_LPW(O)                                                                  \
-  if (mode == 0) launch_pw<O, 0>(s, grid, tasks, nt, pa, pb, oc, task_card, dense); \
-  else launch_pw<O, 1>(s, grid, tasks, nt, pa, pb, oc, task_card, dense);
-  switch (op) {
-    case OP_AND: RBG_LPW(OP_AND) break;
-    case OP_OR: RBG_LPW(OP_OR) break;
-    case OP_XOR: RBG_LPW(OP_XOR) break;
-    default: RBG_LPW(OP_ANDNOT) break;
-  }
-#undef RBG_LPW
+  with_op_mode(op, mode, [&](auto o, auto m) {
+    launch_pw<decltype(o)::value, decltype(m)::value>(s, grid, tasks, nt, pa, pb, oc, task_card, dense);
+  });
 }
 
 }  // namespace rbg

@@ -36,26 +36,17 @@
 
 namespace rbg {
 
-__device__ uint16_t g_full_run_rm[16] = {1, 0, 0xFFFF};  // RunContainer.full(); slack for the 16 B over-read
-
 __device__ __forceinline__ void rmut_cut(int key, const RmutArgs& ra, int* lo, int* hi) {
   *lo = key == ra.hbs ? ra.lbs : 0;
   *hi = key == ra.hbl ? ra.lbl : 65535;
 }
 
-__global__ __launch_bounds__(256) void k_plan_rmut(const uint32_t* __restrict__ koa, const CDesc* __restrict__ da,
-                                                   const uint8_t* __restrict__ pa, RmutArgs ra,
-                                                   uint64_t* __restrict__ wg_epoch, uint32_t epoch,
-                                                   PTask* __restrict__ tasks, uint32_t* __restrict__ n_tasks,
-                                                   uint64_t* zlb, uint64_t* ztile, uint32_t* err) {
-  plan_zero(zlb, ztile);
+__global__ __launch_bounds__(256) void k_plan_rmut(BmView A, RmutArgs ra, PlanOut po, uint32_t* err) {
+  plan_zero(po.zlb, po.ztile);
   const uint32_t k = blockIdx.x * blockDim.x + threadIdx.x;
   PTask t;
-  resolve(koa, da, pa, k, t.slot_a, t.card_a, t.kind_a, t.nruns_a);
-  t.slot_b = 0;
-  t.card_b = 0;
-  t.kind_b = kAbsent;
-  t.nruns_b = 0;
+  resolve<0>(A, k, t);
+  ptask_absent<1>(t);
   t.key = (uint16_t)k;
   const bool present = t.kind_a != kAbsent;
   const bool in = (int)k >= ra.hbs && (int)k <= ra.hbl;
@@ -71,7 +62,7 @@ __global__ __launch_bounds__(256) void k_plan_rmut(const uint32_t* __restrict__ 
   } else {
     f = 1;
   }
-  plan_emit(f, t, wg_epoch, epoch, tasks, n_tasks, err);
+  plan_emit(f, t, po, err);
 }
 
 template <int OP, bool BUF>
@@ -83,14 +74,7 @@ __device__ __forceinline__ void rmut_task(uint32_t t, const PTask& tk, const uin
     WCtr x;
     w_materialize(CDesc{tk.slot_a, tk.card_a, tk.key, tk.kind_a, 0}, pa, lds, x);
     const int c = (int)tk.card_a;
-    if (c > 4096) {
-      uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
-      w_store_bitmap(slot, x);
-      w_place(t, true, slot, false, lds, 8192, (uint32_t)c, (uint32_t)key, DK_B, oc);
-    } else {
-      const uint32_t len = w_stage(DK_A, x, c, lds);
-      w_place(t, true, nullptr, true, lds, len, (uint32_t)c, (uint32_t)key, DK_A, oc);
-    }
+    w_emit(t, (uint32_t)key, x, c, by_card(c), oc, lds);
     return;
   }
   if (OP == RMUT_LIMIT && key == ra.hbs) {  // Container.limit(lbs): the first lbs values
@@ -117,55 +101,23 @@ __device__ __forceinline__ void rmut_task(uint32_t t, const PTask& tk, const uin
         }
       }
     }
-    const int kind = tk.kind_a == DK_B ? by_card(n) : tk.kind_a;
-    if (kind == DK_B) {
-      uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
-      w_store_bitmap(slot, x);
-      w_place(t, true, slot, false, lds, 8192, (uint32_t)n, (uint32_t)key, DK_B, oc);
-      return;
-    }
-    if (kind == DK_R) {
-      const int nr = w_runs(x);
-      if (nr > 2047) {
-        w_place_big_runs(t, (uint32_t)key, x, n, nr, oc, big, lds);
-        return;
-      }
-    }
-    const uint32_t len = w_stage(kind, x, n, lds);
-    w_place(t, true, nullptr, true, lds, len, (uint32_t)n, (uint32_t)key, kind, oc);
+    w_emit(t, (uint32_t)key, x, n, tk.kind_a == DK_B ? by_card(n) : tk.kind_a, oc, lds, &big);
     return;
   }
   if (OP == RMUT_DERUN || OP == RMUT_LIMIT || key < ra.hbs || key > ra.hbl) {  // cloned: outside the range,
                                                                                 // not a run container, or kept whole
-    const uint32_t len = tk.kind_a == DK_A ? 2u * tk.card_a : tk.kind_a == DK_B ? 8192u : 2u + 4u * tk.nruns_a;
-    w_place(t, true, pa + tk.slot_a + (tk.kind_a == DK_R ? 2 : 0), false, lds, len, tk.card_a, (uint32_t)key,
-            tk.kind_a, oc);
+    w_clone(t, tk, pa, oc, lds);
     return;
   }
   int lo, hi;
   rmut_cut(key, ra, &lo, &hi);
   constexpr bool ADD = OP == RMUT_ADD || OP == RMUT_ADD_INPLACE || OP == RMUT_RANGE;
-  if ((OP == RMUT_ADD || OP == RMUT_RANGE) && key != ra.hbs && key != ra.hbl) {  // rangeOfOnes(0, 65536): a full run container
-    w_place(t, true, reinterpret_cast<const uint8_t*>(g_full_run_rm), false, lds, 6, 65536, (uint32_t)key, DK_R, oc);
+  if ((OP == RMUT_ADD || OP == RMUT_RANGE) && key != ra.hbs && key != ra.hbl) {  // rangeOfOnes(0, 65536)
+    w_full_run(t, (uint32_t)key, oc, lds);
     return;
   }
-  if (!present) {  // rangeOfOnes(lo, hi + 1) (add / flip), written by lane 0
-    uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
-    const int n = hi - lo + 1;
-    const bool arr = OP != RMUT_RANGE && n <= 2;  // Container.rangeOfOnes; bitmapOfRange: RunContainer's
-    uint16_t* p = reinterpret_cast<uint16_t*>(arr ? slot : slot + 2);
-    if (lane_id() == 0) {
-      if (arr) {
-        p[0] = (uint16_t)lo;
-        p[1] = (uint16_t)hi;
-      } else {
-        p[0] = 1;
-        p[1] = (uint16_t)lo;
-        p[2] = (uint16_t)(hi - lo);
-      }
-    }
-    w_place(t, true, reinterpret_cast<const uint8_t*>(p), false, lds, arr ? 2u * n : 6u, (uint32_t)n, (uint32_t)key,
-            arr ? DK_A : DK_R, oc);
+  if (!present) {  // add / flip: Container.rangeOfOnes(lo, hi + 1); bitmapOfRange: RunContainer's, never an array
+    w_range_of_ones(t, (uint32_t)key, lo, hi, OP != RMUT_RANGE, oc, lds);
     return;
   }
   WCtr x;
@@ -179,7 +131,7 @@ __device__ __forceinline__ void rmut_task(uint32_t t, const PTask& tk, const uin
   }
   const int c = w_card(x);
   if (c == 0) {  // remove / flip emptied the container: dropped
-    w_place(t, false, nullptr, true, lds, 0, 0, (uint32_t)key, DK_A, oc);
+    w_drop(t, (uint32_t)key, oc, lds);
     return;
   }
   const int kx = tk.kind_a;
@@ -187,66 +139,36 @@ __device__ __forceinline__ void rmut_task(uint32_t t, const PTask& tk, const uin
   if (ADD) kind = kx == DK_A ? by_card(c) : kx;
   else if (OP == RMUT_REMOVE) kind = kx == DK_B ? ((BUF ? c < 4096 : c <= 4096) ? DK_A : DK_B) : kx;
   else kind = kx == DK_R ? eff(c, w_runs(x)) : by_card(c);
-  if (kind == DK_B) {  // registers straight to the task's slot
-    uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
-    w_store_bitmap(slot, x);
-    w_place(t, true, slot, false, lds, 8192, (uint32_t)c, (uint32_t)key, DK_B, oc);
-    return;
-  }
-  if (kind == DK_R && OP != RMUT_FLIP) {
-    const int nr = w_runs(x);
-    if (nr > 2047) {
-      w_place_big_runs(t, (uint32_t)key, x, c, nr, oc, big, lds);
-      return;
-    }
-  }
-  const uint32_t len = w_stage(kind, x, c, lds);
-  w_place(t, true, nullptr, true, lds, len, (uint32_t)c, (uint32_t)key, kind, oc);
+  // add / remove keep a run container one whatever its size; flip's toEfficientContainer at most 2047 runs
+  w_emit(t, (uint32_t)key, x, c, kind, oc, lds, OP != RMUT_FLIP ? &big : nullptr);
 }
 
 constexpr int kRmWaves = 4;
 
-// one wave per task over a static stride, the next record fetched while a task runs
 template <int OP, bool BUF>
 __global__ __launch_bounds__(256, 4) void k_rmut(const PTask* __restrict__ tasks, const uint32_t* __restrict__ n_tasks,
                                               const uint8_t* pa, RmutArgs ra, OutCtx oc, BigRuns big) {
   __shared__ __align__(16) uint32_t lds_all[kRmWaves][2048];
-  const int w = threadIdx.x >> 6;
-  uint32_t* lds = lds_all[w];
-  const uint32_t nt = uni(*n_tasks);
-  const uint32_t stride = gridDim.x * kRmWaves;
-  uint32_t t = uni(blockIdx.x * kRmWaves + w);
-  if (t >= nt) return;
-  PTask cur = load_task(tasks, t);
-  for (;;) {
-    const uint32_t tn = t + stride;
-    PTask nxt;
-    if (tn < nt) nxt = load_task(tasks, tn);
-    rmut_task<OP, BUF>(t, cur, pa, ra, oc, big, lds);
-    if (tn >= nt) break;
-    t = tn;
-    cur = nxt;
-  }
+  for_each_wave_task(tasks, n_tasks, lds_all, [&](uint32_t t, const PTask& tk, uint32_t* lds) {
+    rmut_task<OP, BUF>(t, tk, pa, ra, oc, big, lds);
+  });
 }
 
-void launch_rmut(hipStream_t s, const uint32_t* koa, const CDesc* da, const uint8_t* pa, RmutArgs ra, bool buf,
-                 uint64_t* wg_epoch, uint32_t epoch, PTask* tasks, uint32_t* n_tasks, OutCtx oc, uint64_t* zlb,
-                 uint64_t* ztile, BigRuns big, int grid) {
-  hipLaunchKernelGGL(k_plan_rmut, dim3(256), dim3(256), 0, s, koa, da, pa, ra, wg_epoch, epoch, tasks, n_tasks, zlb,
-                     ztile, oc.err);
-  const int g0 = std::max(1, (grid + kRmWaves - 1) / kRmWaves);
-#define RBG_RMUT_LAUNCH(O, B)                                                                                    \
-  hipLaunchKernelGGL((k_rmut<O, B>), dim3(std::min(g0, resident_grid((const void*)&k_rmut<O, B>))), dim3(256), 0, s, \
-                     tasks, n_tasks, pa, ra, oc, big)
-  if (ra.op == RMUT_ADD) RBG_RMUT_LAUNCH(RMUT_ADD, false);
-  else if (ra.op == RMUT_ADD_INPLACE) RBG_RMUT_LAUNCH(RMUT_ADD_INPLACE, false);
-  else if (ra.op == RMUT_DERUN) RBG_RMUT_LAUNCH(RMUT_DERUN, false);
-  else if (ra.op == RMUT_LIMIT) RBG_RMUT_LAUNCH(RMUT_LIMIT, false);
-  else if (ra.op == RMUT_RANGE) RBG_RMUT_LAUNCH(RMUT_RANGE, false);
-  else if (ra.op == RMUT_FLIP) RBG_RMUT_LAUNCH(RMUT_FLIP, false);
-  else if (buf) RBG_RMUT_LAUNCH(RMUT_REMOVE, true);
-  else RBG_RMUT_LAUNCH(RMUT_REMOVE, false);
-#undef RBG_RMUT_LAUNCH
+void launch_rmut(hipStream_t s, BmView A, RmutArgs ra, bool buf, PlanOut po, OutCtx oc, BigRuns big, int grid) {
+  hipLaunchKernelGGL(k_plan_rmut, dim3(256), dim3(256), 0, s, A, ra, po, oc.err);
+  auto run = [&](auto op, auto b) {
+    launch_resident<k_rmut<decltype(op)::value, decltype(b)::value != 0>>(s, grid, kRmWaves, po.tasks, po.n_tasks,
+                                                                         A.payload, ra, oc, big);
+  };
+  switch (ra.op) {
+    case RMUT_ADD: run(Int<RMUT_ADD>{}, Int<0>{}); break;
+    case RMUT_ADD_INPLACE: run(Int<RMUT_ADD_INPLACE>{}, Int<0>{}); break;
+    case RMUT_DERUN: run(Int<RMUT_DERUN>{}, Int<0>{}); break;
+    case RMUT_LIMIT: run(Int<RMUT_LIMIT>{}, Int<0>{}); break;
+    case RMUT_RANGE: run(Int<RMUT_RANGE>{}, Int<0>{}); break;
+    case RMUT_FLIP: run(Int<RMUT_FLIP>{}, Int<0>{}); break;
+    default: buf ? run(Int<RMUT_REMOVE>{}, Int<1>{}) : run(Int<RMUT_REMOVE>{}, Int<0>{}); break;
+  }
 }
 
 }  // namespace rbg

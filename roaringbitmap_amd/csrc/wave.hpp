@@ -529,21 +529,26 @@ __device__ __forceinline__ void plan_zero(uint64_t* lb_header, uint64_t* tile_st
   }
 }
 
-// Descriptor of key k in a single-bitmap batch through its key CSR (O(1), no search)
-__device__ __forceinline__ void resolve(const uint32_t* key_off, const CDesc* desc, const uint8_t* payload, uint32_t k,
-                                        uint64_t& slot, uint32_t& card, uint8_t& kind, uint16_t& nruns) {
-  const uint32_t p = key_off[k];
-  if (key_off[k + 1] > p) {
-    const CDesc d = desc[p];
-    slot = d.slot;
-    card = d.card;
-    kind = d.kind;
-    nruns = d.kind == DK_R ? *reinterpret_cast<const uint16_t*>(payload + d.slot + 2) : 0;
+// One side of a task record (SIDE 0: a, 1: b): no container of that operand under the task's key ...
+template <int SIDE>
+__device__ __forceinline__ void ptask_absent(PTask& t) {
+  (SIDE ? t.slot_b : t.slot_a) = 0;
+  (SIDE ? t.card_b : t.card_a) = 0;
+  (SIDE ? t.kind_b : t.kind_a) = kAbsent;
+  (SIDE ? t.nruns_b : t.nruns_a) = 0;
+}
+// ... or the descriptor of key k in a single-bitmap batch through its key CSR (O(1), no search)
+template <int SIDE>
+__device__ __forceinline__ void resolve(const BmView& v, uint32_t k, PTask& t) {
+  const uint32_t p = v.key_off[k];
+  if (v.key_off[k + 1] > p) {
+    const CDesc d = v.desc[p];
+    (SIDE ? t.slot_b : t.slot_a) = d.slot;
+    (SIDE ? t.card_b : t.card_a) = d.card;
+    (SIDE ? t.kind_b : t.kind_a) = d.kind;
+    (SIDE ? t.nruns_b : t.nruns_a) = d.kind == DK_R ? *reinterpret_cast<const uint16_t*>(v.payload + d.slot + 2) : 0;
   } else {
-    slot = 0;
-    card = 0;
-    kind = kAbsent;
-    nruns = 0;
+    ptask_absent<SIDE>(t);
   }
 }
 
@@ -564,8 +569,9 @@ __device__ __forceinline__ PTask load_task(const PTask* tasks, uint32_t t) {
 // publishes its task count tagged with the op's epoch, sums the counts of the workgroups before it
 // (one per thread, waiting for the epoch), and writes its flagged tasks straight into the dense task
 // list in key order.  The last workgroup writes the task count.
-__device__ __forceinline__ void plan_emit(int f, const PTask& t, uint64_t* wg_epoch, uint32_t epoch, PTask* tasks,
-                                          uint32_t* n_tasks, uint32_t* err) {
+__device__ __forceinline__ void plan_emit(int f, const PTask& t, const PlanOut& po, uint32_t* err) {
+  uint64_t* wg_epoch = po.wg_epoch;
+  const uint32_t epoch = po.epoch;
   __shared__ int wt[4];
   __shared__ int wb[4];
   int tot;
@@ -597,8 +603,8 @@ __device__ __forceinline__ void plan_emit(int f, const PTask& t, uint64_t* wg_ep
   const uint32_t base = (uint32_t)(wb[0] + wb[1] + wb[2] + wb[3]);
   int wpre = 0;
   for (int i = 0; i < (int)(threadIdx.x >> 6); i++) wpre += wt[i];
-  if (f) tasks[base + wpre + lane_pre] = t;
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *n_tasks = base + cnt;
+  if (f) po.tasks[base + wpre + lane_pre] = t;
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) *po.n_tasks = base + cnt;
 }
 
 __device__ __forceinline__ void plan_count(int f, uint32_t* wg_count) {
@@ -1285,6 +1291,11 @@ __device__ __forceinline__ void w_place(uint32_t t, bool keep, const uint8_t* sr
   }
 }
 
+// no container under this key (an empty result is dropped)
+__device__ __forceinline__ void w_drop(uint32_t t, uint32_t key, const OutCtx& oc, const uint32_t* lds) {
+  w_place(t, false, nullptr, true, lds, 0, 0, key, DK_A, oc);
+}
+
 // A run result of more than 2047 runs (results that stay run containers whatever their size: the buffer
 // package's run AND / ANDNOT run, add / remove of an input run container that large) into the big-run arena: [u16 nruns][(start, length - 1) pairs], straight from the
 // registers (w_stage_runs_chunk without the LDS cap), then the ends turned into lengths.
@@ -1301,7 +1312,7 @@ __device__ __forceinline__ void w_place_big_runs(uint32_t t, uint32_t key, const
   }
   off = __shfl(off, 0);
   if (off == ~0ull) {
-    w_place(t, false, nullptr, true, lds, 0, 0, key, DK_A, oc);
+    w_drop(t, key, oc, lds);
     return;
   }
   uint16_t* dst = reinterpret_cast<uint16_t*>(big.base + off);
@@ -1311,6 +1322,98 @@ __device__ __forceinline__ void w_place_big_runs(uint32_t t, uint32_t key, const
   for (int p = lane_id(); p < nr; p += 64) dst[2 + 2 * p] = (uint16_t)(dst[2 + 2 * p] - dst[1 + 2 * p]);
   if (lane_id() == 0) dst[0] = (uint16_t)nr;
   w_place(t, true, big.base + off, false, lds, len, (uint32_t)card, key, DK_R, oc);
+}
+
+// ---------------------------------------------------------------------------
+// What a wave-per-task op leaves for task t, and the loop that hands a wave its tasks
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ uint8_t* w_slot(uint32_t t, const OutCtx& oc) { return oc.scratch + (size_t)t * kSlotBytes; }
+
+// an input container as it is (slot: its slot in the operand's arena); the second form takes side a of a task
+__device__ __forceinline__ void w_clone(uint32_t t, uint32_t key, int kind, uint32_t card, uint32_t nruns,
+                                        const uint8_t* slot, const OutCtx& oc, const uint32_t* lds) {
+  w_place(t, true, slot + (kind == DK_R ? 2 : 0), false, lds, ser_len_of(kind, card, nruns), card, key, kind, oc);
+}
+__device__ __forceinline__ void w_clone(uint32_t t, const PTask& tk, const uint8_t* pa, const OutCtx& oc,
+                                        const uint32_t* lds) {
+  w_clone(t, tk.key, tk.kind_a, tk.card_a, tk.nruns_a, pa + tk.slot_a, oc, lds);
+}
+// The register container x of c values as a container of `kind`: a bitmap straight to the task's slot, an
+// array or a run container staged in the wave's LDS.  A staged run container holds at most 2047 runs (what
+// toEfficientContainer keeps); where a run result keeps its runs whatever their number (raw_runs), the
+// caller gives the arena (big) and a result above 2047 runs goes there.
+__device__ __forceinline__ void w_emit(uint32_t t, uint32_t key, const WCtr& x, int c, int kind, const OutCtx& oc,
+                                       uint32_t* lds, const BigRuns* big = nullptr, bool raw_runs = true) {
+  if (kind == DK_B) {
+    uint8_t* slot = w_slot(t, oc);
+    w_store_bitmap(slot, x);
+    w_place(t, true, slot, false, lds, 8192, (uint32_t)c, key, DK_B, oc);
+    return;
+  }
+  if (big && raw_runs && kind == DK_R) {
+    const int nr = w_runs(x);
+    if (nr > 2047) {
+      w_place_big_runs(t, key, x, c, nr, oc, *big, lds);
+      return;
+    }
+  }
+  const uint32_t len = w_stage(kind, x, c, lds);
+  w_place(t, true, nullptr, true, lds, len, (uint32_t)c, key, kind, oc);
+}
+// Container.rangeOfOnes(lo, hi + 1) (RB/Container.java:29-37), written by lane 0 into the task's slot: an
+// array up to two values where the caller's rule allows one, else a run container
+__device__ __forceinline__ void w_range_of_ones(uint32_t t, uint32_t key, int lo, int hi, bool allow_array,
+                                                const OutCtx& oc, const uint32_t* lds) {
+  uint8_t* slot = w_slot(t, oc);
+  const int n = hi - lo + 1;
+  const bool arr = allow_array && n <= 2;
+  uint16_t* p = reinterpret_cast<uint16_t*>(arr ? slot : slot + 2);
+  if (lane_id() == 0) {
+    if (arr) {
+      p[0] = (uint16_t)lo;
+      p[1] = (uint16_t)hi;
+    } else {
+      p[0] = 1;
+      p[1] = (uint16_t)lo;
+      p[2] = (uint16_t)(hi - lo);
+    }
+  }
+  w_place(t, true, reinterpret_cast<const uint8_t*>(p), false, lds, arr ? 2u * n : 6u, (uint32_t)n, key,
+          arr ? DK_A : DK_R, oc);
+}
+// RunContainer.full() (RB/RunContainer.java:1663-1665): every full result references one constant payload,
+// nruns = 1, (0, 65535); slack after it for the serializer's 16 B over-read
+static __device__ uint16_t g_full_run[16] = {1, 0, 0xFFFF};
+__device__ __forceinline__ void w_full_run(uint32_t t, uint32_t key, const OutCtx& oc, const uint32_t* lds) {
+  w_place(t, true, reinterpret_cast<const uint8_t*>(g_full_run), false, lds, 6, 65536, key, DK_R, oc);
+}
+
+// One wave per task of a planned list, the next record fetched while a task runs: body(t, task, lds) with
+// lds the wave's row of lds_all.  Strided: task w, w + waves, ... of the grid's waves (every wave draws from
+// the whole list); chunked: ceil(nt / waves) consecutive tasks per wave (neighbouring keys to one wave).
+enum TaskWalk : int { kStrided = 0, kChunked = 1 };
+template <TaskWalk WALK = kStrided, int WAVES, int N, class Body>
+__device__ __forceinline__ void for_each_wave_task(const PTask* tasks, const uint32_t* n_tasks,
+                                                   uint32_t (&lds_all)[WAVES][N], Body body) {
+  const int w = threadIdx.x >> 6;
+  uint32_t* lds = lds_all[w];
+  const uint32_t nt = uni(*n_tasks);
+  const uint32_t nw = gridDim.x * WAVES;
+  const uint32_t per = (nt + nw - 1) / nw;
+  uint32_t t = uni((blockIdx.x * WAVES + w) * (WALK == kChunked ? per : 1u));
+  const uint32_t step = WALK == kChunked ? 1u : nw;
+  const uint32_t tend = WALK == kChunked ? min(nt, t + per) : nt;
+  if (t >= tend) return;
+  PTask cur = load_task(tasks, t);
+  for (;;) {
+    const uint32_t tn = t + step;
+    PTask nxt;
+    if (tn < tend) nxt = load_task(tasks, tn);  // in flight while this task runs
+    body(t, cur, lds);
+    if (tn >= tend) break;
+    t = tn;
+    cur = nxt;
+  }
 }
 
 __device__ __forceinline__ void wg_passthrough(uint32_t t, const CDesc& d, const uint8_t* payload, const OutCtx& oc,

@@ -749,7 +749,7 @@ __global__ __launch_bounds__(256, 4) void k_shy_wave(const Task* __restrict__ ta
       continue;
     }
     if (c == 0) {  // dropped (:408)
-      w_place(t, false, nullptr, true, lds, 0, 0, key, DK_A, oc);
+      w_drop(t, key, oc, lds);
       continue;
     }
     if (arr) {
@@ -759,15 +759,7 @@ __global__ __launch_bounds__(256, 4) void k_shy_wave(const Task* __restrict__ ta
       w_place(t, true, nullptr, true, lds, 2u * (uint32_t)c, (uint32_t)c, key, DK_A, oc);
       continue;
     }
-    const int kind = c == 65536 ? DK_R : by_card(c);  // BitmapContainer.repairAfterLazy
-    if (kind == DK_B) {
-      uint8_t* slot = oc.scratch + (size_t)t * kSlotBytes;
-      w_store_bitmap(slot, x);
-      w_place(t, true, slot, false, lds, 8192, (uint32_t)c, key, DK_B, oc);
-      continue;
-    }
-    const uint32_t len = w_stage(kind, x, c, lds);
-    w_place(t, true, nullptr, true, lds, len, (uint32_t)c, key, kind, oc);
+    w_emit(t, key, x, c, c == 65536 ? DK_R : by_card(c), oc, lds);  // BitmapContainer.repairAfterLazy
   }
   if (A.rd_bytes && l == 0 && rd_total) atomicAdd(A.rd_bytes, rd_total);
 }

@@ -134,6 +134,16 @@ def test_quirks_and_errors(gpu):
         x.orNot(x, 10)
 
 
+def test_range_of_ones_at_max_key(gpu):
+    """maxKey held by neither bitmap, lastRun of 1, 2 and 3 values: rangeOfOnes(0, lastRun) is an array up to
+    two values, then a run container; at key 0 and after a full key"""
+    a = O.from_values(np.array([5 << 16], dtype=np.uint32))
+    b = O.from_values(np.array([(6 << 16) + 9], dtype=np.uint32))
+    for base in (0, 1 << 16):
+        for n in (1, 2, 3):
+            _check(a, b, base + n, f"neither, lastRun {n}")
+
+
 def test_dense_full_universe(gpu):
     """rangeEnd = 2^32 over 4096-key operands: 65,536 result containers (the full-run fast path)."""
     rng = np.random.default_rng(77)

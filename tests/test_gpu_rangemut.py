@@ -73,6 +73,15 @@ def test_every_container_mode(gpu):
             _check(buf, st, en, m)
 
 
+def test_range_of_ones_on_absent_key(gpu):
+    """add / flip of 1, 2 and 3 values on a key the bitmap does not hold (Container.rangeOfOnes: an array up to
+    two values, then a run container), at the start of the key and across its end"""
+    buf = encode([(1, A, [7]), (4, R, np.arange(100, 200))])
+    for st in (5, (2 << 16) + 65534):
+        for n in (1, 2, 3):
+            _check(buf, st, st + n, f"absent key, {n} values")
+
+
 def test_buffer_remove_keeps_4096_value_bitmap(gpu):
     x = encode([(0, A, np.arange(0, 4000, 2)), (1, B, np.arange(0, 65536, 3))])
     assert O.range_mut("remove", x, (1 << 16) + 12288, 2 << 16, buffer=True) != \
