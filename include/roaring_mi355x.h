@@ -699,4 +699,9 @@ int rbg_ctx_fetch_shard_device_dyn(rbg_ctx* ctx, const void* layout, int rank, i
 #ifdef __cplusplus
 }
 #endif
+
+/* Dense bitsets and masks to resident bitmaps and back (BitSetUtil, RB/BitSetUtil.java): the entry points of
+ * that interchange form, each citing its method, are declared in the file below. */
+#include "roaring_mi355x_bitset.h"
+
 #endif /* ROARING_MI355X_H */

@@ -30,6 +30,7 @@ SOURCES = [
     "rankdir.hip",
     "build.hip",
     "expand.hip",
+    "bitset.hip",
     "bsibuild.hip",
     "bsival.hip",
     "bsiadd.hip",
@@ -44,7 +45,7 @@ SOURCES = [
     "engine_api.cpp",
     "format.cpp",
 ]
-HEADERS = ["device.hpp", "kernels.hpp", "format.hpp", "wave.hpp", "vb.hpp", "bsival.hpp", "engine.hpp"]
+HEADERS = ["device.hpp", "kernels.hpp", "format.hpp", "wave.hpp", "vb.hpp", "bsival.hpp", "engine.hpp", "build.hpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result"]
 
@@ -55,8 +56,9 @@ def _mtime(p):
 
 def build(verbose=False, jobs=8):
     os.makedirs(OBJDIR, exist_ok=True)
-    inc = os.path.join(os.path.dirname(HERE), "include", "roaring_mi355x.h")
-    dep_time = max([_mtime(os.path.join(CSRC, h)) for h in HEADERS] + [_mtime(inc), _mtime(__file__)])
+    inc = os.path.join(os.path.dirname(HERE), "include")
+    dep_time = max([_mtime(os.path.join(CSRC, h)) for h in HEADERS] + [_mtime(__file__)]
+                   + [_mtime(os.path.join(inc, h)) for h in ("roaring_mi355x.h", "roaring_mi355x_bitset.h")])
     procs, objs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

@@ -161,6 +161,18 @@ SIGNATURES = {
 }
 EXPORTED = list(SIGNATURES)  # the names alone
 
+# Every entry point of include/roaring_mi355x_bitset.h (BitSetUtil: dense bitsets and masks), which
+# roaring_mi355x.h includes, in that file's order.  lib() applies it with the table above.
+RBG_BITS_PACKED, RBG_BITS_BYTES = 0, 1
+BITSET_SIGNATURES = {
+    "rbg_ctx_from_bitset": (ci, [vp, vp, u64, ci, ci, i32p]),
+    "rbg_ctx_from_bitset_device": (ci, [vp, vp, u64, ci, ci, i32p]),
+    "rbg_ctx_to_bitset": (ci, [vp, i32, sz, u64, u64, ci, vp]),
+    "rbg_ctx_to_bitset_device": (ci, [vp, i32, sz, u64, u64, ci, vp]),
+    "rbg_bitset_build": (ci, [vp, u64, ci, ci, buf]),
+    "rbg_bitset_expand": (ci, [u8p, sz, buf]),
+}
+
 _lib = None
 
 
@@ -173,7 +185,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the engine has no CPU fallback)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in SIGNATURES.items():
+        for name, (restype, argtypes) in {**SIGNATURES, **BITSET_SIGNATURES}.items():
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
         _lib = L

@@ -18,8 +18,7 @@
 //
 // Types (format.cpp: make_ctr with kind_hint -1): by_card, and with run_optimize runopt_kind
 // (device.hpp).
-#include "kernels.hpp"
-#include "wave.hpp"
+#include "build.hpp"
 
 namespace rbg {
 
@@ -93,46 +92,11 @@ __global__ __launch_bounds__(256) void k_bld_scatter(const uint32_t* __restrict_
   }
 }
 
-struct BldInfo {
-  uint32_t card;
-  uint16_t nruns;
-  uint8_t kind;
-  uint8_t pad;
-};
-static_assert(sizeof(BldInfo) == kBldInfoBytes, "the engine sizes the plan's table by kBldInfoBytes");
-
-// totals (u64, zeroed by the caller): [0..2] containers of kind A / B / R, [3] serialized payload
-// bytes, [4] cardinality
+// the plan and write stages over the scattered workspace (build.hpp: the bodies, shared with bitset.hip)
 __global__ __launch_bounds__(256) void k_bld_plan(const uint8_t* __restrict__ ws, uint64_t n, int run_optimize,
                                                   BldInfo* __restrict__ info, uint64_t* __restrict__ size,
                                                   unsigned long long* __restrict__ totals) {
-  const int lane = lane_id();
-  const uint64_t nw = (uint64_t)gridDim.x * 4;
-  unsigned long long cnt[3] = {0, 0, 0}, ser = 0, cards = 0;
-  for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += nw) {
-    WCtr x;
-    w_load_bitmap(ws + 8192 * i, x);
-    const int card = w_card(x);
-    int kind = by_card(card), nruns = 0;
-    if (run_optimize) {
-      nruns = w_runs(x);
-      kind = runopt_kind(kind, card, nruns);
-    }
-    const uint32_t len = ser_len_of(kind, (uint32_t)card, (uint32_t)nruns);
-    if (lane == 0) {
-      info[i] = BldInfo{(uint32_t)card, (uint16_t)nruns, (uint8_t)kind, 0};
-      size[i] = slot_bytes(kind, len);
-    }
-    cnt[kind]++;
-    ser += len;
-    cards += (unsigned long long)card;
-  }
-  if (lane == 0) {  // one add per counter per wave
-    for (int k = 0; k < 3; k++)
-      if (cnt[k]) atomicAdd(&totals[k], cnt[k]);
-    if (ser) atomicAdd(&totals[3], ser);
-    if (cards) atomicAdd(&totals[4], cards);
-  }
+  bld_plan_body(WsSource{ws}, n, run_optimize, info, size, totals);
 }
 
 __global__ __launch_bounds__(256, 4) void k_bld_write(const uint8_t* __restrict__ ws, uint64_t n,
@@ -142,25 +106,7 @@ __global__ __launch_bounds__(256, 4) void k_bld_write(const uint8_t* __restrict_
                                                       uint32_t* __restrict__ bm, uint32_t* __restrict__ bm_off,
                                                       uint8_t* __restrict__ payload) {
   __shared__ __align__(16) uint32_t lds_all[4][2048];
-  uint32_t* lds = lds_all[threadIdx.x >> 6];
-  const int lane = lane_id();
-  const uint64_t nw = (uint64_t)gridDim.x * 4;
-  if (blockIdx.x == 0 && threadIdx.x == 0) {  // the bitmap CSR of a one-bitmap batch
-    bm_off[0] = 0;
-    bm_off[1] = (uint32_t)n;
-  }
-  for (uint64_t i = (uint64_t)blockIdx.x * 4 + (threadIdx.x >> 6); i < n; i += nw) {
-    const BldInfo in = info[i];
-    const uint64_t o = off[i];
-    const int kind = in.kind;
-    WCtr x;
-    w_load_bitmap(ws + 8192 * i, x);
-    w_write_slot(kind, x, (int)in.card, lds, payload + o);
-    if (lane == 0) {
-      desc[i] = CDesc{o, in.card, keys[i], (uint8_t)kind, 0};
-      bm[i] = 0;
-    }
-  }
+  bld_write_body(WsSource{ws}, n, info, off, keys, desc, bm, bm_off, payload, lds_all);
 }
 
 void launch_bld_keys(hipStream_t s, const uint32_t* v, uint64_t n, uint8_t* flag, uint16_t* keys, uint32_t* key_off,

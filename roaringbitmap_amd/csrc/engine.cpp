@@ -537,8 +537,12 @@ int ctx_to_values_host(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t
 // (build.hip).  Two read-backs: the container count (to size the workspace of 8 KiB bitmaps) and the
 // totals (payload size, kinds, cardinality).  The values are read by two kernels: they must not change
 // until the call returns.
-int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32_t* out_id) {
+// The source is either those values or (bits != null) a dense bitset's own words, which then stand where the
+// scattered workspace stands (bitset.hip): at most 2^29 bytes, read by three kernels.
+static int build_batch(Ctx* c, const uint32_t* v_dev, size_t n, const uint8_t* bits, uint64_t nbytes, bool run_opt,
+                       int32_t* out_id) {
   hipStream_t s = c->stream;
+  if (bits) n = (size_t)((nbytes + 8191) / 8192);  // the bound of the key count
   const int32_t id = new_batch(c);
   Batch& b = *c->batches[id];
   struct Drop {  // an error below frees the half-built batch
@@ -557,7 +561,8 @@ int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32
                                                                 // bytes, [5] cardinality, [6] slot bytes
   HIPCHK(hipMemsetAsync(c->flag.p, 0, kMaxKeys, s));
   HIPCHK(hipMemsetAsync(sc, 0, 64, s));
-  launch_bld_keys(s, v_dev, n, c->flag.as<uint8_t>(), b.keys.as<uint16_t>(), b.key_off.as<uint32_t>(), sc);
+  if (bits) launch_bits_flags(s, bits, nbytes, c->flag.as<uint8_t>(), b.keys.as<uint16_t>(), b.key_off.as<uint32_t>(), sc);
+  else launch_bld_keys(s, v_dev, n, c->flag.as<uint8_t>(), b.keys.as<uint16_t>(), b.key_off.as<uint32_t>(), sc);
   HIPCHK(hipGetLastError());
   unsigned long long h[8] = {};
   HIPCHK(hipMemcpyAsync(h, sc, 8, hipMemcpyDeviceToHost, s));
@@ -565,13 +570,19 @@ int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32
   const size_t C = (size_t)h[0];
   dbg(s, "from_values: keys");
   if (C) {
-    CHK(pool_take(c, ws, 8192 * C));
-    HIPCHK(hipMemsetAsync(ws.p, 0, 8192 * C, s));
-    launch_bld_scatter(s, v_dev, n, b.key_off.as<uint32_t>(), ws.as<uint32_t>());
+    if (!bits) {
+      CHK(pool_take(c, ws, 8192 * C));
+      HIPCHK(hipMemsetAsync(ws.p, 0, 8192 * C, s));
+      launch_bld_scatter(s, v_dev, n, b.key_off.as<uint32_t>(), ws.as<uint32_t>());
+    }
     CHK(c->bld_info.ensure(kBldInfoBytes * C));
     CHK(c->bld_size.ensure(8 * C + 16));
     CHK(c->bld_part.ensure(8 * (scan_parts(C) + 1)));
-    launch_bld_plan(s, ws.as<uint8_t>(), C, run_opt ? 1 : 0, c->bld_info.p, c->bld_size.as<uint64_t>(), sc + 1);
+    if (bits)
+      launch_bits_plan(s, bits, nbytes, b.keys.as<uint16_t>(), C, run_opt ? 1 : 0, c->bld_info.p,
+                       c->bld_size.as<uint64_t>(), sc + 1);
+    else
+      launch_bld_plan(s, ws.as<uint8_t>(), C, run_opt ? 1 : 0, c->bld_info.p, c->bld_size.as<uint64_t>(), sc + 1);
     launch_exclusive_scan(s, c->bld_size.as<uint64_t>(), c->bld_size.as<uint64_t>(), C, c->bld_part.as<uint64_t>(),
                           reinterpret_cast<uint64_t*>(sc + 6));
     HIPCHK(hipGetLastError());
@@ -583,7 +594,10 @@ int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32
   CHK(pool_take(c, b.desc, sizeof(CDesc) * C + 16));
   CHK(pool_take(c, b.bm, 4 * C + 16));
   CHK(pool_take(c, b.payload, b.payload_bytes + 64));
-  if (C)
+  if (C && bits)
+    launch_bits_write(s, bits, nbytes, b.keys.as<uint16_t>(), C, c->bld_info.p, c->bld_size.as<uint64_t>(),
+                      b.desc.as<CDesc>(), b.bm.as<uint32_t>(), b.bm_off.as<uint32_t>(), b.payload.as<uint8_t>());
+  else if (C)
     launch_bld_write(s, ws.as<uint8_t>(), C, c->bld_info.p, c->bld_size.as<uint64_t>(), b.keys.as<uint16_t>(),
                      b.desc.as<CDesc>(), b.bm.as<uint32_t>(), b.bm_off.as<uint32_t>(), b.payload.as<uint8_t>());
   else
@@ -609,23 +623,29 @@ int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32
   return RBG_OK;
 }
 
+int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32_t* out_id) {
+  return build_batch(c, v_dev, n, nullptr, 0, run_opt, out_id);
+}
+
 // one empty bitmap as a new batch: the result of a query that no column can satisfy
 int ctx_empty_bitmap(Ctx* c, int32_t* out_id) { return ctx_from_values(c, nullptr, 0, false, out_id); }
 
-// n 32-bit words from host memory into dst (device), through the context's pinned buffer, a chunk at a time
-int upload_words(Ctx* c, void* dst, const void* src, size_t n) {
-  constexpr size_t kChunk = 16u << 20;  // words per staged copy (64 MiB)
+// n bytes from host memory into dst (device), through the context's pinned buffer, a chunk at a time
+static int upload_bytes(Ctx* c, void* dst, const void* src, size_t n) {
+  constexpr size_t kChunk = 64u << 20;  // bytes per staged copy
   if (!n) return RBG_OK;
-  CHK(pinned_ensure(c, 4 * std::min(n, kChunk)));
+  CHK(pinned_ensure(c, std::min(n, kChunk)));
   HIPCHK(hipStreamSynchronize(c->stream));  // nothing enqueued earlier still reads the staging buffer
   for (size_t off = 0; off < n; off += kChunk) {
     const size_t m = std::min(kChunk, n - off);
-    std::memcpy(c->pinned, reinterpret_cast<const uint32_t*>(src) + off, 4 * m);
-    HIPCHK(hipMemcpyAsync(reinterpret_cast<uint32_t*>(dst) + off, c->pinned, 4 * m, hipMemcpyHostToDevice, c->stream));
+    std::memcpy(c->pinned, reinterpret_cast<const uint8_t*>(src) + off, m);
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(dst) + off, c->pinned, m, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return RBG_OK;
 }
+// n 32-bit words
+int upload_words(Ctx* c, void* dst, const void* src, size_t n) { return upload_bytes(c, dst, src, 4 * n); }
 
 // ctx_from_values from host memory
 int ctx_from_values_host(Ctx* c, const uint32_t* v, size_t n, bool run_opt, int32_t* out_id) {
@@ -635,6 +655,115 @@ int ctx_from_values_host(Ctx* c, const uint32_t* v, size_t n, bool run_opt, int3
   const int st = ctx_from_values(c, in.as<uint32_t>(), n, run_opt, out_id);
   pool_put(c, in);
   return st;
+}
+
+// ---- dense bitsets (bitset.hip): BitSetUtil, RB/BitSetUtil.java ----
+// The key arithmetic of bitmapOf (from * Long.SIZE, :169) is Java int: a bitset has at most 2^32 bits.
+constexpr uint64_t kBitsetMaxBits = 1ull << 32;
+
+// the refusals of a build, decided from the arguments alone; device: bits is read in place by the kernels
+int check_bitset_build(const void* bits, uint64_t n, int layout, bool device) {
+  if (layout != RBG_BITS_PACKED && layout != RBG_BITS_BYTES) {
+    set_err("bitset: unknown layout (RBG_BITS_PACKED or RBG_BITS_BYTES)");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (n && !bits) {
+    set_err("bitset: no input");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (n > (layout == RBG_BITS_PACKED ? kBitsetMaxBits / 8 : kBitsetMaxBits)) {
+    set_err("bitset: more than 2^32 bits");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (device && layout == RBG_BITS_PACKED && (reinterpret_cast<uintptr_t>(bits) & 7)) {
+    set_err("bitset: packed words must be 8-byte aligned");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  return RBG_OK;
+}
+
+// the refusals of an expansion's window [first, first + n) of bit positions
+int check_bitset_window(uint64_t first, uint64_t n, int layout) {
+  if (layout != RBG_BITS_PACKED && layout != RBG_BITS_BYTES) {
+    set_err("bitset: unknown layout (RBG_BITS_PACKED or RBG_BITS_BYTES)");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (layout == RBG_BITS_PACKED && (first & 63)) {
+    set_err("bitset: a packed window starts at a multiple of 64");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (first > kBitsetMaxBits || n > kBitsetMaxBits - first) {
+    set_err("bitset: the window reaches past 2^32");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  return RBG_OK;
+}
+
+// BitSetUtil.bitmapOf(long[]) (:160-174, containerOf :270-283) / bitmapOf(ByteBuffer) (:185-259) [+ runOptimize]
+// of a dense bitset in device memory, as the batch ctx_from_values of its bit positions makes.  layout
+// RBG_BITS_PACKED: n bytes of little-endian 64-bit words, the last possibly cut short; RBG_BITS_BYTES: n mask
+// elements, first packed into a pooled buffer of words.  Arguments as check_bitset_build passes them.  The
+// input is read by up to four kernels: it must not change until the call returns.
+int ctx_from_bitset(Ctx* c, const void* bits_dev, uint64_t n, int layout, bool run_opt, int32_t* out_id) {
+  if (!n) return build_batch(c, nullptr, 0, nullptr, 0, run_opt, out_id);
+  if (layout == RBG_BITS_PACKED)
+    return build_batch(c, nullptr, 0, reinterpret_cast<const uint8_t*>(bits_dev), n, run_opt, out_id);
+  const uint64_t nbytes = 8 * ((n + 63) / 64);
+  DevBuf words;
+  CHK(pool_take(c, words, nbytes + 16));
+  launch_bits_pack(c->stream, reinterpret_cast<const uint8_t*>(bits_dev), n, words.as<uint64_t>());
+  HIPCHK(hipGetLastError());
+  const int st = build_batch(c, nullptr, 0, words.as<uint8_t>(), nbytes, run_opt, out_id);
+  pool_put(c, words);
+  return st;
+}
+
+// the same from host memory
+int ctx_from_bitset_host(Ctx* c, const void* bits, uint64_t n, int layout, bool run_opt, int32_t* out_id) {
+  DevBuf in;
+  CHK(pool_take(c, in, n + 16));
+  CHK(upload_bytes(c, in.p, bits, n));
+  const int st = ctx_from_bitset(c, in.p, n, layout, run_opt, out_id);
+  pool_put(c, in);
+  return st;
+}
+
+// BitSetUtil.toLongArray (:67-108) over the window [first, first + n) of bit positions of bitmap i of a batch,
+// into out_dev: packed words or mask bytes (launch_bits_expand), enqueued on the context stream; nothing is
+// read back.  Arguments as check_bitset_window passes them.
+int ctx_to_bitset(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t n, int layout, void* out_dev) {
+  Operand o;
+  CHK(resolve(c, batch, i, &o));
+  if (!n) return RBG_OK;
+  if (!out_dev || (layout == RBG_BITS_PACKED && (reinterpret_cast<uintptr_t>(out_dev) & 7))) {
+    set_err("bitset: no output buffer, or packed words not 8-byte aligned");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  launch_bits_expand(c->stream, o.key_off, o.desc, o.payload, first, n, layout == RBG_BITS_BYTES, out_dev);
+  HIPCHK(hipGetLastError());
+  return RBG_OK;
+}
+
+// the same into host memory, one window of at most 256 MiB on the device at a time
+int ctx_to_bitset_host(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t n, int layout, void* out) {
+  CHK(ctx_to_bitset(c, batch, i, first, 0, layout, nullptr));  // the operand check
+  if (!n) return RBG_OK;
+  if (!out) {
+    set_err("bitset: no output buffer");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  const bool mask = layout == RBG_BITS_BYTES;
+  const uint64_t window = mask ? 1ull << 28 : 1ull << 31;  // bit positions per pass; a multiple of 64
+  auto bytes_of = [&](uint64_t bits) { return mask ? bits : 8 * ((bits + 63) / 64); };
+  CHK(c->tv_out.ensure(bytes_of(std::min(n, window))));
+  for (uint64_t done = 0; done < n; done += window) {
+    const uint64_t w = std::min(window, n - done);
+    CHK(ctx_to_bitset(c, batch, i, first + done, w, layout, c->tv_out.p));
+    HIPCHK(hipMemcpyAsync(reinterpret_cast<uint8_t*>(out) + bytes_of(done), c->tv_out.p, bytes_of(w),
+                          hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+  }
+  return RBG_OK;
 }
 
 // ImmutableRoaringBitmap.and / andNot and MutableRoaringBitmap's static and / andNot

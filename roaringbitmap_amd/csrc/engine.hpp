@@ -256,6 +256,12 @@ int ctx_to_values_host(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t
                        uint64_t* n_out);
 int ctx_from_values(Ctx* c, const uint32_t* v_dev, size_t n, bool run_opt, int32_t* out_id);
 int ctx_from_values_host(Ctx* c, const uint32_t* v, size_t n, bool run_opt, int32_t* out_id);
+int check_bitset_build(const void* bits, uint64_t n, int layout, bool device);
+int check_bitset_window(uint64_t first, uint64_t n, int layout);
+int ctx_from_bitset(Ctx* c, const void* bits_dev, uint64_t n, int layout, bool run_opt, int32_t* out_id);
+int ctx_from_bitset_host(Ctx* c, const void* bits, uint64_t n, int layout, bool run_opt, int32_t* out_id);
+int ctx_to_bitset(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t n, int layout, void* out_dev);
+int ctx_to_bitset_host(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t n, int layout, void* out);
 int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, bool card_only, int key_lo = 0,
                  int key_hi = kMaxKeys);
 int ctx_ornot(Ctx* c, int32_t ia, size_t ma, int32_t ib, size_t mb, int64_t range_end, int flags);

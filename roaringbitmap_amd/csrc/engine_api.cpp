@@ -222,6 +222,84 @@ int rbg_expand_values(const uint8_t* buf, size_t len, rbg_buffer* out) {
   return RBG_OK;
 }
 
+/* ---- dense bitsets (bitset.hip): BitSetUtil.  The argument checks come before the session is entered, so a
+ * refusal needs no device. ---- */
+
+int rbg_ctx_from_bitset(rbg_ctx* ctx, const void* bits, uint64_t n, int layout, int run_optimize, int32_t* batch) {
+  CHK(check_bitset_build(bits, n, layout, false));
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!batch) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_from_bitset_host(c, bits, n, layout, run_optimize != 0, batch);
+}
+
+int rbg_ctx_from_bitset_device(rbg_ctx* ctx, const void* bits_dev, uint64_t n, int layout, int run_optimize,
+                               int32_t* batch) {
+  CHK(check_bitset_build(bits_dev, n, layout, true));
+  Ctx* c;
+  CHK(session(ctx, &c));
+  if (!batch) return RBG_ERR_ILLEGAL_ARGUMENT;
+  return ctx_from_bitset(c, bits_dev, n, layout, run_optimize != 0, batch);
+}
+
+int rbg_ctx_to_bitset(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t n, int layout, void* out) {
+  CHK(check_bitset_window(first, n, layout));
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_to_bitset_host(c, batch, i, first, n, layout, out);
+}
+
+int rbg_ctx_to_bitset_device(rbg_ctx* ctx, int32_t batch, size_t i, uint64_t first, uint64_t n, int layout,
+                             void* out_dev) {
+  CHK(check_bitset_window(first, n, layout));
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_to_bitset(c, batch, i, first, n, layout, out_dev);
+}
+
+int rbg_bitset_build(const void* bits, uint64_t n, int layout, int run_optimize, rbg_buffer* out) {
+  CHK(check_bitset_build(bits, n, layout, false));
+  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(ctx_from_bitset_host(c, bits, n, layout, run_optimize != 0, &id));
+  os.adopt(id);
+  return ctx_batch_fetch(c, id, 0, out);
+}
+
+// toLongArray's length (RB/BitSetUtil.java:76-79): lastBit = max(last, 64), rounded down to a multiple of 64
+static uint64_t words_in_use(uint64_t last) { return std::max<uint64_t>(last, 64) / 64 + 1; }
+
+int rbg_bitset_expand(const uint8_t* buf, size_t len, rbg_buffer* out) {
+  if (!out || (!buf && len)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  OneShot os;
+  CHK(os.open());
+  Ctx* c = os.c;
+  int32_t id;
+  CHK(os.load_separate(&buf, &len, 1, &id));
+  if (c->batches[id]->long_card == 0) return emit_bytes(nullptr, 0, out);  // new long[0] (:68-70)
+  const uint32_t q = 0xFFFFFFFFu;
+  int64_t last = -1;
+  CHK(ctx_point_host(c, PT_PREV, id, 0, &q, 1, &last));  // bitmap.last()
+  if (last >= (int64_t)1 << 31) {
+    set_err("bitmap has negative bits set");  // :72-75
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  const uint64_t nw = words_in_use((uint64_t)last);
+  uint8_t* p = (uint8_t*)std::malloc(8 * nw);
+  if (!p) return RBG_ERR_OUT_OF_MEMORY;
+  const int st = ctx_to_bitset_host(c, id, 0, 0, 64 * nw, RBG_BITS_PACKED, p);
+  if (st != RBG_OK) {
+    std::free(p);
+    return st;
+  }
+  out->data = p;
+  out->len = (size_t)(8 * nw);
+  return RBG_OK;
+}
+
 // x.limit(maxcardinality) (RB/RoaringBitmap.java:2457-2476).  The cut is planned from the serialized
 // header's cardinalities on the host (the reference's own loop walks getCardinality per container);
 // ctx_limit cuts on the device.

@@ -511,6 +511,26 @@ void launch_bld_plan(hipStream_t s, const uint8_t* ws, uint64_t n_ctr, int run_o
 void launch_bld_write(hipStream_t s, const uint8_t* ws, uint64_t n_ctr, const void* info, const uint64_t* off,
                       const uint16_t* keys, CDesc* desc, uint32_t* bm, uint32_t* bm_off, uint8_t* payload);
 
+// bitset.hip: the same batch from a dense bitset in device memory, BitSetUtil.bitmapOf(long[]) / (ByteBuffer)
+// (RB/BitSetUtil.java:160-174, 185-259) [+ runOptimize].  bits: nbytes <= 2^29 bytes of little-endian 64-bit
+// words, 8 B aligned, the last word possibly cut short; no byte at or past nbytes is read.  The three
+// launches stand where launch_bld_keys, launch_bld_plan and launch_bld_write stand, with the same arguments
+// otherwise; there is no workspace.
+void launch_bits_flags(hipStream_t s, const uint8_t* bits, uint64_t nbytes, uint8_t* flag, uint16_t* keys,
+                       uint32_t* key_off, unsigned long long* n_ctr);
+void launch_bits_plan(hipStream_t s, const uint8_t* bits, uint64_t nbytes, const uint16_t* keys, uint64_t n_ctr,
+                      int run_optimize, void* info, uint64_t* size, unsigned long long* totals);
+void launch_bits_write(hipStream_t s, const uint8_t* bits, uint64_t nbytes, const uint16_t* keys, uint64_t n_ctr,
+                       const void* info, const uint64_t* off, CDesc* desc, uint32_t* bm, uint32_t* bm_off,
+                       uint8_t* payload);
+// a mask of n elements (one byte each, nonzero = set) as ceil(n / 64) words; bits at or past n are zero
+void launch_bits_pack(hipStream_t s, const uint8_t* mask, uint64_t n, uint64_t* words);
+// BitSetUtil.toLongArray (:67-108) over the bit positions [first, first + n), first + n <= 2^32, of a
+// one-bitmap key-major batch: ceil(n / 64) words (first % 64 == 0; out 8 B aligned; bits at or past n zero) or,
+// with mask, n bytes of 0 / 1 (any first).  Writes every word / byte of the window once and nothing else.
+void launch_bits_expand(hipStream_t s, const uint32_t* key_off, const CDesc* desc, const uint8_t* payload,
+                        uint64_t first, uint64_t n, bool mask, void* out);
+
 // bsibuild.hip: the key-major batch [ebM, bA[0..nbits-1]] of a bit-sliced index from n (column, value)
 // pairs in device memory (RoaringBitmapSliceIndex.setValue, BSI/:299-347) [+ runOptimize].
 // mm: {min, max} of the values, set to {INT_MAX, INT_MIN} by the caller

@@ -151,6 +151,32 @@ __device__ __forceinline__ void w_load_bitmap(const uint8_t* p, WCtr& x) {
     x.w[2 * i + 1] = (uint64_t)v.z | ((uint64_t)v.w << 32);
   }
 }
+// The same from a caller's buffer (bitset.hip): p is only 8 B aligned and only its first `avail` bytes (>= 1)
+// may be read; what lies behind them counts as zero.  A word the end cuts through is put together from its
+// 1..7 bytes, little-endian (BitSetUtil.bitmapOf(ByteBuffer), RB/BitSetUtil.java:238-251).  A whole 16 B
+// aligned block takes w_load_bitmap's path (wave-uniform choice).
+__device__ __forceinline__ void w_load_bitmap_bounded(const uint8_t* p, uint64_t avail, WCtr& x) {
+  if (avail >= 8192 && (reinterpret_cast<uintptr_t>(p) & 15) == 0) {
+    w_load_bitmap(p, x);
+    return;
+  }
+  const uint32_t lim = avail < 8192 ? (uint32_t)avail : 8192u;
+#pragma unroll
+  for (int k = 0; k < 16; k++) {
+    const uint32_t o = 1024u * (k >> 1) + 16u * lane_id() + 8u * (k & 1);
+    x.w[k] = o + 8 <= lim ? *reinterpret_cast<const uint64_t*>(p + o) : 0ull;
+  }
+  if (lim & 7) {  // the one word the end cuts: word lim / 8, register 2 (word / 128) + (word & 1) of lane (word & 127) / 2
+    const uint32_t tw = lim >> 3;
+    uint64_t t = 0;
+    for (uint32_t j = 0; j < (lim & 7); j++) t |= (uint64_t)p[8 * tw + j] << (8 * j);
+    const int tk = (int)(2 * (tw >> 7) + (tw & 1));
+    const bool mine = lane_id() == (int)((tw & 127) >> 1);
+#pragma unroll
+    for (int k = 0; k < 16; k++)
+      if (mine && k == tk) x.w[k] = t;
+  }
+}
 // bits [lo, hi] of register k of the wave layout (WCtr: w[2 i + j] = word 128 i + 2 lane + j)
 __device__ __forceinline__ uint64_t wrange(int k, int lo, int hi) {
   const int w = 128 * (k >> 1) + 2 * lane_id() + (k & 1);

@@ -385,6 +385,124 @@ class Engine:
                                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), ctypes.byref(n_out)))
         return out
 
+    # ---- dense bitsets and masks (bitset.hip): BitSetUtil, RB/BitSetUtil.java ----
+    def _from_bitset(self, what, x, layout, torch_dtypes, numpy_dtypes, run_optimize):
+        """the shared front of from_words / from_mask: a torch tensor on this engine's GPU is read in place
+        (made contiguous, and for packed bytes 8-byte aligned, on the current stream first), anything else
+        is uploaded"""
+        out = ctypes.c_int32()
+        if is_torch(x):
+            import torch
+            if x.device.type != "cuda" or x.device.index != self.device:
+                raise ValueError(f"{what}: the tensor must be on device {self.device}")
+            if x.dtype not in [getattr(torch, d) for d in torch_dtypes]:
+                raise ValueError(f"{what}: a tensor of {' or '.join(torch_dtypes)} is required")
+            t = x.contiguous().reshape(-1)
+            if layout == _lib.RBG_BITS_PACKED and t.numel() and t.data_ptr() % 8:
+                t = t.clone()  # a byte view at an odd address: a fresh allocation is aligned
+            done = self._handshake(x.device)
+            check(lib().rbg_ctx_from_bitset_device(self._ctx, _dptr(t), t.numel() * t.element_size()
+                                                   if layout == _lib.RBG_BITS_PACKED else t.numel(), layout,
+                                                   int(bool(run_optimize)), ctypes.byref(out)))
+            done()
+            return out.value
+        if isinstance(x, (bytes, bytearray, memoryview)):
+            v = np.frombuffer(x, dtype=np.uint8)
+        else:
+            v = np.ascontiguousarray(x)
+        if v.dtype not in [np.dtype(d) for d in numpy_dtypes]:
+            raise ValueError(f"{what}: an array of {' or '.join(numpy_dtypes)} is required")
+        v = v.reshape(-1)
+        n = v.nbytes if layout == _lib.RBG_BITS_PACKED else v.size
+        check(lib().rbg_ctx_from_bitset(self._ctx, ctypes.c_void_p(v.ctypes.data) if n else None, n, layout,
+                                        int(bool(run_optimize)), ctypes.byref(out)))
+        return out.value
+
+    def from_words(self, words, run_optimize=False) -> int:
+        """A resident bitmap from a dense bitset given as packed little-endian 64-bit words, built on the device
+        (rbg_ctx_from_bitset): BitSetUtil.bitmapOf(long[]) (RB/BitSetUtil.java:160-174) and
+        bitmapOf(ByteBuffer) (:185-259), with run_optimize followed by runOptimize() -> batch id of a
+        one-bitmap batch, the same as from_values of the set bit positions.  A numpy uint64 / int64 array, or
+        bytes of any length (a tail of 1..7 bytes is a last word), is uploaded.  A torch int64 / uint8 tensor
+        on this engine's GPU is read in place (rbg_ctx_from_bitset_device) with point_query's stream
+        handshake: the words are not copied (a non-contiguous tensor, or a uint8 view at an address that is
+        not 8-byte aligned, is first made a contiguous aligned one on the current stream), nothing at or past
+        the end is read, and three kernels read them, so they must not change until the call returns.  At
+        most 2^26 words (2^32 bits): more raises IllegalArgumentException before any device work.
+        Synchronous: the container count and the batch totals are read back.  Against torch.nonzero +
+        from_values the call was 2 to 23 times faster at every shape measured, 2^24 to 2^32 bits at densities 2^-10
+        to 1/2; sparser bitsets were not measured."""
+        return self._from_bitset("from_words", words, _lib.RBG_BITS_PACKED, ("int64", "uint8"),
+                                 ("uint64", "int64", "uint8"), run_optimize)
+
+    def from_mask(self, mask, run_optimize=False) -> int:
+        """The same from a mask, one element per bit position, nonzero = set (so 2 and 255 count): a numpy
+        bool / uint8 array, or a torch bool / uint8 tensor on this engine's GPU such as `x > 0`, which one
+        kernel packs into pooled words (a non-contiguous mask is made contiguous on the current stream first).
+        A mask of n elements sets no bit at or above n.  At most 2^32 elements."""
+        return self._from_bitset("from_mask", mask, _lib.RBG_BITS_BYTES, ("bool", "uint8"), ("bool", "uint8"),
+                                 run_optimize)
+
+    def _last(self, batch, ia):
+        """the largest value of a resident bitmap, -1 for an empty one (the existing previousValue query)"""
+        return int(self.point_query("prev", batch, [0xFFFFFFFF], ia)[0])
+
+    def _to_bitset(self, batch, ia, first, n, layout, count, dtype, torch_dtype, numpy_dtype):
+        """the shared back of to_words / to_mask: `count` output elements for the window [first, first + n)"""
+        if dtype is not None and is_torch(dtype):
+            import torch
+            if dtype != getattr(torch, torch_dtype):
+                raise ValueError(f"a torch result is torch.{torch_dtype}")
+            dev = torch.device("cuda", self.device)
+            out = torch.empty(count, dtype=dtype, device=dev)
+            done = self._handshake(dev) if count else None
+            check(lib().rbg_ctx_to_bitset_device(self._ctx, int(batch), int(ia), first, n, layout, _dptr(out)))
+            if done:
+                done()
+            return out
+        if dtype is not None and np.dtype(dtype) != np.dtype(numpy_dtype):
+            raise ValueError(f"a numpy result is {numpy_dtype}")
+        out = np.empty(count, dtype=numpy_dtype)
+        check(lib().rbg_ctx_to_bitset(self._ctx, int(batch), int(ia), first, n, layout,
+                                      ctypes.c_void_p(out.ctypes.data) if count else None))
+        return out
+
+    def to_words(self, batch, ia=0, first_word=0, n_words=None, dtype=None):
+        """Words [first_word, first_word + n_words) of a resident bitmap as a dense bitset of little-endian
+        64-bit words, expanded on the device (rbg_ctx_to_bitset): BitSetUtil.toLongArray
+        (RB/BitSetUtil.java:67-108).  n_words None: toLongArray's own length from the bitmap's last value
+        (:76-79: none for an empty bitmap, last / 64 + 1 words for last >= 64, 2 words for every last in
+        0..63), and IllegalArgumentException("bitmap has negative bits set") for a last value of at least
+        2^31 (:72-75); an explicit window may cover the whole 32-bit universe (2^26 words).  Absent keys and
+        everything past the last value are zero words.  dtype None -> numpy uint64, synchronous; torch.int64
+        -> a tensor on this engine's GPU written on the engine stream with no host synchronisation (the
+        current stream waits for it, as with to_values).  Every word of the window is written once: the
+        output is not zeroed first."""
+        first_word = int(first_word)
+        if n_words is None:
+            last = self._last(batch, ia)
+            if last >= 1 << 31:
+                raise _lib.IllegalArgumentException("bitmap has negative bits set")
+            n_words = max((max(last, 64) // 64 + 1 if last >= 0 else 0) - first_word, 0)
+        n_words = int(n_words)
+        if first_word < 0 or n_words < 0:
+            raise ValueError("to_words: first_word and n_words must not be negative")
+        return self._to_bitset(batch, ia, 64 * first_word, 64 * n_words, _lib.RBG_BITS_PACKED, n_words, dtype,
+                               "int64", "uint64")
+
+    def to_mask(self, batch, ia=0, first=0, n=None, dtype=None):
+        """Bit positions [first, first + n) of a resident bitmap as a mask, one element each (any first; n
+        None: up to the last value, nothing for an empty bitmap): dtype None -> numpy bool, synchronous;
+        torch.bool -> a tensor on this engine's GPU, as to_words gives one.  Against to_values + an indexed
+        store into a zeroed mask the call was 1.8 to 8.6 times faster at every shape measured."""
+        first = int(first)
+        if n is None:
+            n = max(self._last(batch, ia) + 1 - first, 0)
+        n = int(n)
+        if first < 0 or n < 0:
+            raise ValueError("to_mask: first and n must not be negative")
+        return self._to_bitset(batch, ia, first, n, _lib.RBG_BITS_BYTES, n, dtype, "bool", "bool")
+
     def bsi_from_columns(self, columns, values, run_optimize=False):
         """A resident bit-sliced index from (column, value) pairs, built on the device
         (rbg_ctx_bsi_from_columns): setValue(column, value) for every pair, with run_optimize followed by
