@@ -703,5 +703,8 @@ int rbg_ctx_fetch_shard_device_dyn(rbg_ctx* ctx, const void* layout, int rank, i
 /* Dense bitsets and masks to resident bitmaps and back (BitSetUtil, RB/BitSetUtil.java): the entry points of
  * that interchange form, each citing its method, are declared in the file below. */
 #include "roaring_mi355x_bitset.h"
+/* The range-encoded index (RangeBitmap, RB/RangeBitmap.java): map a serialized index, keep it resident, answer
+ * lte / lt / gt / gte / eq / neq / between and their cardinalities, with or without a context bitmap. */
+#include "roaring_mi355x_rangebitmap.h"
 
 #endif /* ROARING_MI355X_H */

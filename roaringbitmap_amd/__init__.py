@@ -11,9 +11,10 @@ from .engine import Engine  # noqa: F401
 from .roaring import (BufferFastAggregation, FastAggregation, ImmutableRoaringBitmap, MutableRoaringBitmap,  # noqa: F401
                       ParallelAggregation, RoaringBitmap, batch_and_cardinality, run_optimize_many)
 from .bitset import BitSetUtil  # noqa: F401
+from .rangebitmap import RangeBitmap  # noqa: F401
 from .bsi import BitSliceIndexBase, ImmutableBitSliceIndex, MutableBitSliceIndex, RoaringBitmapSliceIndex  # noqa: F401
 
 __all__ = ["RoaringBitmap", "ImmutableRoaringBitmap", "MutableRoaringBitmap", "FastAggregation", "BufferFastAggregation", "ParallelAggregation", "RoaringBitmapSliceIndex", "ImmutableBitSliceIndex",
-           "MutableBitSliceIndex", "BitSliceIndexBase", "BitSetUtil", "Engine", "batch_and_cardinality", "run_optimize_many",
+           "MutableBitSliceIndex", "BitSliceIndexBase", "BitSetUtil", "RangeBitmap", "Engine", "batch_and_cardinality", "run_optimize_many",
            "InvalidRoaringFormat",
            "TruncatedInput", "IllegalArgumentException", "NoSuchElementException", "DeviceError", "RoaringError"]

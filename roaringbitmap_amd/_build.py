@@ -31,6 +31,7 @@ SOURCES = [
     "build.hip",
     "expand.hip",
     "bitset.hip",
+    "rangebitmap.hip",
     "bsibuild.hip",
     "bsival.hip",
     "bsiadd.hip",
@@ -42,10 +43,13 @@ SOURCES = [
     "engine_wide.cpp",
     "engine_bsi.cpp",
     "engine_synth.cpp",
+    "engine_rangebitmap.cpp",
     "engine_api.cpp",
     "format.cpp",
+    "rangebitmap_format.cpp",
 ]
-HEADERS = ["device.hpp", "kernels.hpp", "format.hpp", "wave.hpp", "vb.hpp", "bsival.hpp", "engine.hpp", "build.hpp"]
+HEADERS = ["device.hpp", "kernels.hpp", "format.hpp", "wave.hpp", "vb.hpp", "bsival.hpp", "engine.hpp", "build.hpp",
+           "rangebitmap_format.hpp"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-Wall", "-Wno-unused-function",
          "-Wno-unused-result"]
 
@@ -58,7 +62,8 @@ def build(verbose=False, jobs=8):
     os.makedirs(OBJDIR, exist_ok=True)
     inc = os.path.join(os.path.dirname(HERE), "include")
     dep_time = max([_mtime(os.path.join(CSRC, h)) for h in HEADERS] + [_mtime(__file__)]
-                   + [_mtime(os.path.join(inc, h)) for h in ("roaring_mi355x.h", "roaring_mi355x_bitset.h")])
+                   + [_mtime(os.path.join(inc, h)) for h in ("roaring_mi355x.h", "roaring_mi355x_bitset.h",
+                                                             "roaring_mi355x_rangebitmap.h")])
     procs, objs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

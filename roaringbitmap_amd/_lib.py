@@ -173,6 +173,20 @@ BITSET_SIGNATURES = {
     "rbg_bitset_expand": (ci, [u8p, sz, buf]),
 }
 
+# Every entry point of include/roaring_mi355x_rangebitmap.h (RangeBitmap: the range-encoded index), which
+# roaring_mi355x.h includes, in that file's order.
+RANGEBITMAP_OP = {"lte": 0, "lt": 1, "gt": 2, "gte": 3, "eq": 4, "neq": 5, "between": 6}  # RBG_RB_*
+RANGEBITMAP_SIGNATURES = {
+    "rbg_rangebitmap_validate": (ci, [u8p, sz, u64p]),
+    "rbg_ctx_rangebitmap_load": (ci, [vp, u8p, sz, i32p]),
+    "rbg_ctx_rangebitmap_release": (ci, [vp, i32]),
+    "rbg_ctx_rangebitmap_info": (ci, [vp, i32, u64p]),
+    "rbg_ctx_rangebitmap_query": (ci, [vp, i32, ci, u64, u64, i32, sz, i32p]),
+    "rbg_ctx_rangebitmap_count": (ci, [vp, i32, ci, u64, u64, i32, sz, i64p]),
+    "rbg_rangebitmap_query": (ci, [u8p, sz, ci, u64, u64, u8p, sz, buf]),
+    "rbg_rangebitmap_count": (ci, [u8p, sz, ci, u64, u64, u8p, sz, i64p]),
+}
+
 _lib = None
 
 
@@ -185,7 +199,7 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the engine has no CPU fallback)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**SIGNATURES, **BITSET_SIGNATURES}.items():
+        for name, (restype, argtypes) in {**SIGNATURES, **BITSET_SIGNATURES, **RANGEBITMAP_SIGNATURES}.items():
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
         _lib = L

@@ -386,14 +386,10 @@ int ctx_serialize(Ctx* c) {
   return RBG_OK;
 }
 
-
 // Bitmap i of a batch as the operand of a per-key op: what the kernels see of it (BmView: key CSR, container
 // table, payload, container count) and the batch (statistics read).  The range must be contiguous: a
 // one-bitmap key-major batch.
-struct Operand : BmView {
-  Batch* b;
-};
-static int resolve(Ctx* c, int32_t id, size_t i, Operand* op) {
+int resolve(Ctx* c, int32_t id, size_t i, Operand* op) {
   Batch* b;
   CHK(get_batch(c, id, &b));
   if (i >= b->n_bm) {

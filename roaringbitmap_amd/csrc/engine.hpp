@@ -4,6 +4,7 @@
 //   engine_load.cpp   upload of serialized bitmaps and their decode on the device
 //   engine_wide.cpp   the aggregations (FastAggregation's dispatch, the horizontal and priority-queue forms)
 //   engine_bsi.cpp    every bit-sliced-index pipeline and its entry points
+//   engine_rangebitmap.cpp  the range-encoded index: load, queries, counts
 //   engine_synth.cpp  the bench workload synthesizers
 //   engine_api.cpp    the exported C ABI
 // What is declared here is defined once; what no other unit calls stays static in its own.
@@ -121,6 +122,15 @@ struct Batch {
   std::vector<uint32_t> h_pos, h_pos_off;
 };
 
+// A resident range-encoded index (engine_rangebitmap.cpp; RB/RangeBitmap.java): not a batch, because its slices
+// are not bitmaps of the portable format (a bitmap container of any cardinality, rangebitmap_format.hpp)
+struct RangeIndex {
+  uint32_t nslices = 0, n_blocks = 0;
+  uint64_t max_rid = 0, mask = 0;
+  uint64_t payload_bytes = 0;  // container payload bytes of the stream
+  DevBuf dir, masks, arena;    // n_blocks x nslices CDesc, n_blocks u64, the containers' slots
+};
+
 struct DecBufs {  // scratch of the device decode (decode.hip), reused across loads
   DevBuf meta, head, nctr, base, nch, chbase, chmap, flag, err, card, cons, part, q, qkey, sort, skey, iota, perm,
       size, cpart;
@@ -134,6 +144,7 @@ struct Ctx {
   DevBuf pc_cnt, pc_part, pc_items, pc_large;  // batched andCardinality scratch
   hipStream_t stream = nullptr;
   std::vector<std::unique_ptr<Batch>> batches;
+  std::vector<std::unique_ptr<RangeIndex>> range_indexes;  // by index id; a released one is null
   uint64_t* zlb = nullptr;    // look-back state the next plan kernel zeroes (null: none)
   uint64_t* ztile = nullptr;
   DevBuf bsi_defer, bsi_cnts, bsi_kin, bsi_table;  // scratch of the register-resident BSI kernels
@@ -247,6 +258,11 @@ int ctx_batch_fetch_range(Ctx* c, int32_t batch, size_t i0, size_t i1, rbg_buffe
 int ctx_fetch_shard_device(Ctx* c, int64_t total_containers, int has_run, int64_t payload_base, void* desc_dst,
                            void* offsets_dst, void* runflag_dst, void* payload_dst);
 // engine.cpp, the ops.
+// One operand of a per-key op: bitmap i of a single-bitmap key-major slot-aligned batch, and that batch
+struct Operand : BmView {
+  Batch* b;
+};
+int resolve(Ctx* c, int32_t id, size_t i, Operand* op);
 int ctx_empty_bitmap(Ctx* c, int32_t* out_id);
 int ctx_point(Ctx* c, int op, int32_t batch, size_t i, const uint32_t* q_dev, size_t n, long long* out_dev);
 int ctx_point_host(Ctx* c, int op, int32_t batch, size_t i, const uint32_t* q, size_t n, int64_t* out);
@@ -284,6 +300,14 @@ int ctx_load_separate(Ctx* c, const uint8_t* const* bufs, const size_t* lens, si
 bool wide_reads_packed(int op, size_t n);
 int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const int32_t* ids, bool card_only,
              int* host_card_out, bool* host_card_valid, int32_t start_override = -1);
+// engine_rangebitmap.cpp: the range-encoded index (RB/RangeBitmap.java).  ctx_batch < 0: no context.
+int check_rb_query(int op, bool has_ctx, bool count);
+int ctx_rb_load(Ctx* c, const uint8_t* buf, size_t len, int32_t* out_index);
+int ctx_rb_release(Ctx* c, int32_t index);
+int ctx_rb_info(Ctx* c, int32_t index, uint64_t* info);
+int ctx_rb_query(Ctx* c, int32_t index, int op, uint64_t a, uint64_t b, int32_t ctx_batch, size_t ctx_i,
+                 int32_t* out_batch);
+int ctx_rb_count(Ctx* c, int32_t index, int op, uint64_t a, uint64_t b, int32_t ctx_batch, size_t ctx_i, int64_t* out);
 // engine_synth.cpp.
 int synth_c2(Ctx* c, int kind, uint64_t seed, int32_t* out_id);
 int synth_c3(Ctx* c, int kind, uint64_t seed, size_t n, int key_lo, int key_hi, int32_t* out_id);

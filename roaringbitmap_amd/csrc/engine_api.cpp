@@ -1,6 +1,6 @@
 // The exported C ABI of include/roaring_mi355x.h (engine.hpp: the host units), but the BSI entry points
-// (engine_bsi.cpp), rbg_synth_key_bytes (engine_synth.cpp) and the accessors of the core's process-wide state
-// (engine.cpp): argument checks, the one-shot fronts and the session calls over the units' ctx_* functions.
+// (engine_bsi.cpp), those of the range-encoded index (engine_rangebitmap.cpp), rbg_synth_key_bytes
+// (engine_synth.cpp) and the accessors of the core's process-wide state (engine.cpp): argument checks, the one-shot fronts and the session calls over the units' ctx_* functions.
 #include <algorithm>
 
 #include "engine.hpp"

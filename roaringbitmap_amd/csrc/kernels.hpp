@@ -531,6 +531,35 @@ void launch_bits_pack(hipStream_t s, const uint8_t* mask, uint64_t n, uint64_t* 
 void launch_bits_expand(hipStream_t s, const uint32_t* key_off, const CDesc* desc, const uint8_t* payload,
                         uint64_t first, uint64_t n, bool mask, void* out);
 
+// rangebitmap.hip: one query of a resident range-encoded index (RB/RangeBitmap.java), a wave per block of
+// 65,536 rows.  The wave replays the block's part of SingleEvaluation / DoubleEvaluation over its registers,
+// ANDs the context's container of that key in, and either stores the block's 8 KiB of bits at out + 8192 k
+// (zeros for a block the context has no key for: the whole workspace is written) or adds its cardinality to
+// *count.
+enum RbMode : int {
+  RBM_LTE = 0,      // evaluateHorizontalSliceRange (:671-734)
+  RBM_GT = 1,       // the same, flipped over the block's rows (:562-565)
+  RBM_EQ = 2,       // evaluateHorizontalSlicePoint (:736-770)
+  RBM_NEQ = 3,      // the same, flipped (:438-441)
+  RBM_BETWEEN = 4,  // DoubleEvaluation.evaluateHorizontalSlice (:1016-1061): t0 < value <= t1
+};
+struct RbArgs {
+  const CDesc* dir;       // n_blocks x nslices slots of the arena; kind kAbsent where the block's mask has no bit
+  const uint64_t* masks;  // the blocks' container masks
+  const uint8_t* arena;
+  uint32_t n_blocks, nslices;
+  uint64_t max_rid, mask;
+  uint64_t t0, t1;
+  BmView ctx;      // the context bitmap (has_ctx)
+  int has_ctx;
+  int ctx_minus;   // count only, RBM_LTE with a context: |context \ bits| per visited key (countRange, :659-661)
+  int ctx_first;   // count only, RBM_BETWEEN with a context: every key from the context's first to its last is
+                   // intersected with the context's FIRST container (count, :984-1012, never advances contextPos)
+  uint8_t* out;    // 8192 n_blocks bytes, 16 B aligned; null: count
+  unsigned long long* count;  // zeroed by the caller
+};
+void launch_rb_query(hipStream_t s, int mode, const RbArgs& a);
+
 // bsibuild.hip: the key-major batch [ebM, bA[0..nbits-1]] of a bit-sliced index from n (column, value)
 // pairs in device memory (RoaringBitmapSliceIndex.setValue, BSI/:299-347) [+ runOptimize].
 // mm: {min, max} of the values, set to {INT_MAX, INT_MIN} by the caller

@@ -647,6 +647,42 @@ class Engine:
                                              ctypes.byref(n_out)))
         return cols, vals
 
+    # ---- the range-encoded index (RangeBitmap, rbg_ctx_rangebitmap_*) -----------
+    def rangebitmap_load(self, index) -> int:
+        """RangeBitmap.map of a serialized index (bytes, or a RangeBitmap), kept resident -> index handle (not
+        a batch id)."""
+        b = index.serialize() if hasattr(index, "serialize") else bytes(index)
+        out = ctypes.c_int32()
+        check(lib().rbg_ctx_rangebitmap_load(self._ctx, b, len(b), ctypes.byref(out)))
+        return out.value
+
+    def rangebitmap_release(self, index):
+        check(lib().rbg_ctx_rangebitmap_release(self._ctx, int(index)))
+
+    def rangebitmap_info(self, index) -> dict:
+        s = (ctypes.c_uint64 * 6)()
+        check(lib().rbg_ctx_rangebitmap_info(self._ctx, int(index), s))
+        return dict(zip(["slices", "blocks", "rows", "mask", "payload_bytes"], [int(x) for x in s]))
+
+    def rangebitmap_query(self, index, op, a, b=0, context=None, context_i=0) -> int:
+        """lte / lt / gt / gte / eq / neq (a) or between (a, b) of a resident index, optionally intersected
+        with bitmap context_i of the batch `context` -> a new one-bitmap batch, as pairwise's operands are."""
+        out = ctypes.c_int32()
+        check(lib().rbg_ctx_rangebitmap_query(self._ctx, int(index), _lib.RANGEBITMAP_OP.get(op, op),
+                                              int(a) & 0xFFFFFFFFFFFFFFFF, int(b) & 0xFFFFFFFFFFFFFFFF,
+                                              -1 if context is None else int(context), int(context_i),
+                                              ctypes.byref(out)))
+        return out.value
+
+    def rangebitmap_count(self, index, op, a, b=0, context=None, context_i=0) -> int:
+        """the *Cardinality form of rangebitmap_query, reduced on the device (synchronous)"""
+        out = ctypes.c_int64()
+        check(lib().rbg_ctx_rangebitmap_count(self._ctx, int(index), _lib.RANGEBITMAP_OP.get(op, op),
+                                              int(a) & 0xFFFFFFFFFFFFFFFF, int(b) & 0xFFFFFFFFFFFFFFFF,
+                                              -1 if context is None else int(context), int(context_i),
+                                              ctypes.byref(out)))
+        return out.value
+
     def batch_counts(self, batch) -> np.ndarray:
         """containers per input bitmap of a batch"""
         n = self.batch_stats(batch)["bitmaps"]
