@@ -706,5 +706,8 @@ int rbg_ctx_fetch_shard_device_dyn(rbg_ctx* ctx, const void* layout, int rank, i
 /* The range-encoded index (RangeBitmap, RB/RangeBitmap.java): map a serialized index, keep it resident, answer
  * lte / lt / gt / gte / eq / neq / between and their cardinalities, with or without a context bitmap. */
 #include "roaring_mi355x_rangebitmap.h"
+/* The same index built on the GPU from a value tensor (RangeBitmap.Appender), and a resident index written
+ * back out as the reference's stream. */
+#include "roaring_mi355x_rangebitmap_build.h"
 
 #endif /* ROARING_MI355X_H */

@@ -32,6 +32,7 @@ SOURCES = [
     "expand.hip",
     "bitset.hip",
     "rangebitmap.hip",
+    "rangebitmap_build.hip",
     "bsibuild.hip",
     "bsival.hip",
     "bsiadd.hip",
@@ -63,7 +64,8 @@ def build(verbose=False, jobs=8):
     inc = os.path.join(os.path.dirname(HERE), "include")
     dep_time = max([_mtime(os.path.join(CSRC, h)) for h in HEADERS] + [_mtime(__file__)]
                    + [_mtime(os.path.join(inc, h)) for h in ("roaring_mi355x.h", "roaring_mi355x_bitset.h",
-                                                             "roaring_mi355x_rangebitmap.h")])
+                                                             "roaring_mi355x_rangebitmap.h",
+                                                             "roaring_mi355x_rangebitmap_build.h")])
     procs, objs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

@@ -187,6 +187,16 @@ RANGEBITMAP_SIGNATURES = {
     "rbg_rangebitmap_count": (ci, [u8p, sz, ci, u64, u64, u8p, sz, i64p]),
 }
 
+# Every entry point of include/roaring_mi355x_rangebitmap_build.h (RangeBitmap.Appender on the device, and a
+# resident index back to the reference's stream), which roaring_mi355x.h includes, in that file's order.
+RANGEBITMAP_BUILD_SIGNATURES = {
+    "rbg_ctx_rangebitmap_build": (ci, [vp, vp, u64, u64, ci, i32p]),
+    "rbg_ctx_rangebitmap_build_device": (ci, [vp, vp, u64, u64, ci, i32p]),
+    "rbg_ctx_rangebitmap_serialize": (ci, [vp, i32, buf]),
+    "rbg_rangebitmap_build": (ci, [vp, u64, u64, ci, buf]),
+    "rbg_rangebitmap_reserialize": (ci, [u8p, sz, buf]),
+}
+
 _lib = None
 
 
@@ -199,7 +209,8 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the engine has no CPU fallback)")
         L = ctypes.CDLL(LIB_PATH)
-        for name, (restype, argtypes) in {**SIGNATURES, **BITSET_SIGNATURES, **RANGEBITMAP_SIGNATURES}.items():
+        for name, (restype, argtypes) in {**SIGNATURES, **BITSET_SIGNATURES, **RANGEBITMAP_SIGNATURES,
+                                          **RANGEBITMAP_BUILD_SIGNATURES}.items():
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
         _lib = L

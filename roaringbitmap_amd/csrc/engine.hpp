@@ -4,7 +4,7 @@
 //   engine_load.cpp   upload of serialized bitmaps and their decode on the device
 //   engine_wide.cpp   the aggregations (FastAggregation's dispatch, the horizontal and priority-queue forms)
 //   engine_bsi.cpp    every bit-sliced-index pipeline and its entry points
-//   engine_rangebitmap.cpp  the range-encoded index: load, queries, counts
+//   engine_rangebitmap.cpp  the range-encoded index: load, build from values, serialize, queries, counts
 //   engine_synth.cpp  the bench workload synthesizers
 //   engine_api.cpp    the exported C ABI
 // What is declared here is defined once; what no other unit calls stays static in its own.
@@ -128,6 +128,7 @@ struct RangeIndex {
   uint32_t nslices = 0, n_blocks = 0;
   uint64_t max_rid = 0, mask = 0;
   uint64_t payload_bytes = 0;  // container payload bytes of the stream
+  uint64_t arena_bytes = 0;    // the slots' bytes (the arena carries kSlack behind them)
   DevBuf dir, masks, arena;    // n_blocks x nslices CDesc, n_blocks u64, the containers' slots
 };
 
@@ -163,6 +164,8 @@ struct Ctx {
   // a BSI batch from (column, value) pairs (bsibuild.hip): the present keys and their CSR, the plan's cell
   // table, the cells' size words (scanned in place) and scan scratch, the per-input totals
   DevBuf bsib_pkeys, bsib_pkoff, bsib_info, bsib_size, bsib_part, bsib_per;
+  DevBuf rbb_info, rbb_size, rbb_part;  // a range-encoded index from values (rangebitmap_build.hip): the plan's cell
+                                        // table, the cells' slot sizes (scanned in place), scan scratch
   DevBuf bsia_run;  // the sum of two indexes (bsiadd.hip): per present key, ebM' is a full run container
   // parallelTransposeWithCount (bsitr.hip): the candidate input keys and their CSR, the result-key flags, per
   // result key its distinct values and whether it is full
@@ -303,6 +306,11 @@ int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const int32_t* 
 // engine_rangebitmap.cpp: the range-encoded index (RB/RangeBitmap.java).  ctx_batch < 0: no context.
 int check_rb_query(int op, bool has_ctx, bool count);
 int ctx_rb_load(Ctx* c, const uint8_t* buf, size_t len, int32_t* out_index);
+int check_rb_build(const void* values, uint64_t n, const void* out);
+int ctx_rb_build(Ctx* c, const uint64_t* dev_values, uint64_t n, uint64_t max_value, bool max_from_data, int32_t* index);
+int ctx_rb_build_host(Ctx* c, const uint64_t* values, uint64_t n, uint64_t max_value, bool max_from_data,
+                      int32_t* index);
+int ctx_rb_serialize(Ctx* c, int32_t index, rbg_buffer* out);
 int ctx_rb_release(Ctx* c, int32_t index);
 int ctx_rb_info(Ctx* c, int32_t index, uint64_t* info);
 int ctx_rb_query(Ctx* c, int32_t index, int op, uint64_t a, uint64_t b, int32_t ctx_batch, size_t ctx_i,

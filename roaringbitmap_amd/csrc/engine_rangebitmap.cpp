@@ -1,7 +1,9 @@
 // The range-encoded index (RB/RangeBitmap.java) on the host side of the engine: the load of a serialized
-// index (rangebitmap_format.cpp walks it once), the dispatch of a query to a shortcut or to k_rb_query
+// index (rangebitmap_format.cpp walks it once), the build of one from a value tensor (rangebitmap_build.hip), its
+// way back to a stream (rangebitmap_format.cpp: rb_emit), the dispatch of a query to a shortcut or to k_rb_query
 // (rangebitmap.hip), the result batch, and the entry points of include/roaring_mi355x_rangebitmap.h.
 #include <algorithm>
+#include <cstdlib>
 
 #include "engine.hpp"
 #include "rangebitmap_format.hpp"
@@ -39,6 +41,17 @@ static int find_index(Ctx* c, int32_t index, RangeIndex** out) {
   return RBG_OK;
 }
 
+// a new index under the lowest free handle
+static int32_t register_index(Ctx* c, std::unique_ptr<RangeIndex> R) {
+  size_t id = 0;
+  while (id < c->range_indexes.size() && c->range_indexes[id]) id++;
+  if (id == c->range_indexes.size()) c->range_indexes.emplace_back();
+  c->range_indexes[id] = std::move(R);
+  return (int32_t)id;
+}
+
+static int nlz(uint64_t x) { return x ? __builtin_clzll(x) : 64; }
+
 // RangeBitmap.map (:65-85): the directory and the re-laid containers go up in three copies
 int ctx_rb_load(Ctx* c, const uint8_t* buf, size_t len, int32_t* out_index) {
   RbIndex idx;
@@ -49,6 +62,7 @@ int ctx_rb_load(Ctx* c, const uint8_t* buf, size_t len, int32_t* out_index) {
   R->max_rid = idx.max_rid;
   R->mask = idx.mask;
   R->payload_bytes = idx.payload_bytes;
+  R->arena_bytes = idx.arena_bytes;
   if (idx.n_blocks) {
     std::vector<CDesc> dir(idx.dir.size());
     for (size_t j = 0; j < dir.size(); j++) {
@@ -64,12 +78,163 @@ int ctx_rb_load(Ctx* c, const uint8_t* buf, size_t len, int32_t* out_index) {
     CHK(upload_words(c, R->masks.p, idx.masks.data(), 2 * idx.masks.size()));
     CHK(upload_words(c, R->arena.p, arena.data(), idx.arena_bytes / 4));
   }
-  size_t id = 0;
-  while (id < c->range_indexes.size() && c->range_indexes[id]) id++;
-  if (id == c->range_indexes.size()) c->range_indexes.emplace_back();
-  c->range_indexes[id] = std::move(R);
-  *out_index = (int32_t)id;
+  *out_index = register_index(c, std::move(R));
   return RBG_OK;
+}
+
+// Workspace bytes of one pass of the build (rangebitmap_build.hip).  RBG_RB_BUILD_WS=<bytes> overrides the
+// default, read at every call (tests force several passes at small shapes); a pass always holds at least one
+// whole block's cells.
+constexpr size_t kRbbBudget = 1ull << 30;  // a released workspace of this size still goes to the pool
+static size_t rbb_budget() {
+  const char* e = std::getenv("RBG_RB_BUILD_WS");
+  const unsigned long long v = e ? std::strtoull(e, nullptr, 10) : 0;
+  return (size_t)std::min<unsigned long long>(v ? v : kRbbBudget, 4ull << 30);
+}
+
+constexpr uint64_t kRbMaxRows = 65535ull * 65536;  // the header's u16 maxKey states at most 65,535 blocks
+
+// the refusals of a build, decided from the arguments alone
+int check_rb_build(const void* values, uint64_t n, const void* out) {
+  if (!out) {
+    set_err("range bitmap build: no output");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (n && !values) {
+    set_err("range bitmap build: no input");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  if (n > kRbMaxRows) {
+    set_err("range bitmap build: more than 65,535 blocks of 65,536 rows");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  return RBG_OK;
+}
+
+// RangeBitmap.appender(max_value) (:52-56), add (:1511-1533) for every one of the n values in device memory, in
+// order, and build (:1415-1438), as the resident index that ctx_rb_load of the Appender's stream makes: the same
+// directory, masks and slots, at other offsets only (rangebitmap_build.hip).  max_from_data: max_value is the
+// largest value given.  A value outside the mask refuses the whole call (the reference throws at that row, with
+// the rows before it added).  Two read-backs: the largest value, then the arena's size with the payload bytes.
+// One pass: transpose, plan, scan, write from the same workspace.  Several: every pass is transposed and
+// planned (sizes alone), the scan places every container, and each pass is transposed again before it is
+// written -- the arena is allocated once at its exact size, as the BSI builders' payload is.
+// The values are read by every transpose: they must not change until the call returns.
+int ctx_rb_build(Ctx* c, const uint64_t* dev_values, uint64_t n, uint64_t max_value, bool max_from_data,
+                 int32_t* out_index) {
+  CHK(check_rb_build(dev_values, n, out_index));
+  hipStream_t s = c->stream;
+  CHK(c->scalar.ensure(64));
+  unsigned long long* sc = c->scalar.as<unsigned long long>();  // [0] largest value, [1] payload bytes, [2] arena
+  unsigned long long h[3] = {0, 0, 0};
+  if (n) {
+    HIPCHK(hipMemsetAsync(sc, 0, 64, s));
+    launch_rbb_max(s, dev_values, n, sc);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h, sc, 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  if (max_from_data) max_value = h[0];
+  const int nslices = 64 - nlz(max_value | 1);  // rangeMask / bytesPerMask of maxValue | 1 (:1622-1630)
+  const uint64_t mask = ~0ull >> (64 - nslices);
+  if (h[0] & ~mask) {
+    set_err(std::to_string(h[0]) + " too large");  // add's message (:1513-1515), for the largest such value
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  auto R = std::make_unique<RangeIndex>();
+  R->nslices = (uint32_t)nslices;
+  R->n_blocks = (uint32_t)((n + 0xFFFF) >> 16);
+  R->max_rid = n;
+  R->mask = mask;
+  const size_t K = R->n_blocks, cells = K * (size_t)nslices;
+  if (K) {
+    CHK(c->rbb_info.ensure(kRbbInfoBytes * cells + 16));
+    CHK(c->rbb_size.ensure(8 * (cells + 1)));
+    CHK(c->rbb_part.ensure(8 * (scan_parts(cells) + 1)));
+    uint64_t* size = c->rbb_size.as<uint64_t>();
+    const size_t block_bytes = 8192 * (size_t)nslices;
+    const size_t P = std::min(K, std::max<size_t>(1, rbb_budget() / block_bytes));  // blocks per pass
+    DevBuf ws;  // back to the pool after the last write (freed on an error)
+    CHK(pool_take(c, ws, block_bytes * P));
+    auto transpose = [&](size_t k_lo, size_t k_hi) {
+      launch_rbb_transpose(s, dev_values, n, mask, (uint32_t)k_lo, (uint32_t)k_hi, nslices, ws.as<uint8_t>());
+    };
+    for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+      const size_t k_hi = std::min(K, k_lo + P);
+      transpose(k_lo, k_hi);
+      launch_rbb_plan(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, nslices, c->rbb_info.p, size, sc + 1);
+    }
+    launch_exclusive_scan(s, size, size, cells, c->rbb_part.as<uint64_t>(), reinterpret_cast<uint64_t*>(sc + 2));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(h + 1, sc + 1, 16, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    dbg(s, "rangebitmap_build: transpose + plan");
+    R->payload_bytes = h[1];
+    R->arena_bytes = h[2];
+    CHK(pool_take(c, R->dir, sizeof(CDesc) * cells + 16));
+    CHK(pool_take(c, R->masks, 8 * K + 16));
+    CHK(pool_take(c, R->arena, R->arena_bytes + kSlack));
+    for (size_t k_lo = 0; k_lo < K; k_lo += P) {
+      const size_t k_hi = std::min(K, k_lo + P);
+      if (P < K) transpose(k_lo, k_hi);  // several passes: the workspace held another pass since the plan
+      launch_rbb_write(s, ws.as<uint8_t>(), (uint32_t)k_lo, (uint32_t)k_hi, nslices, c->rbb_info.p, size,
+                       R->dir.as<CDesc>(), R->masks.as<uint64_t>(), R->arena.as<uint8_t>());
+    }
+    HIPCHK(hipGetLastError());
+    pool_put(c, ws);  // whatever takes it next is enqueued on this stream, after the write kernels
+    HIPCHK(hipStreamSynchronize(s));
+    dbg(s, "rangebitmap_build: write");
+  }
+  *out_index = register_index(c, std::move(R));
+  return RBG_OK;
+}
+
+// the same from host memory: the values go to the device through the context's pinned buffer
+int ctx_rb_build_host(Ctx* c, const uint64_t* values, uint64_t n, uint64_t max_value, bool max_from_data,
+                      int32_t* out_index) {
+  CHK(check_rb_build(values, n, out_index));
+  DevBuf in;
+  CHK(pool_take(c, in, 8 * n + 16));
+  CHK(upload_words(c, in.p, values, 2 * n));
+  const int st = ctx_rb_build(c, in.as<uint64_t>(), n, max_value, max_from_data, out_index);
+  pool_put(c, in);
+  return st;
+}
+
+// Appender.serialize (:1483-1504) of a resident index, loaded or built: the directory, the masks and the arena
+// come to the host and rangebitmap_format.cpp's rb_emit writes the stream
+int ctx_rb_serialize(Ctx* c, int32_t index, rbg_buffer* out) {
+  RangeIndex* R;
+  CHK(find_index(c, index, &R));
+  hipStream_t s = c->stream;
+  RbIndex idx;
+  idx.nslices = R->nslices;
+  idx.n_blocks = R->n_blocks;
+  idx.max_rid = R->max_rid;
+  idx.mask = R->mask;
+  idx.masks.resize(R->n_blocks);
+  idx.dir.resize((size_t)R->n_blocks * R->nslices);
+  std::vector<CDesc> dir(idx.dir.size());
+  std::vector<uint8_t> arena(R->arena_bytes);
+  if (R->n_blocks) {
+    HIPCHK(hipMemcpyAsync(dir.data(), R->dir.p, sizeof(CDesc) * dir.size(), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipMemcpyAsync(idx.masks.data(), R->masks.p, 8 * idx.masks.size(), hipMemcpyDeviceToHost, s));
+    if (R->arena_bytes) HIPCHK(hipMemcpyAsync(arena.data(), R->arena.p, R->arena_bytes, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+  }
+  for (size_t j = 0; j < dir.size(); j++) {
+    idx.dir[j].kind = dir[j].kind;
+    idx.dir[j].card = dir[j].card;
+    idx.dir[j].slot = dir[j].slot;
+  }
+  std::vector<uint8_t> bytes;
+  std::string err;
+  const int st = rb_emit(idx, arena.data(), arena.size(), &bytes, &err);
+  if (st) {
+    set_err(err);
+    return st;
+  }
+  return emit_host(bytes, out);
 }
 
 int ctx_rb_release(Ctx* c, int32_t index) {
@@ -97,7 +262,6 @@ struct RbPlan {
   int mode;  // RbMode
   uint64_t t0, t1;
 };
-static int nlz(uint64_t x) { return x ? __builtin_clzll(x) : 64; }
 static RbPlan rb_plan(uint64_t mask, int op, uint64_t a, uint64_t b) {
   auto above = [&](uint64_t t) { return nlz(t) < nlz(mask); };  // Long.numberOfLeadingZeros(t) < ...(mask)
   if (op == RBG_RB_BETWEEN) {
@@ -259,6 +423,56 @@ int rbg_ctx_rangebitmap_load(rbg_ctx* ctx, const uint8_t* buf, size_t len, int32
   Ctx* c;
   CHK(session(ctx, &c));
   return ctx_rb_load(c, buf, len, index);
+}
+
+int rbg_ctx_rangebitmap_build(rbg_ctx* ctx, const uint64_t* values, uint64_t n, uint64_t max_value, int max_from_data,
+                              int32_t* index) {
+  CHK(check_rb_build(values, n, index));  // the refusals need no device
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_rb_build_host(c, values, n, max_value, max_from_data != 0, index);
+}
+
+int rbg_ctx_rangebitmap_build_device(rbg_ctx* ctx, const uint64_t* values_dev, uint64_t n, uint64_t max_value,
+                                     int max_from_data, int32_t* index) {
+  CHK(check_rb_build(values_dev, n, index));
+  if (reinterpret_cast<uintptr_t>(values_dev) & 7) {
+    set_err("range bitmap build: the values must be 8-byte aligned");
+    return RBG_ERR_ILLEGAL_ARGUMENT;
+  }
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_rb_build(c, values_dev, n, max_value, max_from_data != 0, index);
+}
+
+int rbg_ctx_rangebitmap_serialize(rbg_ctx* ctx, int32_t index, rbg_buffer* out) {
+  if (!out) return RBG_ERR_ILLEGAL_ARGUMENT;
+  Ctx* c;
+  CHK(session(ctx, &c));
+  return ctx_rb_serialize(c, index, out);
+}
+
+int rbg_rangebitmap_build(const uint64_t* values, uint64_t n, uint64_t max_value, int max_from_data, rbg_buffer* out) {
+  CHK(check_rb_build(values, n, out));
+  RbOneShot os;
+  CHK(os.open());
+  CHK(ctx_rb_build_host(os.c, values, n, max_value, max_from_data != 0, &os.index));
+  return ctx_rb_serialize(os.c, os.index, out);
+}
+
+int rbg_rangebitmap_reserialize(const uint8_t* buf, size_t len, rbg_buffer* out) {
+  if (!out || (!buf && len)) return RBG_ERR_ILLEGAL_ARGUMENT;
+  RbIndex idx;
+  CHK(parse_index(buf, len, &idx));
+  std::vector<uint8_t> arena(idx.arena_bytes), bytes;
+  rb_relay(buf, idx, arena.data());
+  std::string err;
+  const int st = rb_emit(idx, arena.data(), arena.size(), &bytes, &err);
+  if (st) {
+    set_err(err);
+    return st;
+  }
+  return emit_host(bytes, out);
 }
 
 int rbg_ctx_rangebitmap_release(rbg_ctx* ctx, int32_t index) {

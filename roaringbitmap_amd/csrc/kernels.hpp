@@ -560,6 +560,25 @@ struct RbArgs {
 };
 void launch_rb_query(hipStream_t s, int mode, const RbArgs& a);
 
+// rangebitmap_build.hip: a resident range-encoded index from n u64 values in device memory, row r = values[r]
+// (RangeBitmap.Appender.add / append, :1511-1588).  Block k is rows [65536 k, 65536 (k + 1)); cell (k, i) holds
+// the block's rows whose value has bit i clear.
+// *max (zeroed by the caller) = the largest value, unsigned
+void launch_rbb_max(hipStream_t s, const uint64_t* v, uint64_t n, unsigned long long* max);
+// One pass over the blocks [k_lo, k_hi).  ws: (k_hi - k_lo) x nslices bitmaps of 8 KiB, every word of which the
+// transpose writes (zeros at and past row n), so the caller zeroes nothing.
+void launch_rbb_transpose(hipStream_t s, const uint64_t* v, uint64_t n, uint64_t mask, uint32_t k_lo, uint32_t k_hi,
+                          int nslices, uint8_t* ws);
+constexpr size_t kRbbInfoBytes = 8;  // per (block, slice) cell: the plan's (card, nruns, kind); card 0: no container
+// info / size: n_blocks x nslices cells (the pass fills its own; size = slot bytes, 0 for an empty cell);
+// *payload (zeroed by the caller) += the stream's payload bytes of the pass (a run: 4 per run)
+void launch_rbb_plan(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t k_hi, int nslices, void* info,
+                     uint64_t* size, unsigned long long* payload);
+// off: the exclusive scan of size[] over all cells.  Writes the pass's slots and directory entries (an empty
+// cell: kind kAbsent) and the blocks' container masks.
+void launch_rbb_write(hipStream_t s, const uint8_t* ws, uint32_t k_lo, uint32_t k_hi, int nslices, const void* info,
+                      const uint64_t* off, CDesc* dir, uint64_t* masks, uint8_t* arena);
+
 // bsibuild.hip: the key-major batch [ebM, bA[0..nbits-1]] of a bit-sliced index from n (column, value)
 // pairs in device memory (RoaringBitmapSliceIndex.setValue, BSI/:299-347) [+ runOptimize].
 // mm: {min, max} of the values, set to {INT_MAX, INT_MIN} by the caller

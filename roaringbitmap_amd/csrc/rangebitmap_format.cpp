@@ -112,4 +112,61 @@ void rb_relay(const uint8_t* p, const RbIndex& idx, uint8_t* arena) {
   }
 }
 
+int rb_emit(const RbIndex& idx, const uint8_t* arena, uint64_t arena_bytes, std::vector<uint8_t>* out, std::string* err) {
+  auto invalid = [&](const char* what) {
+    if (err) *err = std::string("range bitmap directory: ") + what;
+    return RBG_ERR_INVALID_FORMAT;
+  };
+  out->clear();
+  if (idx.nslices < 1 || idx.nslices > 64 || idx.n_blocks > 0xFFFF || idx.max_rid > 0xFFFFFFFFull ||
+      (idx.max_rid + 0xFFFF) >> 16 != idx.n_blocks || idx.masks.size() != idx.n_blocks ||
+      idx.dir.size() != (size_t)idx.n_blocks * idx.nslices)
+    return invalid("the header does not describe it");
+  auto put16 = [&](uint32_t v) {
+    out->push_back((uint8_t)(v & 0xFF));
+    out->push_back((uint8_t)((v >> 8) & 0xFF));
+  };
+  put16(kRbCookie);
+  out->push_back(2);
+  out->push_back((uint8_t)idx.nslices);
+  put16(idx.n_blocks);
+  put16((uint32_t)(idx.max_rid & 0xFFFF));
+  put16((uint32_t)(idx.max_rid >> 16));
+  const size_t bpm = (idx.nslices + 7) >> 3;
+  for (uint64_t m : idx.masks)
+    for (size_t j = 0; j < bpm; j++) out->push_back((uint8_t)(m >> (8 * j)));
+  for (size_t j = 0; j < idx.dir.size(); j++) {
+    const RbEntry& e = idx.dir[j];
+    const bool in_mask = (idx.masks[j / idx.nslices] >> (j % idx.nslices)) & 1;
+    if (in_mask != (e.kind != kRbAbsent)) return invalid("a mask and its entries disagree");
+    if (!in_mask) continue;
+    if (e.kind > 2 || (e.slot & 1)) return invalid("an entry of no known kind or an odd slot");
+    if (e.slot > arena_bytes) return invalid("a slot outside the arena");
+    const uint64_t room = arena_bytes - e.slot;
+    const uint8_t* src = arena + e.slot;
+    uint64_t len;
+    if (e.kind == 1) {
+      if (e.card < 1 || e.card > 65536) return invalid("a bitmap's cardinality");
+      out->push_back(RBT_BITMAP);
+      put16(e.card & 0xFFFF);
+      len = 8192;
+    } else if (e.kind == 2) {
+      if (room < 4) return invalid("a slot outside the arena");
+      const uint32_t nruns = rd16(src + 2);
+      out->push_back(RBT_RUN);
+      put16(nruns);
+      len = 4ull * nruns + 4;
+    } else {
+      if (e.card > 0xFFFF) return invalid("an array's cardinality");
+      out->push_back(RBT_ARRAY);
+      put16(e.card);
+      len = 2ull * e.card;
+    }
+    if (room < len) return invalid("a slot outside the arena");
+    const size_t skip = e.kind == 2 ? 4 : 0;
+    out->insert(out->end(), src + skip, src + len);
+  }
+  return RBG_OK;
+}
+
 }  // namespace rbg

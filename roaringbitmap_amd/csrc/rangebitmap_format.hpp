@@ -53,5 +53,12 @@ struct RbIndex {
 int rb_parse(const uint8_t* p, size_t n, RbIndex* out, std::string* err);
 // every container of the directory into its slot of arena (arena_bytes, zeroed by the caller)
 void rb_relay(const uint8_t* p, const RbIndex& idx, uint8_t* arena);
+// The inverse of rb_relay, Appender.serialize (:1483-1504): the stream of a directory (nslices, n_blocks,
+// max_rid, masks and per entry kind, card and slot; src and nruns are not read), its containers taken from
+// their slots of an arena of arena_bytes.  A run's count is read from its slot, a bitmap's size field is its
+// cardinality as a Java char (65,536 written as 0).  For what rb_parse and rb_relay made of a stream these are
+// the bytes rb_parse consumed.  RBG_ERR_INVALID_FORMAT for a directory that does not fit its header or a slot
+// that leaves the arena.
+int rb_emit(const RbIndex& idx, const uint8_t* arena, uint64_t arena_bytes, std::vector<uint8_t>* out, std::string* err);
 
 }  // namespace rbg

@@ -656,6 +656,44 @@ class Engine:
         check(lib().rbg_ctx_rangebitmap_load(self._ctx, b, len(b), ctypes.byref(out)))
         return out.value
 
+    def rangebitmap_build(self, values, maxValue=None) -> int:
+        """RangeBitmap.appender(maxValue), add for every value in order, build -- on the device
+        (rbg_ctx_rangebitmap_build) -> index handle, the one rangebitmap_load gives for the Appender's stream
+        of the same values.  A numpy uint64 / int64 array (int64 taken as its bit pattern, as add_many takes
+        it) is uploaded.  A torch int64 tensor on this engine's GPU is read in place
+        (rbg_ctx_rangebitmap_build_device) with point_query's stream handshake: the values are not copied (a
+        non-contiguous tensor is first made contiguous on the current stream) and must not change until the
+        call returns.  maxValue=None: the largest value given.  A value outside maxValue's mask raises
+        IllegalArgumentException("... too large") and builds nothing (the reference's add throws at that row).
+        Synchronous: the largest value and the arena's size are read back."""
+        out = ctypes.c_int32()
+        from_data = maxValue is None
+        mx = 0 if from_data else int(maxValue) & 0xFFFFFFFFFFFFFFFF
+        if is_torch(values):
+            import torch
+            if values.device.type != "cuda" or values.device.index != self.device:
+                raise ValueError(f"rangebitmap_build: the tensor must be on device {self.device}")
+            if values.dtype != torch.int64:
+                raise ValueError("rangebitmap_build: a tensor of int64 is required")
+            t = values.contiguous().reshape(-1)
+            done = self._handshake(values.device)
+            check(lib().rbg_ctx_rangebitmap_build_device(self._ctx, _dptr(t), t.numel(), mx, int(from_data),
+                                                         ctypes.byref(out)))
+            done()
+            return out.value
+        v = np.asarray(values)
+        if v.dtype not in (np.dtype(np.uint64), np.dtype(np.int64)):
+            raise ValueError("rangebitmap_build: an array of uint64 or int64 is required")
+        v = np.ascontiguousarray(v).reshape(-1)
+        check(lib().rbg_ctx_rangebitmap_build(self._ctx, ctypes.c_void_p(v.ctypes.data) if v.size else None, v.size,
+                                              mx, int(from_data), ctypes.byref(out)))
+        return out.value
+
+    def rangebitmap_serialize(self, index) -> bytes:
+        """Appender.serialize of a resident index, loaded or built (rbg_ctx_rangebitmap_serialize): for a built
+        one the Appender's bytes, for a loaded one the bytes that were mapped."""
+        return call_bytes(lib().rbg_ctx_rangebitmap_serialize, self._ctx, int(index))
+
     def rangebitmap_release(self, index):
         check(lib().rbg_ctx_rangebitmap_release(self._ctx, int(index)))
 

@@ -168,6 +168,23 @@ class RangeBitmap:
         return Appender(maxValue)
 
     @classmethod
+    def from_values(cls, values, maxValue=None, gpu=False):
+        """appender(maxValue), add for every value of a numpy array (uint64, or int64 taken as its bit pattern)
+        in order, build -> RangeBitmap.  maxValue=None: the largest value given.  The host default runs the
+        Appender; gpu=True builds and serializes on the device (rbg_rangebitmap_build), the same bytes.  A value
+        outside the mask raises IllegalArgumentException."""
+        v = np.asarray(values)
+        if v.dtype.kind == "i":
+            v = v.astype(np.int64).view(np.uint64)
+        v = np.ascontiguousarray(v.astype(np.uint64, copy=False)).reshape(-1)
+        if not gpu:
+            app = Appender(int(v.max()) if maxValue is None and v.size else (maxValue or 0))
+            app.add_many(v)
+            return app.build()
+        return cls(call_bytes(lib().rbg_rangebitmap_build, ctypes.c_void_p(v.ctypes.data) if v.size else None, v.size,
+                              0 if maxValue is None else _u64(maxValue), int(maxValue is None)))
+
+    @classmethod
     def map(cls, buffer):
         """map(ByteBuffer) (:65-85): validated on the host (InvalidRoaringFormat / TruncatedInput)"""
         return cls(buffer)
