@@ -71,8 +71,15 @@ Ctx::~Ctx() {
     g_ctxs.erase(std::remove(g_ctxs.begin(), g_ctxs.end(), this), g_ctxs.end());
   }
   prof_free();
+  if (rs[1].stream) {  // both streams drained before anything they use goes
+    (void)hipStreamSynchronize(rs[1].stream);
+    if (stream) (void)hipStreamSynchronize(stream);
+  }
   if (pinned) (void)hipHostFree(pinned);
   batches.clear();
+  if (rs[1].done) (void)hipEventDestroy(rs[1].done);
+  if (rs[1].main_done) (void)hipEventDestroy(rs[1].main_done);
+  if (rs[1].stream) (void)hipStreamDestroy(rs[1].stream);
   if (stream) (void)hipStreamDestroy(stream);
 }
 
@@ -133,11 +140,14 @@ int DevBuf::ensure(size_t bytes) {
 }
 
 // entry of a session call: the context's device, and the context out-of-memory retries empty first
-int enter(Ctx* c) {
+int enter(Ctx* c, bool counts) {
   t_cur_ctx = c;
+  if (counts) c->seq++;  // (see Ctx::seq)
   HIPCHK(hipSetDevice(c->device));
   return RBG_OK;
 }
+
+static int rs_alloc(Ctx* c, ResultSet& r);
 
 int ctx_init(Ctx* c, int device) {
   int n = 0;
@@ -161,19 +171,86 @@ int ctx_init(Ctx* c, int device) {
   HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   CHK(c->by_key.ensure(sizeof(PTask) * kMaxKeys));  // Task (wide) or PTask (pairwise) records
   CHK(c->flag.ensure(kMaxKeys));
+  CHK(c->wg_count.ensure(4 * 256));
+  CHK(c->scalar.ensure(64));
+  return rs_alloc(c, c->rs[0]);
+}
+
+// ---------------------------------------------------------------------------
+// the two result sets and their streams
+// ---------------------------------------------------------------------------
+// One op after the other on one stream leaves HBM idle at every launch boundary and through the compute
+// kernel's tail, and the serialization cannot start before the last task is placed.  A stream of independent
+// pairwise ops is therefore run as two in-order lanes: op N with its serialization on set N % 2's stream,
+// with that set's own records, buffers and plan state, so each lane's launch gaps and tails are filled by
+// the other lane's kernels.  Within a lane the stream's order is all the ordering there is; between the
+// lanes there is no event in the steady state.  Events order the rest: the context's stream waits for set
+// 1's stream before anything consumes a result, frees an operand or runs an op of another kind (join_set),
+// and set 1's stream waits for the context's stream after any call that may have given it work (lane_sync).
+// The host waits for nothing.
+static int join_set(Ctx* c, ResultSet& r) {
+  r.in_flight = false;  // consumed, or overwritten by what follows
+  if (r.stream == c->stream || !r.touched) return RBG_OK;
+  HIPCHK(hipEventRecord(r.done, r.stream));
+  HIPCHK(hipStreamWaitEvent(c->stream, r.done, 0));
+  r.touched = false;
+  return RBG_OK;
+}
+int join_result(Ctx* c) { return join_set(c, c->r()); }
+int join_all(Ctx* c) {
+  CHK(join_set(c, c->rs[0]));
+  return join_set(c, c->rs[1]);
+}
+// an op that runs on the context's stream: behind both lanes, into set 0
+int main_set(Ctx* c) {
+  CHK(join_all(c));
+  c->cur = 0;
+  c->seq++;
+  return RBG_OK;
+}
+// before the current set's stream is given work: it has run behind everything the context's stream held
+// when the last counted call returned (a load, a consumer that placed or read this set, an op of another kind)
+static int lane_sync(Ctx* c) {
+  ResultSet& r = c->r();
+  if (r.stream == c->stream) return RBG_OK;
+  if (r.synced_seq != c->seq) {
+    HIPCHK(hipEventRecord(r.main_done, c->stream));
+    HIPCHK(hipStreamWaitEvent(r.stream, r.main_done, 0));
+    r.synced_seq = c->seq;
+  }
+  r.touched = true;
+  return RBG_OK;
+}
+// the host waits for both streams; nothing is in flight afterwards, so the next op runs on the context's stream
+int sync_streams(Ctx* c) {
+  if (c->rs[1].stream) HIPCHK(hipStreamSynchronize(c->rs[1].stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (ResultSet& r : c->rs) r.in_flight = r.touched = false;
+  return RBG_OK;
+}
+// a set's stream, events and the buffers whose size no op changes (result and scratch are sized by
+// prepare_output); set 0 runs on the context's stream
+static int rs_alloc(Ctx* c, ResultSet& r) {
+  if (r.ready) return RBG_OK;
+  if (&r == &c->rs[0]) {
+    r.stream = c->stream;
+  } else {
+    if (!r.stream) HIPCHK(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
+    if (!r.done) HIPCHK(hipEventCreateWithFlags(&r.done, hipEventDisableTiming));
+    if (!r.main_done) HIPCHK(hipEventCreateWithFlags(&r.main_done, hipEventDisableTiming));
+  }
   // (+ 32768 records past the largest task list: sized for the removed key-order pairwise form's
   // wave-major layout; kept so no op's buffer shrinks)
-  CHK(c->tasks.ensure(sizeof(PTask) * (kMaxKeys + 32768)));
-  CHK(c->ntasks.ensure(64));
-  CHK(c->wg_count.ensure(4 * 256));
-  CHK(c->wg_epoch.ensure(8 * 256));
-  HIPCHK(hipMemset(c->wg_epoch.p, 0, 8 * 256));
-  CHK(c->lb.ensure(kLbHeader + 8 * (kMaxKeys + 2 * kMaxTiles + kMaxAggTiles)));  // + the pairwise tile aggregates
-  CHK(c->recs.ensure(sizeof(ORec) * kMaxKeys));
-  CHK(c->kind_by_out.ensure(kMaxKeys));
-  CHK(c->scalar.ensure(64));
-  CHK(c->info.ensure(sizeof(ResultInfo)));
-  CHK(c->task_card.ensure(4 * kMaxKeys));
+  CHK(r.tasks.ensure(sizeof(PTask) * (kMaxKeys + 32768)));
+  CHK(r.ntasks.ensure(64));
+  CHK(r.wg_epoch.ensure(8 * 256));
+  HIPCHK(hipMemsetAsync(r.wg_epoch.p, 0, 8 * 256, r.stream));  // in front of the stream's first plan kernel
+  CHK(r.lb.ensure(kLbHeader + 8 * (kMaxKeys + 2 * kMaxTiles + kMaxAggTiles)));  // + the pairwise tile aggregates
+  CHK(r.recs.ensure(sizeof(ORec) * kMaxKeys));
+  CHK(r.kind_by_out.ensure(kMaxKeys));
+  CHK(r.info.ensure(sizeof(ResultInfo)));
+  CHK(r.task_card.ensure(4 * kMaxKeys));
+  r.ready = true;
   return RBG_OK;
 }
 
@@ -189,14 +266,14 @@ int pinned_ensure(Ctx* c, size_t bytes) {
 
 // epoch of the next pairwise plan (never 0, the value the tags start from)
 static uint32_t next_epoch(Ctx* c) {
-  if (++c->epoch == 0) ++c->epoch;
-  return c->epoch;
+  if (++c->r().epoch == 0) ++c->r().epoch;
+  return c->r().epoch;
 }
 // Where the plan kernel of the op being enqueued writes (after prepare_output, which decides what it
 // zeroes); one new epoch per plan that compacts its tasks (k_plan_balanced does not: compacts = false)
 static PlanOut plan_out(Ctx* c, bool compacts = true) {
-  return PlanOut{c->wg_epoch.as<uint64_t>(), compacts ? next_epoch(c) : 0, c->tasks.as<PTask>(),
-                 c->ntasks.as<uint32_t>(), c->zlb, c->ztile};
+  return PlanOut{c->r().wg_epoch.as<uint64_t>(), compacts ? next_epoch(c) : 0, c->r().tasks.as<PTask>(),
+                 c->r().ntasks.as<uint32_t>(), c->zlb, c->ztile};
 }
 
 int find_batch(Ctx* c, int32_t id, Batch** out) {
@@ -312,38 +389,58 @@ int grid_for(size_t tasks, size_t cap) {
 // Output state of a materialising op: per-task records + scratch slots (the
 // device-resident result), and the portable-format buffer the serialization
 // writes into on fetch.  Card-only ops need no output state.
-int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* oc, bool card_only) {
-  uint8_t* lb = c->lb.as<uint8_t>();  // look-back state: ticket @0, error word @64, statuses @256
+// lanes (a materialising pairwise op): if the current set's serialization is enqueued and nothing consumed
+// it, the op takes the other set (made by the first op that does) and runs on that set's stream, behind the
+// serialization of two ops ago and beside the last one.  Every other op runs on the context's stream,
+// behind both lanes, into set 0.
+int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* oc, bool card_only, bool lanes) {
+  if (!lanes || card_only) {
+    CHK(main_set(c));
+  } else {
+    if (c->r().in_flight) {
+      ResultSet& o = c->rs[c->cur ^ 1];
+      CHK(rs_alloc(c, o));
+      c->cur ^= 1;
+      o.in_flight = false;  // its own stream orders this op behind that serialization
+      o.last = 0;
+    } else if (c->cur != 0) {
+      // nothing to run beside (the last result was consumed, or the host has waited): back to the context's
+      // stream, so that whatever a caller puts on that stream brackets and follows the op as it always did
+      CHK(main_set(c));
+    }
+    CHK(lane_sync(c));
+  }
+  uint8_t* lb = c->r().lb.as<uint8_t>();  // look-back state: ticket @0, error word @64, statuses @256
   *oc = OutCtx{};
   oc->err = reinterpret_cast<uint32_t*>(lb + 64);
   oc->status = reinterpret_cast<uint64_t*>(lb + kLbHeader);
   oc->tile_status = reinterpret_cast<uint64_t*>(lb + kLbHeader + 8 * kMaxKeys);
   oc->tile_card = reinterpret_cast<uint64_t*>(lb + kLbHeader + 8 * (kMaxKeys + kMaxTiles));
-  oc->recs = c->recs.as<ORec>();
-  c->serialized = false;
-  c->place_pending = false;
-  c->agg_ok = false;
-  c->ri_valid = false;
-  c->pending_ub = 0;
+  oc->recs = c->r().recs.as<ORec>();
+  c->r().serialized = false;
+  c->r().place_pending = false;
+  c->r().agg_ok = false;
+  c->r().ri_valid = false;
+  c->r().pending_ub = 0;
   c->zlb = c->ztile = nullptr;
-  c->pending_src.clear();
+  c->r().pending_src.clear();
   if (card_only) {
     c->zlb = reinterpret_cast<uint64_t*>(lb);  // the error word must not carry over from an earlier op
     return RBG_OK;
   }
   const uint64_t P0 = header_reserve(max_tasks);
-  CHK(c->result.ensure(P0 + max_payload + 64));
-  c->result_cap = P0 + max_payload;
-  CHK(c->scratch.ensure((size_t)kSlotBytes * std::max<size_t>(max_tasks, 1) + 64));
+  CHK(c->r().result.ensure(P0 + max_payload + 64));
+  c->r().result_cap = P0 + max_payload;
+  CHK(c->r().scratch.ensure((size_t)kSlotBytes * std::max<size_t>(max_tasks, 1) + 64));
   // the look-back header and tile statuses are zeroed by the op's plan kernel
   c->zlb = reinterpret_cast<uint64_t*>(lb);
   c->ztile = reinterpret_cast<uint64_t*>(lb + kLbHeader + 8 * kMaxKeys);
-  oc->out = c->result.as<uint8_t>();
+  oc->out = c->r().result.as<uint8_t>();
   oc->payload_base = P0;
-  oc->scratch = c->scratch.as<uint8_t>();
-  oc->kind_by_out = c->kind_by_out.as<uint8_t>();
-  c->pending = *oc;
-  c->pending_ub = max_tasks;
+  oc->scratch = c->r().scratch.as<uint8_t>();
+  oc->kind_by_out = c->r().kind_by_out.as<uint8_t>();
+  c->r().pending = *oc;
+  c->r().pending_ub = max_tasks;
   return RBG_OK;
 }
 
@@ -351,38 +448,49 @@ int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* oc, boo
 // (serialization, result statistics, a key-shard fetch): an op whose caller only wants the
 // result to exist on the device (a BSI query followed by its sum) does not pay for it.
 void defer_place(Ctx* c) {
-  c->place_pending = true;
-  c->last = 1;
+  c->r().place_pending = true;
+  c->r().last = 1;
 }
-int ensure_placed(Ctx* c) {
-  if (!c->place_pending) return RBG_OK;
-  launch_place(c->stream, c->ntasks.as<uint32_t>(), c->pending, c->info.as<ResultInfo>());
+static int place_on(Ctx* c, hipStream_t s) {
+  if (!c->r().place_pending) return RBG_OK;
+  launch_place(s, c->r().ntasks.as<uint32_t>(), c->r().pending, c->r().info.as<ResultInfo>());
   HIPCHK(hipGetLastError());
-  c->place_pending = false;
+  c->r().place_pending = false;
   return RBG_OK;
 }
+int ensure_placed(Ctx* c) { return place_on(c, c->stream); }
 
 // Portable serialization of the pending result (RB/RoaringArray.java:896-940),
 // on the device, once per result.
-int ctx_serialize(Ctx* c) {
-  if (c->last != 1) {
+// Its kernels go to the set's own stream, where the op's kernels are (on_main: to the context's stream, joined
+// first); in_flight from here until something consumes the result.
+int ctx_serialize(Ctx* c, bool on_main) {
+  ResultSet& r = c->r();
+  if (r.last != 1) {
     set_err("no materialised result pending");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  if (c->serialized) return RBG_OK;
-  if (c->place_pending && c->agg_ok && !c->pending.spec && c->pending_ub <= (size_t)kMaxAggTiles * kAggTile) {
-    // placement from the compute kernel's tile sums and the serialization in one launch
-    launch_serialize_agg(c->stream, c->ntasks.as<uint32_t>(), c->pending, c->info.as<ResultInfo>(), c->pending_ub);
-    HIPCHK(hipGetLastError());
-    c->place_pending = false;
-    c->serialized = true;
-    return RBG_OK;
+  if (r.serialized) return RBG_OK;
+  hipStream_t s = r.stream;
+  if (on_main) {
+    CHK(join_result(c));
+    c->seq++;  // the set's stream runs behind this before it goes on
+    s = c->stream;
+  } else {
+    CHK(lane_sync(c));  // (a consumer may have placed the result on the context's stream)
   }
-  CHK(ensure_placed(c));
-  if (c->pending.spec) launch_spec_fix(c->stream, c->ntasks.as<uint32_t>(), c->pending);
-  launch_serialize(c->stream, c->ntasks.as<uint32_t>(), c->pending);
+  if (r.place_pending && r.agg_ok && !r.pending.spec && r.pending_ub <= (size_t)kMaxAggTiles * kAggTile) {
+    // placement from the compute kernel's tile sums and the serialization in one launch
+    launch_serialize_agg(s, r.ntasks.as<uint32_t>(), r.pending, r.info.as<ResultInfo>(), r.pending_ub);
+    r.place_pending = false;
+  } else {
+    CHK(place_on(c, s));
+    if (r.pending.spec) launch_spec_fix(s, r.ntasks.as<uint32_t>(), r.pending);
+    launch_serialize(s, r.ntasks.as<uint32_t>(), r.pending);
+  }
   HIPCHK(hipGetLastError());
-  c->serialized = true;
+  r.serialized = true;
+  r.in_flight = !on_main;
   return RBG_OK;
 }
 
@@ -408,7 +516,7 @@ int resolve(Ctx* c, int32_t id, size_t i, Operand* op) {
 // pass-through records point into, the first two phase marks), op_end after the launch (the placement
 // deferred, the last two marks, the launch's error).
 static void op_begin(Ctx* c, std::initializer_list<int32_t> src) {
-  c->pending_src = src;
+  c->r().pending_src = src;
   c->mark(0);
   c->mark(1);
 }
@@ -777,7 +885,7 @@ static int ctx_pairwise_buffer(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib
   return with_big_runs(c, true, "buffer and / andNot", [&](const BigRuns& big) -> int {
     OutCtx oc;
     CHK(prepare_output(c, ub, A.b->payload_bytes + B.b->payload_bytes + kStagedMax * ub + big.cap, &oc, false));
-    c->pending_src = {ia, ib};
+    c->r().pending_src = {ia, ib};
     c->mark(0);
     const PlanOut po = plan_out(c);
     launch_plan_pairwise(s, op, key_lo, key_hi, A, B, po, oc.err);
@@ -815,7 +923,7 @@ int ctx_ornot(Ctx* c, int32_t ia, size_t ma, int32_t ib, size_t mb, int64_t rang
     HIPCHK(hipMemcpyAsync(&pl, c->ornot_plan.p, sizeof(pl), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
     if (pl.neg) {
-      c->last = 0;
+      c->r().last = 0;
       set_err("orNot: negative maxSize (the reference throws NegativeArraySizeException)");
       return RBG_ERR_ILLEGAL_ARGUMENT;
     }
@@ -912,13 +1020,13 @@ int ctx_add_offset(Ctx* c, int32_t ia, size_t ma, int64_t offset) {
 // op RBG_OR_INPLACE: x1.or(x2) in place (RB/RoaringBitmap.java:2481-2523), the OR with Container.ior's
 // types (k_ior_fix)
 int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, bool card_only, int key_lo,
-                 int key_hi) {
+                 int key_hi, bool lanes) {
   if (op == RBG_AND_BUFFER || op == RBG_ANDNOT_BUFFER) {
     if (card_only) return RBG_ERR_ILLEGAL_ARGUMENT;
     return ctx_pairwise_buffer(c, op == RBG_AND_BUFFER ? OP_AND : OP_ANDNOT, ia, ma, ib, mb, key_lo, key_hi);
   }
   if (op == RBG_OR_INPLACE && !card_only) {
-    CHK(ctx_pairwise(c, OP_OR, ia, ma, ib, mb, false, key_lo, key_hi));
+    CHK(ctx_pairwise(c, OP_OR, ia, ma, ib, mb, false, key_lo, key_hi, false));  // on the context's stream, like the fix-up
     if (!c->ones.p) {
       CHK(c->ones.ensure(8192));
       HIPCHK(hipMemsetAsync(c->ones.p, 0xFF, 8192, c->stream));
@@ -926,9 +1034,10 @@ int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, b
     Operand A, B;
     CHK(resolve(c, ia, ma, &A));
     CHK(resolve(c, ib, mb, &B));
-    launch_ior_fix(c->stream, c->ntasks.as<uint32_t>(), c->recs.as<ORec>(), A, B, c->ones.as<uint8_t>());
+    CHK(join_result(c));
+    launch_ior_fix(c->stream, c->r().ntasks.as<uint32_t>(), c->r().recs.as<ORec>(), A, B, c->ones.as<uint8_t>());
     HIPCHK(hipGetLastError());
-    c->agg_ok = false;  // k_ior_fix changed records after the compute kernel summed them
+    c->r().agg_ok = false;  // k_ior_fix changed records after the compute kernel summed them
     return RBG_OK;
   }
   if (op < 0 || op > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
@@ -937,7 +1046,6 @@ int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, b
   Operand A, B;
   CHK(resolve(c, ia, ma, &A));
   CHK(resolve(c, ib, mb, &B));
-  hipStream_t s = c->stream;
   const int plan_op = card_only ? OP_AND : op;
   size_t ub;
   switch (plan_op) {
@@ -952,8 +1060,9 @@ int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, b
   const bool dense = nkeys > 0 && 2 * ub >= nkeys;
   OutCtx oc;
   CHK(prepare_output(c, dense ? std::max(ub, nkeys) : ub, A.b->payload_bytes + B.b->payload_bytes + kStagedMax * ub,
-                     &oc, card_only));
-  c->pending_src = {ia, ib};
+                     &oc, card_only, lanes));
+  hipStream_t s = c->r().stream;  // the set's own
+  c->r().pending_src = {ia, ib};
   c->mark(0);
   const PwDirect pd{key_lo};
   const PlanOut po = plan_out(c, !dense);
@@ -961,7 +1070,7 @@ int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, b
     // tasks binned by estimated cost so every wave draws the same mix (k_plan_balanced)
     // ... run by one 16-wave workgroup per CU that claims the CU's tasks through LDS (k_pair_cu)
     launch_plan_balanced(s, plan_op, card_only ? 1 : 0, key_lo, (uint32_t)nkeys, A, B, po, oc,
-                         c->task_card.as<uint32_t>());
+                         c->r().task_card.as<uint32_t>());
   } else {
     launch_plan_pairwise(s, plan_op, key_lo, key_hi, A, B, po, oc.err);
     dbg(s, "plan");
@@ -971,18 +1080,18 @@ int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, b
   // plan kernel has zeroed the sums first
   if (!card_only) {
     oc.tile_agg = reinterpret_cast<unsigned long long*>(oc.tile_status + 2 * kMaxTiles);
-    c->pending.tile_agg = oc.tile_agg;
-    c->agg_ok = true;
+    c->r().pending.tile_agg = oc.tile_agg;
+    c->r().agg_ok = true;
   }
   // 4 waves (tasks) per workgroup, clamped to the resident grid
   const int grid = grid_for(((dense ? nkeys : ub) + 3) / 4, 16384);
   launch_pairwise(s, op, card_only ? 1 : 0, grid, po.tasks, po.n_tasks, A.payload, B.payload, oc,
-                  c->task_card.as<uint32_t>(), dense ? &pd : nullptr);
+                  c->r().task_card.as<uint32_t>(), dense ? &pd : nullptr);
   dbg(s, "pairwise");
   c->mark(2);
   if (card_only) {
-    launch_reduce_card(s, c->task_card.as<uint32_t>(), c->ntasks.as<uint32_t>(), c->info.as<ResultInfo>(), oc.err);
-    c->last = 2;
+    launch_reduce_card(s, c->r().task_card.as<uint32_t>(), c->r().ntasks.as<uint32_t>(), c->r().info.as<ResultInfo>(), oc.err);
+    c->r().last = 2;
   } else {
     defer_place(c);
   }
@@ -1017,27 +1126,28 @@ int batch_host_index(Ctx* c, Batch* b) {
 }
 
 int ctx_info(Ctx* c, ResultInfo* ri) {
-  if (c->last == 1) CHK(ensure_placed(c));
-  HIPCHK(hipMemcpyAsync(ri, c->info.p, sizeof(ResultInfo), hipMemcpyDeviceToHost, c->stream));
+  CHK(join_result(c));
+  if (c->r().last == 1) CHK(ensure_placed(c));
+  HIPCHK(hipMemcpyAsync(ri, c->r().info.p, sizeof(ResultInfo), hipMemcpyDeviceToHost, c->stream));
   uint64_t card = 0;
   uint32_t err = 0;
-  if (c->last == 1)  // materialised result: k_place / the pairwise placer accumulated its cardinality
-    HIPCHK(hipMemcpyAsync(&card, c->lb.as<uint8_t>() + 64 + 8 * kCardWord, 8, hipMemcpyDeviceToHost, c->stream));
-  if (c->last == 1 || c->last == 2)  // spin timeouts of any kernel of the op
-    HIPCHK(hipMemcpyAsync(&err, c->lb.as<uint8_t>() + 64, 4, hipMemcpyDeviceToHost, c->stream));
+  if (c->r().last == 1)  // materialised result: k_place / the pairwise placer accumulated its cardinality
+    HIPCHK(hipMemcpyAsync(&card, c->r().lb.as<uint8_t>() + 64 + 8 * kCardWord, 8, hipMemcpyDeviceToHost, c->stream));
+  if (c->r().last == 1 || c->r().last == 2)  // spin timeouts of any kernel of the op
+    HIPCHK(hipMemcpyAsync(&err, c->r().lb.as<uint8_t>() + 64, 4, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->last == 1) {
+  if (c->r().last == 1) {
     ri->long_card = (int64_t)card;
     ri->card32 = (uint32_t)card;
   }
   ri->err |= err;
-  if ((c->last == 1 || c->last == 2) && ri->err) {
+  if ((c->r().last == 1 || c->r().last == 2) && ri->err) {
     set_err("a look-back spin of the op's plan or placement timed out: the result is invalid");
     return RBG_ERR_DEVICE;
   }
-  if (c->last == 1) {
-    c->last_ri = *ri;
-    c->ri_valid = true;
+  if (c->r().last == 1) {
+    c->r().last_ri = *ri;
+    c->r().ri_valid = true;
   }
   return RBG_OK;
 }
@@ -1129,18 +1239,18 @@ uint8_t* out_alloc(size_t n) {
 }
 
 int ctx_fetch(Ctx* c, rbg_buffer* out) {
-  if (c->last != 1) {
+  if (c->r().last != 1) {
     set_err("no serialized result pending");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  CHK(ctx_serialize(c));
+  CHK(ctx_serialize(c, true));  // consumed at once: on the context's stream (a no-op if already serialized)
   ResultInfo ri;
-  CHK(ctx_info(c, &ri));
+  CHK(ctx_info(c, &ri));  // joins the set's stream
   uint8_t* p = out_alloc(ri.total);
   if (!p) return RBG_ERR_OUT_OF_MEMORY;
   out->data = p;
   out->len = ri.total;
-  const int st = download_staged(c, c->result.as<uint8_t>() + ri.start, ri.total, p);
+  const int st = download_staged(c, c->r().result.as<uint8_t>() + ri.start, ri.total, p);
   if (st != RBG_OK) {
     rbg_free(out);
     return st;
@@ -1245,6 +1355,7 @@ int ctx_batch_card(Ctx* c, int32_t id) {
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
   const size_t np = B->n_bm / 2;
+  CHK(main_set(c));  // takes no set of its own: set 0's `last` changes
   CHK(c->cards.ensure(4 * std::max<size_t>(np, 1)));
   if (B->key_major && B->n_bm > 1) {
     // pairs need bitmap-major ranges: permuted view of a key-major batch is not supported
@@ -1270,7 +1381,7 @@ int ctx_batch_card(Ctx* c, int32_t id) {
   c->mark(3);
   HIPCHK(hipGetLastError());
   c->n_cards = np;
-  c->last = 3;
+  c->r().last = 3;
   return RBG_OK;
 }
 
@@ -1278,7 +1389,7 @@ int ctx_batch_card(Ctx* c, int32_t id) {
 // total_containers containers, enqueued on the context stream.
 int ctx_fetch_shard_device(Ctx* c, int64_t total_containers, int has_run, int64_t payload_base, void* desc_dst,
                            void* offsets_dst, void* runflag_dst, void* payload_dst) {
-  if (c->last != 1) {
+  if (c->r().last != 1) {
     set_err("no materialised result pending");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
@@ -1295,8 +1406,9 @@ int ctx_fetch_shard_device(Ctx* c, int64_t total_containers, int has_run, int64_
   // reported a timed-out spin as RBG_ERR_DEVICE), so the fetch stays asynchronous; without one,
   // ctx_info synchronises here
   ResultInfo ri;
-  if (c->ri_valid) {
-    ri = c->last_ri;
+  CHK(join_result(c));
+  if (c->r().ri_valid) {
+    ri = c->r().last_ri;
     CHK(ensure_placed(c));
   } else {
     CHK(ctx_info(c, &ri));
@@ -1307,15 +1419,15 @@ int ctx_fetch_shard_device(Ctx* c, int64_t total_containers, int has_run, int64_
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
   uint8_t* emit_dst = (uint8_t*)payload_dst;
-  if (c->serialized) {
+  if (c->r().serialized) {
     // already serialized (possibly because an operand batch was released since): copy the
     // payload region rather than re-reading the operands' pass-through containers
     if (ri.payload)
-      HIPCHK(hipMemcpyAsync(payload_dst, c->result.as<uint8_t>() + c->pending.payload_base, ri.payload,
+      HIPCHK(hipMemcpyAsync(payload_dst, c->r().result.as<uint8_t>() + c->r().pending.payload_base, ri.payload,
                             hipMemcpyDeviceToDevice, c->stream));
     emit_dst = nullptr;
   }
-  launch_serialize_shard(c->stream, grid_for((c->pending_ub + 255) / 256, 256), c->ntasks.as<uint32_t>(), c->pending,
+  launch_serialize_shard(c->stream, grid_for((c->r().pending_ub + 255) / 256, 256), c->r().ntasks.as<uint32_t>(), c->r().pending,
                          emit_dst, off0, (uint8_t*)desc_dst, offsets ? (uint8_t*)offsets_dst : nullptr,
                          has_run ? (uint8_t*)runflag_dst : nullptr);
   HIPCHK(hipGetLastError());
@@ -1483,7 +1595,7 @@ int ctx_select_range(Ctx* c, int32_t id, int64_t start, int64_t end, int32_t* ou
 
 // HIP-event phase timing of the next max_ops ops (Ctx::mark); max_ops <= 0 turns it off
 int ctx_profile(Ctx* c, int max_ops, bool compute_only) {
-  HIPCHK(hipStreamSynchronize(c->stream));
+  CHK(sync_streams(c));
   c->prof_free();
   c->prof_compute_only = compute_only;
   if (max_ops <= 0) return RBG_OK;

@@ -137,13 +137,58 @@ struct DecBufs {  // scratch of the device decode (decode.hip), reused across lo
       size, cpart;
 };
 
+// Everything prepare_output hands out to a materialising op and everything that describes the result until
+// it is consumed, with the stream its kernels run on and the plan state of a pairwise op.  A context holds
+// two: a pairwise op that finds the current set's serialization enqueued and not consumed takes the other
+// set, on the other stream, so a stream of independent ops runs as two in-order lanes with no event between
+// them.  Set 0 runs on the context's own stream.
+struct ResultSet {
+  hipStream_t stream = nullptr;
+  DevBuf tasks;     // the op's task list: Task (wide) or PTask (pairwise) records
+  DevBuf wg_epoch;  // pairwise plan: per-workgroup task counts tagged with the op epoch
+  uint32_t epoch = 0;
+  // look-back state: ticket @0, error word @64, result card @96, the task statuses @kLbHeader, then the tile
+  // statuses, tile cardinalities and the pairwise tile sums
+  DevBuf lb;
+  DevBuf recs, scratch, result, kind_by_out, info, ntasks, task_card;
+  size_t result_cap = 0;
+  OutCtx pending{};         // output state of the set's materialising op
+  std::vector<int32_t> pending_src;  // batches the pending result's pass-through records point into
+  size_t pending_ub = 0;
+  bool serialized = false;  // pending result already in the portable layout
+  bool place_pending = false;  // the op's k_place not launched yet (serialization then places too)
+  // the pending result's records were summed per tile by its compute kernel (OutCtx::tile_agg): its
+  // serialization places and copies in one launch (k_serialize_agg) instead of k_place + k_serialize
+  bool agg_ok = false;
+  ResultInfo last_ri{};   // the pending result's facts, once ctx_info has read them (fetch_shard_device)
+  bool ri_valid = false;
+  int last = 0;  // 0 none, 1 serialized result, 2 cardinality, 3 batch cardinalities
+  bool ready = false;  // the stream, the events and the fixed-size buffers exist (rs_alloc)
+  bool in_flight = false;  // the result's serialization is enqueued on the set's stream and nothing consumed it yet
+  // set 1 only.  touched: its stream was given work the context's stream has not waited for (join_set records
+  // `done` behind it and makes the context's stream wait).  synced_seq: the value of Ctx::seq up to which its
+  // stream has waited for the context's stream (lane_sync records `main_done` there)
+  bool touched = false;
+  uint64_t synced_seq = 0;
+  hipEvent_t done = nullptr, main_done = nullptr;
+};
+
 struct Ctx {
   int device = 0;
   DecBufs dec;
-  DevBuf wg_epoch;         // pairwise plan: per-workgroup task counts tagged with the op epoch
-  uint32_t epoch = 0;
   DevBuf pc_cnt, pc_part, pc_items, pc_large;  // batched andCardinality scratch
-  hipStream_t stream = nullptr;
+  hipStream_t stream = nullptr;  // the context's stream (the one callers see): everything but set 1's pairwise
+                                 // ops and their serializations, and everything that reads a result
+  ResultSet rs[2];               // rs[1] (with its stream) is made by the first op that finds rs[0] in flight
+  int cur = 0;                   // the set of the last op: what serialize / fetch / statistics mean
+  ResultSet& r() { return rs[cur]; }
+  // counts the calls that may have given the context's stream work set 1's stream has to run behind: every
+  // entry but a pairwise op's or a serialization's own, and every op that runs on the context's stream.
+  // (Not an event recorded on every lane-1 op instead: the context's stream is also lane 0, so that wait
+  // would put op N behind serialization N - 1 and undo the lanes.)  A new entry point counts unless it only
+  // calls ctx_pairwise / ctx_serialize; whatever gives the context's stream work inside an uncounted entry
+  // bumps seq itself (main_set, ctx_serialize(on_main)).
+  uint64_t seq = 1;
   std::vector<std::unique_ptr<Batch>> batches;
   std::vector<std::unique_ptr<RangeIndex>> range_indexes;  // by index id; a released one is null
   uint64_t* zlb = nullptr;    // look-back state the next plan kernel zeroes (null: none)
@@ -180,22 +225,9 @@ struct Ctx {
   std::vector<DevBuf> pool;
   size_t pool_bytes = 0;
   std::mutex pool_mu;  // the pool may be emptied by another thread's out-of-memory allocation
-  ResultInfo last_ri{};   // the pending result's facts, once ctx_info has read them (fetch_shard_device)
-  bool ri_valid = false;
   int bsi_nbits = 0;
-  DevBuf by_key, flag, tasks, ntasks, wg_count, lb, recs, kind_by_out, info, task_card, result, cards, skip, raw,
-      scalar, scratch;
-  size_t result_cap = 0;
-  OutCtx pending{};         // output state of the last materialising op
-  std::vector<int32_t> pending_src;  // batches the pending result's pass-through records point into
-  size_t pending_ub = 0;
-  bool serialized = false;  // pending result already in the portable layout
-  bool place_pending = false;  // the op's k_place not launched yet (serialization then places too)
-  // the pending result's records were summed per tile by its compute kernel (OutCtx::tile_agg): its
-  // serialization places and copies in one launch (k_serialize_agg) instead of k_place + k_serialize
-  bool agg_ok = false;
+  DevBuf by_key, flag, wg_count, cards, skip, raw, scalar;
   size_t n_cards = 0;
-  int last = 0;  // 0 none, 1 serialized result, 2 cardinality, 3 batch cardinalities
   void* pinned = nullptr;
   size_t pinned_cap = 0;
   // HIP-event phase timing: 4 events per op (start, after plan+compact, after
@@ -214,7 +246,7 @@ struct Ctx {
       if (phase == 3 && prof_n < prof_cap) prof_n++;  // the op's record is complete
       return;
     }
-    if (prof_n < prof_cap) (void)hipEventRecord(prof_ev[4 * prof_n + phase], stream);
+    if (prof_n < prof_cap) (void)hipEventRecord(prof_ev[4 * prof_n + phase], r().stream);  // the op's stream
     if (phase == 3 && prof_n < prof_cap) prof_n++;
   }
   ~Ctx();
@@ -235,7 +267,7 @@ static inline uint64_t round16(uint64_t x) { return (x + 15) & ~15ULL; }
 // engine.cpp, contexts, pools and batches.
 void dbg(hipStream_t s, const char* what);
 int ctx_init(Ctx* c, int device);
-int enter(Ctx* c);
+int enter(Ctx* c, bool counts = true);
 int tl_ctx(Ctx** out);
 int find_batch(Ctx* c, int32_t id, Batch** out);
 int get_batch(Ctx* c, int32_t id, Batch** out);
@@ -248,12 +280,24 @@ int pinned_ensure(Ctx* c, size_t bytes);
 int upload_words(Ctx* c, void* dst, const void* src, size_t n);
 int ctx_profile(Ctx* c, int max_ops, bool compute_only);
 // engine.cpp, the output of an op: its bracket, placement, serialization, the result's facts and bytes.
-int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* oc, bool card_only);
+// lanes: the op may take the other set and its stream (the pairwise ops alone; OutCtx and the plan state are
+// then the set's own and its kernels go to c->r().stream)
+int prepare_output(Ctx* c, size_t max_tasks, size_t max_payload, OutCtx* oc, bool card_only, bool lanes = false);
 void defer_place(Ctx* c);
 int ensure_placed(Ctx* c);
 int grid_for(size_t tasks, size_t cap = 4096);
 int op_end(Ctx* c);
-int ctx_serialize(Ctx* c);
+// on_main: the caller consumes the result at once (a fetch) or needs the context stream's own order (an
+// operand's release): the serialization is enqueued on the context's stream, behind a join
+int ctx_serialize(Ctx* c, bool on_main = false);
+// The context's stream waits for what the current set's stream holds (join_result) or both sets' (join_all):
+// before anything reads or changes a result, before an operand's buffers go to the pool, and before an op
+// that runs on the context's stream (main_set: join_all, then set 0 is the current one).  Nothing on set
+// 1's stream since the last join: no call into the runtime.
+int join_result(Ctx* c);
+int join_all(Ctx* c);
+int main_set(Ctx* c);
+int sync_streams(Ctx* c);  // the host waits for both streams
 int ctx_info(Ctx* c, ResultInfo* ri);
 uint8_t* out_alloc(size_t n);
 int ctx_fetch(Ctx* c, rbg_buffer* out);
@@ -282,7 +326,7 @@ int ctx_from_bitset_host(Ctx* c, const void* bits, uint64_t n, int layout, bool 
 int ctx_to_bitset(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t n, int layout, void* out_dev);
 int ctx_to_bitset_host(Ctx* c, int32_t batch, size_t i, uint64_t first, uint64_t n, int layout, void* out);
 int ctx_pairwise(Ctx* c, int op, int32_t ia, size_t ma, int32_t ib, size_t mb, bool card_only, int key_lo = 0,
-                 int key_hi = kMaxKeys);
+                 int key_hi = kMaxKeys, bool lanes = true);
 int ctx_ornot(Ctx* c, int32_t ia, size_t ma, int32_t ib, size_t mb, int64_t range_end, int flags);
 int check_range(int64_t start, int64_t end);
 int ctx_range_mut(Ctx* c, int op, int32_t ia, size_t ma, int64_t start, int64_t end, bool buf);
@@ -343,6 +387,7 @@ static int emit_host(const std::vector<uint8_t>& v, rbg_buffer* out) { return em
 template <class Pass>
 static int with_big_runs(Ctx* c, bool use_arena, const char* what, Pass&& pass) {
   if (!use_arena) return pass(BigRuns{nullptr, nullptr, 0});
+  CHK(main_set(c));  // a serialization in flight may read records in the arena this op rewrites
   if (!c->big_ctl.p) CHK(c->big_ctl.ensure(16));
   if (!c->big.p) CHK(c->big.ensure(16ull << 20));
   for (int attempt = 0;; attempt++) {
@@ -439,5 +484,5 @@ struct __attribute__((visibility("hidden"))) rbg_ctx {
 
 namespace rbg {
 // engine_api.cpp.  Entry of a session call: a null handle is an illegal argument; else the context, entered
-int session(rbg_ctx* ctx, Ctx** c);
+int session(rbg_ctx* ctx, Ctx** c, bool counts = true);
 }  // namespace rbg

@@ -49,10 +49,11 @@ static int one_shot_binary(const uint8_t* a, size_t a_len, const uint8_t* b, siz
 using namespace rbg;
 
 // entry of a session call: a null handle is an illegal argument; else the context, entered
-int rbg::session(rbg_ctx* ctx, Ctx** c) {
+// counts false: the entry of a pairwise op or a serialization, which may go to set 1's stream (Ctx::seq)
+int rbg::session(rbg_ctx* ctx, Ctx** c, bool counts) {
   if (!ctx) return RBG_ERR_ILLEGAL_ARGUMENT;
   *c = &ctx->c;
-  return enter(*c);
+  return enter(*c, counts);
 }
 
 extern "C" {
@@ -571,7 +572,7 @@ int rbg_ctx_profile_bytes(rbg_ctx* ctx, int64_t* bytes) {
   }
   Ctx* c;
   CHK(session(ctx, &c));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  CHK(sync_streams(c));
   unsigned long long v = 0;
   if (c->rd_ctr.p) HIPCHK(hipMemcpy(&v, c->rd_ctr.p, 8, hipMemcpyDeviceToHost));
   *bytes = (int64_t)v;
@@ -580,7 +581,7 @@ int rbg_ctx_profile_bytes(rbg_ctx* ctx, int64_t* bytes) {
 int rbg_ctx_profile_read(rbg_ctx* ctx, double* ms3, int* n_ops) {
   Ctx* c;
   CHK(session(ctx, &c));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  CHK(sync_streams(c));
   ms3[0] = ms3[1] = ms3[2] = 0.0;
   for (size_t i = 0; i < c->prof_n; i++) {
     for (int ph = 0; ph < 3; ph++) {
@@ -597,8 +598,7 @@ int rbg_ctx_profile_read(rbg_ctx* ctx, double* ms3, int* n_ops) {
 int rbg_ctx_sync(rbg_ctx* ctx) {
   Ctx* c;
   CHK(session(ctx, &c));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return RBG_OK;
+  return sync_streams(c);
 }
 int rbg_ctx_load_separate(rbg_ctx* ctx, const uint8_t* const* bufs, const size_t* lens, size_t n, int32_t* ids) {
   Ctx* c;
@@ -625,12 +625,14 @@ int rbg_ctx_release(rbg_ctx* ctx, int32_t batch) {
   CHK(enter(&c));
   // A materialised result references pass-through containers inside its operand
   // batches (ORec::src) until it is serialized: serialize it before an operand goes.
-  if (c.last == 1 && !c.serialized &&
-      std::find(c.pending_src.begin(), c.pending_src.end(), batch) != c.pending_src.end())
-    CHK(ctx_serialize(&c));
+  if (c.r().last == 1 && !c.r().serialized &&
+      std::find(c.r().pending_src.begin(), c.r().pending_src.end(), batch) != c.r().pending_src.end())
+    CHK(ctx_serialize(&c, true));  // on the context's stream: in front of whatever reuses the buffers
   // No host sync: the buffers go to this context's pool, and whatever reuses them is enqueued on
-  // the same stream after every launch that reads them; a pooled buffer that is freed goes through
-  // hipFree, which waits for the device.
+  // the context's stream after every launch that reads them -- an op or a serialization on set 1's
+  // stream may be one, so the context's stream waits for that stream first (join_all); a pooled buffer
+  // that is freed goes through hipFree, which waits for the device.
+  CHK(join_all(&c));
   for (DevBuf* d : {&b->keys, &b->desc, &b->bm, &b->key_off, &b->bm_off, &b->payload, &b->ro_stats,
                     &b->bsi_tasks, &b->bsi_nt, &b->bsi_table, &b->rd_cum, &b->rd_off, &b->rd_aux})
     pool_put(&c, *d);
@@ -674,19 +676,19 @@ int rbg_ctx_batch_fetch_range(rbg_ctx* ctx, int32_t batch, size_t first, size_t 
 }
 int rbg_ctx_pairwise(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib) {
   Ctx* c;
-  CHK(session(ctx, &c));
+  CHK(session(ctx, &c, false));
   return ctx_pairwise(c, op, a, ia, b, ib, false);
 }
 int rbg_ctx_pairwise_serialized(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib) {
   Ctx* c;
-  CHK(session(ctx, &c));
+  CHK(session(ctx, &c, false));
   if (op < 0 || op > 3) return RBG_ERR_ILLEGAL_ARGUMENT;
   CHK(ctx_pairwise(c, op, a, ia, b, ib, false));
   return ctx_serialize(c);
 }
 int rbg_ctx_pairwise_range(rbg_ctx* ctx, int op, int32_t a, size_t ia, int32_t b, size_t ib, int key_lo, int key_hi) {
   Ctx* c;
-  CHK(session(ctx, &c));
+  CHK(session(ctx, &c, false));
   if (key_lo > key_hi) return RBG_ERR_ILLEGAL_ARGUMENT;
   return ctx_pairwise(c, op, a, ia, b, ib, false, key_lo, key_hi);
 }
@@ -761,7 +763,7 @@ int rbg_ctx_wide_card(rbg_ctx* ctx, int op, int32_t batch, int key_lo, int key_h
     ResultInfo ri = {};
     ri.card32 = (uint32_t)hc;
     ri.long_card = hc;
-    HIPCHK(hipMemcpyAsync(c->info.p, &ri, sizeof(ri), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(c->r().info.p, &ri, sizeof(ri), hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
   }
   return RBG_OK;
@@ -800,7 +802,7 @@ int rbg_ctx_result_stats(rbg_ctx* ctx, int64_t* st) {
 }
 int rbg_ctx_serialize(rbg_ctx* ctx) {
   Ctx* c;
-  CHK(session(ctx, &c));
+  CHK(session(ctx, &c, false));
   return ctx_serialize(c);
 }
 int rbg_ctx_fetch(rbg_ctx* ctx, rbg_buffer* out) {
@@ -812,17 +814,18 @@ int rbg_ctx_result_layout_device(rbg_ctx* ctx, void* dst3) {
   Ctx* c;
   CHK(session(ctx, &c));
   if (!dst3) return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (c->last != 1) {
+  if (c->r().last != 1) {
     set_err("no materialised result pending");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  if (c->place_pending) {  // the placement writes the layout too (one launch fewer per sharded step)
-    OutCtx o = c->pending;
+  CHK(join_result(c));
+  if (c->r().place_pending) {  // the placement writes the layout too (one launch fewer per sharded step)
+    OutCtx o = c->r().pending;
     o.layout_out = reinterpret_cast<int64_t*>(dst3);
-    launch_place(c->stream, c->ntasks.as<uint32_t>(), o, c->info.as<ResultInfo>());
-    c->place_pending = false;
+    launch_place(c->stream, c->r().ntasks.as<uint32_t>(), o, c->r().info.as<ResultInfo>());
+    c->r().place_pending = false;
   } else {
-    launch_layout_out(c->stream, c->info.as<ResultInfo>(), reinterpret_cast<int64_t*>(dst3));
+    launch_layout_out(c->stream, c->r().info.as<ResultInfo>(), reinterpret_cast<int64_t*>(dst3));
   }
   HIPCHK(hipGetLastError());
   return RBG_OK;
@@ -832,19 +835,20 @@ int rbg_ctx_fetch_shard_device_dyn(rbg_ctx* ctx, const void* layout, int rank, i
   CHK(session(ctx, &c));
   if (!layout || !out || world < 1 || world > 1024 || rank < 0 || rank >= world)
     return RBG_ERR_ILLEGAL_ARGUMENT;
-  if (c->last != 1) {
+  if (c->r().last != 1) {
     set_err("no materialised result pending");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
+  CHK(join_result(c));
   CHK(ensure_placed(c));
   // an already serialized result's pass-through records may point into released operands: copy its
   // payload region instead (like rbg_ctx_fetch_shard_device); not expected on the sharded path
-  if (c->serialized) {
+  if (c->r().serialized) {
     set_err("fetch_shard_device_dyn: the result was already serialized; fetch it before releasing operands "
             "or use rbg_ctx_fetch_shard_device");
     return RBG_ERR_ILLEGAL_ARGUMENT;
   }
-  launch_serialize_shard_dyn(c->stream, grid_for((c->pending_ub + 255) / 256, 256), c->ntasks.as<uint32_t>(), c->pending,
+  launch_serialize_shard_dyn(c->stream, grid_for((c->r().pending_ub + 255) / 256, 256), c->r().ntasks.as<uint32_t>(), c->r().pending,
                              reinterpret_cast<const int64_t*>(layout), rank, world, (uint8_t*)out, (uint8_t*)runb, true);
   HIPCHK(hipGetLastError());
   return RBG_OK;

@@ -915,7 +915,7 @@ static int ctx_bsi(Ctx* c, int32_t id, int op, int nbits, int has_found, int32_t
   const size_t ub = std::min<size_t>(kMaxKeys, std::max<size_t>(B->n_ctr, 1));
   OutCtx oc;
   CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser, &oc, op == BSI_SUM_ONLY));
-  c->pending_src = {id};
+  c->r().pending_src = {id};
   const uint32_t need = mode == -1 ? 0xFFFFFFFFu : (op == BSI_SUM_ONLY ? (uint32_t)(nbits + 1) : 0u);
   BsiScratch sc{};
   if (mode >= 0 && mode <= BSI_RANGE) {
@@ -935,8 +935,8 @@ static int ctx_bsi(Ctx* c, int32_t id, int op, int nbits, int has_found, int32_t
   wa.bm = B->bm.as<uint32_t>();
   wa.payload = B->payload.as<uint8_t>();
   c->mark(0);
-  Task* tasks = c->tasks.as<Task>();
-  uint32_t* nt = c->ntasks.as<uint32_t>();
+  Task* tasks = c->r().tasks.as<Task>();
+  uint32_t* nt = c->r().ntasks.as<uint32_t>();
   if (sc.defer && bsi_reg_path(mode, nbits)) {
     // The task list (keys where ebM has a container) and the input table depend on the batch
     // only: planned once per batch, kept with it (RoaringBitmapSliceIndex queries on one index,
@@ -960,7 +960,7 @@ static int ctx_bsi(Ctx* c, int32_t id, int op, int nbits, int has_found, int32_t
     sc.ztile = c->ztile;
     sc.zsums = c->bsi_sums.as<unsigned long long>();
     sc.nt_src = nt;
-    sc.nt_dst = c->ntasks.as<uint32_t>();
+    sc.nt_dst = c->r().ntasks.as<uint32_t>();
   } else {
     launch_plan_bsi(s, B->key_off.as<uint32_t>(), B->bm.as<uint32_t>(), need, c->by_key.as<Task>(),
                     c->flag.as<uint8_t>(), c->wg_count.as<uint32_t>(), c->zlb, c->ztile,
@@ -973,7 +973,7 @@ static int ctx_bsi(Ctx* c, int32_t id, int op, int nbits, int has_found, int32_t
              sc.defer ? &sc : nullptr, want_sum ? c->bsi_sums_dst : nullptr);
   c->mark(2);
   if (op == BSI_SUM_ONLY) {
-    c->last = 0;
+    c->r().last = 0;
   } else {
     defer_place(c);
   }
@@ -1094,13 +1094,13 @@ static int ctx_bsi_buffer(Ctx* c, int32_t id, int op, int nbits, int has_found, 
   return with_big_runs(c, true, "bsi", [&](const BigRuns& big) -> int {
     OutCtx oc;
     CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser + big.cap, &oc, false));
-    c->pending_src = {id};
+    c->r().pending_src = {id};
     const uint32_t need = mode == -1 ? 0xFFFFFFFFu : 0xFFFFFFFEu;  // every key of any input
     c->mark(0);
     launch_plan_bsi(s, B->key_off.as<uint32_t>(), B->bm.as<uint32_t>(), need, c->by_key.as<Task>(),
                     c->flag.as<uint8_t>(), c->wg_count.as<uint32_t>(), c->zlb, c->ztile, nullptr, nullptr);
-    launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(), c->tasks.as<Task>(),
-                   c->ntasks.as<uint32_t>());
+    launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(), c->r().tasks.as<Task>(),
+                   c->r().ntasks.as<uint32_t>());
     c->mark(1);
     WideArgs wa{};
     wa.desc = B->desc.as<CDesc>();
@@ -1123,15 +1123,15 @@ static int ctx_bsi_buffer(Ctx* c, int32_t id, int op, int nbits, int has_found, 
       CHK(c->owen_keys.ensure(4 * ub));
       p.owen_tb = c->owen_tb.p;
       p.task_keys = c->owen_keys.as<uint32_t>();
-      launch_bsi_owen_pre(s, grid, c->tasks.as<Task>(), c->ntasks.as<uint32_t>(), wa, p);
+      launch_bsi_owen_pre(s, grid, c->r().tasks.as<Task>(), c->r().ntasks.as<uint32_t>(), wa, p);
       HIPCHK(hipGetLastError());
       uint32_t nt = 0;
-      HIPCHK(hipMemcpyAsync(&nt, c->ntasks.p, 4, hipMemcpyDeviceToHost, s));
+      HIPCHK(hipMemcpyAsync(&nt, c->r().ntasks.p, 4, hipMemcpyDeviceToHost, s));
       HIPCHK(hipStreamSynchronize(s));
       CHK(owen_order(c, M, nt));
       p.owen_order = c->owen_ord.as<uint8_t>();
     }
-    if (mode >= 0) launch_bsi_buf(s, grid, c->tasks.as<Task>(), c->ntasks.as<uint32_t>(), wa, p, oc);
+    if (mode >= 0) launch_bsi_buf(s, grid, c->r().tasks.as<Task>(), c->r().ntasks.as<uint32_t>(), wa, p, oc);
     return op_end(c);
   });
 }

@@ -103,8 +103,9 @@ int synth_c3(Ctx* c, int kind, uint64_t seed, size_t n, int key_lo, int key_hi, 
   CHK(b.bm_off.ensure(8));
   HIPCHK(hipMemcpyAsync(b.key_off.p, key_off.data(), 4 * (kMaxKeys + 1), hipMemcpyHostToDevice, s));
   if (kind == 1) {
-    CHK(c->scratch.ensure(16 * (size_t)kMaxKeys));
-    unsigned long long* kb = c->scratch.as<unsigned long long>();
+    CHK(main_set(c));  // set 0's scratch is borrowed
+    CHK(c->r().scratch.ensure(16 * (size_t)kMaxKeys));
+    unsigned long long* kb = c->r().scratch.as<unsigned long long>();
     launch_synth_c3u(s, seed, (uint32_t)n, key_lo, nkeys, kb, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
     std::vector<unsigned long long> bytes(nkeys + 1, 0);
     if (nkeys) HIPCHK(hipMemcpyAsync(bytes.data(), kb, 8 * nkeys, hipMemcpyDeviceToHost, s));
@@ -225,8 +226,9 @@ int synth_c5(Ctx* c, uint64_t seed, size_t rows, int key_lo, int key_hi, int32_t
   const int nkeys = std::max(0, key_hi - key_lo);
   hipStream_t s = c->stream;
   const size_t G = (size_t)nkeys * nin;
-  CHK(c->scratch.ensure(8 * G + 64));
-  uint32_t* cards = c->scratch.as<uint32_t>();
+  CHK(main_set(c));  // set 0's scratch is borrowed
+  CHK(c->r().scratch.ensure(8 * G + 64));
+  uint32_t* cards = c->r().scratch.as<uint32_t>();
   uint32_t* pos = cards + G;
   unsigned int* mm = reinterpret_cast<unsigned int*>(c->scalar.p);
   const unsigned int mm0[2] = {0xFFFFFFFFu, 0u};

@@ -159,24 +159,24 @@ static int ctx_pq(Ctx* c, int op, Batch* B, int32_t id, int key_lo, int key_hi) 
   const size_t ub = std::min<size_t>(kMaxKeys, std::max<size_t>(B->n_ctr, 1));
   OutCtx oc;
   CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser, &oc, false));
-  c->pending_src = {id};
+  c->r().pending_src = {id};
   c->mark(0);
   // one task per union key (an empty aggregate has none: new RoaringBitmap())
   launch_plan_wide(s, N ? 0 : 1, B->key_off.as<uint32_t>(), N ? (uint32_t)N : 0xFFFFFFFFu, 0, kMaxKeys,
                    c->by_key.as<Task>(), c->flag.as<uint8_t>(), c->wg_count.as<uint32_t>(), c->zlb, c->ztile);
-  launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(), c->tasks.as<Task>(),
-                 c->ntasks.as<uint32_t>());
+  launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(), c->r().tasks.as<Task>(),
+                 c->r().ntasks.as<uint32_t>());
   c->mark(1);
   if (!N) {
     c->mark(2);
-    launch_place(s, c->ntasks.as<uint32_t>(), oc, c->info.as<ResultInfo>());
-    c->last = 1;
+    launch_place(s, c->r().ntasks.as<uint32_t>(), oc, c->r().info.as<ResultInfo>());
+    c->r().last = 1;
     c->mark(3);
     HIPCHK(hipGetLastError());
     return RBG_OK;
   }
   uint32_t h_nt = 0;
-  HIPCHK(hipMemcpyAsync(&h_nt, c->ntasks.p, 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(&h_nt, c->r().ntasks.p, 4, hipMemcpyDeviceToHost, s));
   std::vector<unsigned long long> leaf(N);
   DevBuf dsz;
   CHK(dsz.ensure(8 * N));
@@ -195,7 +195,7 @@ static int ctx_pq(Ctx* c, int op, Batch* B, int32_t id, int key_lo, int key_hi) 
   const size_t stride = std::max<uint32_t>(h_nt, 1);
   const size_t st_bytes = n_slots * stride * sizeof(PQState);
   std::vector<Task> h_tasks(h_nt);
-  if (h_nt) HIPCHK(hipMemcpyAsync(h_tasks.data(), c->tasks.p, sizeof(Task) * h_nt, hipMemcpyDeviceToHost, s));
+  if (h_nt) HIPCHK(hipMemcpyAsync(h_tasks.data(), c->r().tasks.p, sizeof(Task) * h_nt, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   std::vector<uint32_t> kbase(stride, 0);
   std::vector<int32_t> ktop(stride, 0);
@@ -293,13 +293,13 @@ static int ctx_pq(Ctx* c, int op, Batch* B, int32_t id, int key_lo, int key_hi) 
   const PQArgs pa{B->desc.as<CDesc>(), B->bm.as<uint32_t>(), B->payload.as<uint8_t>()};
   const int grid = grid_for(h_nt, 65536);
   for (size_t k = 0; k + 1 < N; k++) {
-    launch_pq_step(s, grid, c->tasks.as<Task>(), c->ntasks.as<uint32_t>(), pa, D);
+    launch_pq_step(s, grid, c->r().tasks.as<Task>(), c->r().ntasks.as<uint32_t>(), pa, D);
     if ((k & 1023) == 1023) HIPCHK(hipGetLastError());
   }
   c->mark(2);
-  launch_pq_final(s, grid, c->tasks.as<Task>(), c->ntasks.as<uint32_t>(), pa, op == RBG_WIDE_PQ_OR ? 1 : 0, D, oc);
+  launch_pq_final(s, grid, c->r().tasks.as<Task>(), c->r().ntasks.as<uint32_t>(), pa, op == RBG_WIDE_PQ_OR ? 1 : 0, D, oc);
   HIPCHK(hipGetLastError());
-  launch_place(s, c->ntasks.as<uint32_t>(), oc, c->info.as<ResultInfo>());
+  launch_place(s, c->r().ntasks.as<uint32_t>(), oc, c->r().info.as<ResultInfo>());
   PQCtl done{};
   HIPCHK(hipMemcpyAsync(&done, mb, sizeof(done), hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));  // the temps are freed on return
@@ -308,7 +308,7 @@ static int ctx_pq(Ctx* c, int op, Batch* B, int32_t id, int key_lo, int key_hi) 
                      : std::string("priorityqueue: the device queue did not finish"));
     return done.err ? RBG_ERR_OUT_OF_MEMORY : RBG_ERR_DEVICE;
   }
-  c->last = 1;
+  c->r().last = 1;
   c->mark(3);
   HIPCHK(hipGetLastError());
   return RBG_OK;
@@ -384,7 +384,8 @@ int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const int32_t* 
       const int64_t cc = N ? B->h_bm_card[0] : 0;
       *host_card_out = (int32_t)(uint32_t)(uint64_t)cc;
       *host_card_valid = true;
-      c->last = 2;
+      CHK(main_set(c));  // no op bracket: set 0's `last` changes
+      c->r().last = 2;
       return RBG_OK;
     }
     if (op == RBG_WIDE_CARD_AND && N >= 2) {
@@ -454,8 +455,8 @@ int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const int32_t* 
     CHK(prepare_output(c, ub, kStagedMax * ub + B->max_ser + big.cap, &oc, card_only));
     // OR results are bitmaps whenever more than 4096 values survive: write those in place
     // (8192 t < kStagedMax ub, inside the payload region)
-    if (!card_only && (mode == WIDE_OR || mode == WIDE_LAZY_CHAIN)) oc.spec = c->pending.spec = 1;
-    c->pending_src = {id};
+    if (!card_only && (mode == WIDE_OR || mode == WIDE_LAZY_CHAIN)) oc.spec = c->r().pending.spec = 1;
+    c->r().pending_src = {id};
     if (!skip.empty()) {
       CHK(c->skip.ensure(skip.size()));
       HIPCHK(hipMemcpyAsync(c->skip.p, skip.data(), skip.size(), hipMemcpyHostToDevice, s));
@@ -464,8 +465,8 @@ int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const int32_t* 
     c->mark(0);
     launch_plan_wide(s, plan_mode == 0 ? 0 : 1, B->key_off.as<uint32_t>(), n_req, key_lo, key_hi,
                      c->by_key.as<Task>(), c->flag.as<uint8_t>(), c->wg_count.as<uint32_t>(), c->zlb, c->ztile);
-    launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(), c->tasks.as<Task>(),
-                   c->ntasks.as<uint32_t>());
+    launch_compact(s, c->flag.as<uint8_t>(), c->by_key.as<Task>(), c->wg_count.as<uint32_t>(), c->r().tasks.as<Task>(),
+                   c->r().ntasks.as<uint32_t>());
     WideArgs wa{};
     wa.desc = B->desc.as<CDesc>();
     wa.bm = B->bm.as<uint32_t>();
@@ -481,12 +482,12 @@ int ctx_wide(Ctx* c, int op, int32_t id, int key_lo, int key_hi, const int32_t* 
     wa.buffer = buffer ? 1u : 0u;
     wa.big = big;
     c->mark(1);
-    launch_wide(s, mode, grid_for(ub, 65536), c->tasks.as<Task>(), c->ntasks.as<uint32_t>(), wa, oc,
-                c->task_card.as<uint32_t>());
+    launch_wide(s, mode, grid_for(ub, 65536), c->r().tasks.as<Task>(), c->r().ntasks.as<uint32_t>(), wa, oc,
+                c->r().task_card.as<uint32_t>());
     c->mark(2);
     if (card_only) {
-      launch_reduce_card(s, c->task_card.as<uint32_t>(), c->ntasks.as<uint32_t>(), c->info.as<ResultInfo>(), oc.err);
-      c->last = 2;
+      launch_reduce_card(s, c->r().task_card.as<uint32_t>(), c->r().ntasks.as<uint32_t>(), c->r().info.as<ResultInfo>(), oc.err);
+      c->r().last = 2;
     } else {
       defer_place(c);
     }
