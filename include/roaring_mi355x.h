@@ -709,5 +709,8 @@ int rbg_ctx_fetch_shard_device_dyn(rbg_ctx* ctx, const void* layout, int rank, i
 /* The same index built on the GPU from a value tensor (RangeBitmap.Appender), and a resident index written
  * back out as the reference's stream. */
 #include "roaring_mi355x_rangebitmap_build.h"
+/* Batches of values added to or removed from a bitmap, resident or serialized (RoaringBitmap.add(int...) / addN
+ * / remove(int) / checkedAdd / checkedRemove), with the reference's container types, run containers included. */
+#include "roaring_mi355x_mutate.h"
 
 #endif /* ROARING_MI355X_H */

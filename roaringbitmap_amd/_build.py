@@ -39,15 +39,18 @@ SOURCES = [
     "bsiset.hip",
     "bsiin.hip",
     "bsitr.hip",
+    "mutate.hip",
     "engine.cpp",
     "engine_load.cpp",
     "engine_wide.cpp",
     "engine_bsi.cpp",
     "engine_synth.cpp",
     "engine_rangebitmap.cpp",
+    "engine_mutate.cpp",
     "engine_api.cpp",
     "format.cpp",
     "rangebitmap_format.cpp",
+    "mutate_host.cpp",
 ]
 HEADERS = ["device.hpp", "kernels.hpp", "format.hpp", "wave.hpp", "vb.hpp", "bsival.hpp", "engine.hpp", "build.hpp",
            "rangebitmap_format.hpp"]
@@ -65,7 +68,8 @@ def build(verbose=False, jobs=8):
     dep_time = max([_mtime(os.path.join(CSRC, h)) for h in HEADERS] + [_mtime(__file__)]
                    + [_mtime(os.path.join(inc, h)) for h in ("roaring_mi355x.h", "roaring_mi355x_bitset.h",
                                                              "roaring_mi355x_rangebitmap.h",
-                                                             "roaring_mi355x_rangebitmap_build.h")])
+                                                             "roaring_mi355x_rangebitmap_build.h",
+                                                             "roaring_mi355x_mutate.h")])
     procs, objs = [], []
     for src in SOURCES:
         sp = os.path.join(CSRC, src)

@@ -197,6 +197,16 @@ RANGEBITMAP_BUILD_SIGNATURES = {
     "rbg_rangebitmap_reserialize": (ci, [u8p, sz, buf]),
 }
 
+# Every entry point of include/roaring_mi355x_mutate.h (batches of values added to or removed from a bitmap),
+# which roaring_mi355x.h includes, in that file's order.
+RBG_MUT_ADD, RBG_MUT_REMOVE = 0, 1
+MUTATE_SIGNATURES = {
+    "rbg_ctx_mutate_values": (ci, [vp, i32, ci, u32p, sz, i32p, u64p]),
+    "rbg_ctx_mutate_values_device": (ci, [vp, i32, ci, vp, sz, i32p, u64p]),
+    "rbg_mutate_values": (ci, [u8p, sz, ci, u32p, sz, buf, u64p]),
+    "rbg_mutate_values_host": (ci, [u8p, sz, ci, u32p, sz, buf, u64p]),
+}
+
 _lib = None
 
 
@@ -210,7 +220,7 @@ def lib():
                 "(the engine has no CPU fallback)")
         L = ctypes.CDLL(LIB_PATH)
         for name, (restype, argtypes) in {**SIGNATURES, **BITSET_SIGNATURES, **RANGEBITMAP_SIGNATURES,
-                                          **RANGEBITMAP_BUILD_SIGNATURES}.items():
+                                          **RANGEBITMAP_BUILD_SIGNATURES, **MUTATE_SIGNATURES}.items():
             f = getattr(L, name)
             f.restype, f.argtypes = restype, argtypes
         _lib = L

@@ -5,6 +5,7 @@
 //   engine_wide.cpp   the aggregations (FastAggregation's dispatch, the horizontal and priority-queue forms)
 //   engine_bsi.cpp    every bit-sliced-index pipeline and its entry points
 //   engine_rangebitmap.cpp  the range-encoded index: load, build from values, serialize, queries, counts
+//   engine_mutate.cpp  batches of values added to or removed from a resident bitmap, and their entry points
 //   engine_synth.cpp  the bench workload synthesizers
 //   engine_api.cpp    the exported C ABI
 // What is declared here is defined once; what no other unit calls stays static in its own.
@@ -211,6 +212,10 @@ struct Ctx {
   DevBuf bsib_pkeys, bsib_pkoff, bsib_info, bsib_size, bsib_part, bsib_per;
   DevBuf rbb_info, rbb_size, rbb_part;  // a range-encoded index from values (rangebitmap_build.hip): the plan's cell
                                         // table, the cells' slot sizes (scanned in place), scan scratch
+  // values added to or removed from a resident bitmap (mutate.hip): the second key scan's flags, both scans' keys
+  // and CSRs, the counters, per cell was_run and the old cardinality, the plan's table, the size words (scanned
+  // in place) and scan scratch
+  DevBuf mut_flag, mut_keys, mut_off, mut_sc, mut_run, mut_card, mut_info, mut_size, mut_part;
   DevBuf bsia_run;  // the sum of two indexes (bsiadd.hip): per present key, ebM' is a full run container
   // parallelTransposeWithCount (bsitr.hip): the candidate input keys and their CSR, the result-key flags, per
   // result key its distinct values and whether it is full

@@ -640,6 +640,32 @@ void launch_bsis_last(hipStream_t s, const uint32_t* col, uint64_t n, const uint
 void launch_bsis_apply(hipStream_t s, const uint32_t* col, const int32_t* val, uint64_t n, const uint32_t* pkey_off,
                        uint32_t k_lo, uint32_t k_hi, int m, const uint32_t* tab, uint32_t* ws);
 
+// mutate.hip: a batch of values added to (op 0) or removed from (op 1) a resident bitmap, RoaringBitmap.add(int...)
+// / addN / remove(int) (RB/RoaringBitmap.java:483-570, 2637-2648).  a: the operand (n == 0: an empty bitmap, whose
+// key CSR is not read).  touched: launch_bld_keys' flags over the values.
+// flag[key] = touched | present (add), touched & present (remove): the input of the second key scan
+void launch_mut_flags(hipStream_t s, const uint8_t* touched, const uint32_t* a_key_off, bool a_has, int op,
+                      uint8_t* flag);
+// cell_keys / cell_off: the keys with an 8 KiB cell and their CSR (65,537 entries; a key has a cell iff its two
+// entries differ); writes every cell of ws, was_run[] and old_card[]
+void launch_mut_expand(hipStream_t s, BmView a, const uint16_t* cell_keys, uint32_t n_cells, uint8_t* ws,
+                       uint8_t* was_run, uint32_t* old_card);
+// v is read once more here: it must not have changed since launch_bld_keys
+void launch_mut_apply(hipStream_t s, const uint32_t* v, uint64_t n, int op, const uint32_t* cell_off, uint32_t* ws);
+constexpr size_t kMutInfoBytes = 8;  // per candidate key: the plan's (card, nruns, kind, kept / touched)
+// a candidate's size word: 1 << kMutCountShift | slot bytes when kept, else 0; one scan places both (a batch
+// holds at most 65,536 slots of at most 131,088 B)
+constexpr int kMutCountShift = 44;
+// cand_keys: the keys the result may hold, ascending.  totals (7 u64, zeroed by the caller) += {#A, #B, #R,
+// serialized payload bytes, cardinality, values added or removed, serialized bytes of containers above 8,194 B}
+void launch_mut_plan(hipStream_t s, BmView a, const uint16_t* cand_keys, uint64_t n_cand, const uint32_t* cell_off,
+                     const uint8_t* ws, const uint8_t* was_run, const uint32_t* old_card, void* info, uint64_t* size,
+                     unsigned long long* totals);
+// off: the exclusive scan of size[]; n_out: the kept keys; also writes bm_off = {0, n_out}
+void launch_mut_write(hipStream_t s, BmView a, const uint16_t* cand_keys, uint64_t n_cand, uint32_t n_out,
+                      const uint32_t* cell_off, const uint8_t* ws, const void* info, const uint64_t* off, CDesc* desc,
+                      uint16_t* keys, uint32_t* bm, uint32_t* bm_off, uint8_t* payload);
+
 // bsival.hip: values out of a key-major batch [ebM, bA[0..nbits-1], foundSet?]
 struct BsiValArgs {
   const uint32_t* key_off;  // the batch's key CSR (65,537 entries)

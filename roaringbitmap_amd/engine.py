@@ -347,6 +347,39 @@ class Engine:
                                         int(bool(run_optimize)), ctypes.byref(out)))
         return out.value
 
+    def mutate_values(self, batch, values, remove=False):
+        """A batch of values added to (remove=False: RoaringBitmap.add(int...) / addN, RB/RoaringBitmap.java
+        :483-570) or removed from (remove=True: remove(int) value by value, :2637-2648) a resident bitmap, on the
+        device (rbg_ctx_mutate_values) -> (batch id, changed): a new one-bitmap batch, the same as load of the
+        reference's bitmap after the calls (a run container stays a run container, an emptied one is dropped, an
+        untouched one keeps its bytes), and the number of values actually added or removed (the checkedAdd /
+        checkedRemove hits).  The operand stays as it is.  Only the keys the values touch are expanded.  Values
+        as from_values takes them: a numpy array or sequence below 2^32 is uploaded; a torch int64 (low 32 bits)
+        or uint32 tensor on this engine's GPU is read in place (rbg_ctx_mutate_values_device) with point_query's
+        stream handshake.  Synchronous either way."""
+        out = ctypes.c_int32()
+        changed = ctypes.c_uint64()
+        op = _lib.RBG_MUT_REMOVE if remove else _lib.RBG_MUT_ADD
+        if is_torch(values):
+            v = self._words("mutate_values", values, ("int64", "uint32"))
+            done = self._handshake(values.device)
+            check(lib().rbg_ctx_mutate_values_device(self._ctx, int(batch), op, _dptr(v), v.numel(), ctypes.byref(out),
+                                                     ctypes.byref(changed)))
+            done()
+            return out.value, int(changed.value)
+        v = as_u32(values)
+        check(lib().rbg_ctx_mutate_values(self._ctx, int(batch), op, v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)),
+                                          v.size, ctypes.byref(out), ctypes.byref(changed)))
+        return out.value, int(changed.value)
+
+    def add_values(self, batch, values):
+        """mutate_values(batch, values, remove=False)"""
+        return self.mutate_values(batch, values, False)
+
+    def remove_values(self, batch, values):
+        """mutate_values(batch, values, remove=True)"""
+        return self.mutate_values(batch, values, True)
+
     def to_values(self, batch, ia=0, first=0, count=None, dtype=None):
         """The values of ranks [first, first + count) of a resident bitmap (count None: to the end), ascending
         and unsigned: toArray() and the window BatchIterator.nextBatch / limit walk (rbg_ctx_to_values).

@@ -148,8 +148,11 @@ class _RangeMut:
     class `cls`.  With two arguments on an instance of `cls`: x.add / remove / flip(rangeStart, rangeEnd) in
     place (RB/RoaringBitmap.java:1181-1206, 2656-2710, 1893-1925; RB/buffer/MutableRoaringBitmap.java
     :831-858, 1489, 1195): the in-place add runs Container.iadd on every key of the range (its own
-    typing, RBG_RMUT_ADD_INPLACE), the in-place remove / flip end in the static forms' containers.  The
-    single-value forms x.add(int) / remove(int) / flip(int) are not on this path."""
+    typing, RBG_RMUT_ADD_INPLACE), the in-place remove / flip end in the static forms' containers.
+    On a plain RoaringBitmap the calls that Java resolves to the value forms go to add_many / remove_many:
+    x.remove(v) with one int (remove(int), :2637-2648) and x.add(a, b, c, ...) with three or more ints
+    (add(int... dat), :483).  Java picks add(long, long) for two ints (widening comes before varargs), so
+    x.add(a, b) stays the range form.  x.add(v) with one int and flip(int) are not offered."""
 
     def __init__(self, op, buffer=False, cls=None):
         self.op, self.buffer, self.cls = op, buffer, cls
@@ -166,6 +169,15 @@ class _RangeMut:
             return self.static
 
         def call(*args):
+            # Java's overloads by argument count, for ints on a plain RoaringBitmap: remove(int) takes one,
+            # add(int...) three or more; two ints are add / remove(long rangeStart, long rangeEnd) below
+            values = type(obj) is RoaringBitmap and all(isinstance(a, (int, np.integer)) for a in args)
+            if values and self.op == "remove" and len(args) == 1:
+                obj.remove_many(args)
+                return None
+            if values and self.op == "add" and len(args) >= 3:
+                obj.add_many(args)
+                return None
             if len(args) == 3:
                 return self.static(*args)
             if len(args) == 2 and isinstance(obj, self.cls or RoaringBitmap):
@@ -173,7 +185,8 @@ class _RangeMut:
                 obj._lcard = None
                 return None
             raise NotImplementedError(f"{type(obj).__name__}.{self.op}{args}: the range forms "
-                                      f"{self.op}(rb, rangeStart, rangeEnd) and x.{self.op}(rangeStart, rangeEnd)")
+                                      f"{self.op}(rb, rangeStart, rangeEnd) and x.{self.op}(rangeStart, rangeEnd); "
+                                      "x.remove(v), x.add(a, b, c, ...), checkedAdd / checkedRemove, add_many / remove_many take values")
         return call
 
 
@@ -433,6 +446,50 @@ class RoaringBitmap:
     add = _RangeMut("add")
     remove = _RangeMut("remove")
     flip = _RangeMut("flip")
+
+    # ---- batches of values added or removed, in place on this object -------------------------------------
+    def _mutate(self, values, remove, gpu):
+        v = as_u32(values)
+        changed = ctypes.c_uint64()
+        f = lib().rbg_mutate_values if gpu else lib().rbg_mutate_values_host
+        self._buf = call_bytes(lambda *a: f(*a, ctypes.byref(changed)), self._buf, len(self._buf),
+                               _lib.RBG_MUT_REMOVE if remove else _lib.RBG_MUT_ADD,
+                               v.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), v.size)
+        self._lcard = None
+        return int(changed.value)
+
+    def add_many(self, values, gpu=False) -> int:
+        """x.add(int... dat) (RB/RoaringBitmap.java:483; addN :498-570) in place, with the reference's container
+        types: an array or bitmap container by its final cardinality, a run container stays one
+        (RunContainer.add, RB/RunContainer.java:248-302), a key no value touches keeps its bytes.  Values are
+        taken as unsigned 32-bit, in any order, duplicates allowed.  Host by default (rbg_mutate_values_host, no
+        device); gpu=True: the one-shot on the device (rbg_mutate_values), the same bytes.  -> the number of
+        values that were not there before (the checkedAdd hits, :1610)."""
+        return self._mutate(values, False, gpu)
+
+    def remove_many(self, values, gpu=False) -> int:
+        """x.remove(v) (RB/RoaringBitmap.java:2637-2648) for every value, in place: a run container stays one
+        (RunContainer.remove, RB/RunContainer.java:2038-2070), an emptied container is dropped.  -> the number
+        of values that were there (the checkedRemove hits, :1646)."""
+        return self._mutate(values, True, gpu)
+
+    def addN(self, dat, offset, n):
+        """x.addN(dat, offset, n) (RB/RoaringBitmap.java:498-570) with its three argument checks"""
+        if n < 0 or offset < 0:
+            raise _lib.IllegalArgumentException("Negative values do not make sense.")
+        if n == 0:
+            return  # nothing to do
+        if offset + n > len(dat):
+            raise _lib.IllegalArgumentException("Data source is too small.")
+        self._mutate(dat[offset:offset + n], False, False)
+
+    def checkedAdd(self, x) -> bool:
+        """x.checkedAdd(v) (RB/RoaringBitmap.java:1610): True iff v was not there"""
+        return self._mutate([x], False, False) == 1
+
+    def checkedRemove(self, x) -> bool:
+        """x.checkedRemove(v) (RB/RoaringBitmap.java:1646): True iff v was there"""
+        return self._mutate([x], True, False) == 1
 
     @classmethod
     def bitmapOfRange(cls, range_min, range_max):
@@ -962,6 +1019,7 @@ class ImmutableRoaringBitmap(RoaringBitmap):
     or_ = _s_or
     xor = _s_xor
     add = remove = None  # no static add / remove on ImmutableRoaringBitmap (MutableRoaringBitmap's: below)
+    add_many = remove_many = addN = checkedAdd = checkedRemove = None  # the plain RoaringBitmap's alone
     addOffset = None  # MutableRoaringBitmap.addOffset(ImmutableRoaringBitmap, long): below
     removeRunCompression = None  # in place: MutableRoaringBitmap's (RB/buffer/MutableRoaringBitmap.java:1568)
     andCardinality = RoaringBitmap.__dict__["andCardinality"]  # :336-359, a set-level count
